@@ -11,6 +11,8 @@ At N = 1 the same line also carries "sw": shallow-water time steps/s (the second
 and "column": HEVI column Schur solves/s on the same grid (--no-column skips it).
 Prints ONE compact JSON line (rank 0, < 4 KB: compact_record -- the contract's keys, roofline, roofline_cold, cpu_baseline(+_column,
 +_sw) and one-number summaries); the full object with every extra goes to bench_extras.json (repo root and gpurun_out/).
+--dump-outputs DIR writes the result of the last timed step (y of the Umat apply, float64) to DIR/umat_y.npy (N > 1: each rank its
+own patches, DIR/umat_y_rank<r>.npy); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 `python bench.py --gpus N` started without WORLD_SIZE launches its own N ranks as a child torch.distributed.run.  roofline: dominant kernel k_elem_apply<3,UMAT>, HIP-event timed inside the timed
 region, against the launch's COMPULSORY bytes (b1_launch_bytes: frac <= 1 by construction; SURVEY 8(d)'s per-unit
 figure rides along as `algorithmic_reference` only).  The headline workload is Infinity-Cache resident
@@ -943,6 +945,18 @@ def write_extras(out):
     return written
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: {name: tensor} -> d/<name>.npy in float64 (64 MB at most in all)"""
+    host = {k: v.detach().cpu().numpy().astype(np.float64, copy=False) for k, v in arrays.items()}
+    assert sum(h.nbytes for h in host.values()) <= DUMP_CAP_BYTES, "outputs exceed the dump cap"
+    os.makedirs(d, exist_ok=True)
+    for k, h in host.items():
+        np.save(os.path.join(d, k + ".npy"), h)
+
+
 def emit(out):
     ef = write_extras(out)
     _, line = compact_record(out, ef)
@@ -986,6 +1000,8 @@ def main():
     ap.add_argument("--cold", type=int, default=8, metavar="R",
                     help="roofline_cold (not the headline value): the same step on R independent copies of the sphere, "
                          "working set >> the 256 MiB Infinity Cache, i.e. genuinely HBM-resident; 0 skips it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result (the Umat apply's y, float64) as DIR/<name>.npy")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1106,6 +1122,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if a.dump_outputs:
+        # what the caller of the timed step holds after its last step (N > 1: the rank's patches, shared edges complete)
+        dump_outputs(a.dump_outputs, {"umat_y" if world == 1 else "umat_y_rank%d" % rank: y})
     # `value` is the contract's number: EXACTLY `steps` steps, once.  At the driver's --steps 20 that is a 0.4 ms sample, so the same timed
     # region is repeated a few more times (same step count, same fences, max over ranks each) and the median is reported BESIDE it
     rep_dts = [dt]

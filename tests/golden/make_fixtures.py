@@ -4,6 +4,7 @@ container only; /root/reference does not travel to the GPU box, the .npz files d
 
   topo_*.npz / geom_*.npz : scr/Proc2.py (ParaCube) and scr/Geom2.py (init_geom), imported as-is.
   basis_linalg.npz        : eul/Basis.cpp + eul/LinAlg.cpp compiled in place (oracle/_ref, `make -C oracle ref`).
+  assembly_ref_linalg.npz : the oracle's assembly with those compiled dense kernels plugged in (oracle/_ref).
 
 Fixtures are data (inputs + expected outputs) only.  Usage: python tests/golden/make_fixtures.py
 """
@@ -90,6 +91,33 @@ def basis_linalg_fixture():
     np.savez_compressed(os.path.join(HERE, "basis_linalg.npz"), **out)
 
 
+def assembly_ref_linalg_fixture():
+    """the oracle's element matrices and one column operator assembled through the reference's compiled dense kernels
+    (oracle/_ref plugged in with use_reference_linalg), on a seeded p=3 2x2-element 2-level patch: inputs + outputs"""
+    from oracle import pyoracle
+    pyoracle.build(ref=True)
+    rng = np.random.default_rng(7)
+    P = pyoracle.Patch(3, 3, 2, 2)
+    det = rng.uniform(0.5, 2.0, (P.nEl, P.mp12)); J = rng.standard_normal((P.nEl, P.mp12, 4))
+    levels = np.cumsum(rng.uniform(1, 2, (3, P.n0q)), axis=0)
+    P.set_metric(det, J); P.set_levels(levels)
+    h2 = rng.standard_normal(P.n2); u1 = rng.standard_normal(P.n1); q0 = rng.standard_normal(P.n0)
+    rt = np.abs(rng.standard_normal(P.nk * P.n2e)) + 1.0
+    cases = [("UMAT", 1, None), ("WMAT", 1, None), ("UHMAT", 1, h2), ("ROTMAT", 0, q0), ("WTQUMAT", 0, u1),
+             ("WHMAT", 1, h2), ("PMAT", 0, None), ("WMATINV", 0, None), ("UTQWMAT", 0, u1)]
+    out = dict(det=det, J=J, levels=levels, h2=h2, u1=u1, q0=q0, rt=rt)
+    assert pyoracle.use_reference_linalg(True), "oracle/_ref not built"
+    try:
+        P2 = pyoracle.Patch(3, 3, 2, 2)
+        P2.set_metric(det, J); P2.thick[:] = P.thick; P2.thickInv[:] = P.thickInv
+        for op, fl, f in cases:
+            out[f"elmats_{op}"] = P2.op_elmats(op, 1, 1e8, fl, f)
+        out["colop_EOS_BLOCK"] = P2.colop_dense("EOS_BLOCK", 1, 0, f1=rt)
+    finally:
+        pyoracle.use_reference_linalg(False)
+    np.savez_compressed(os.path.join(HERE, "assembly_ref_linalg.npz"), **out)
+
+
 def box_fixture(pn, ne, n_procs, lx=1000.0):
     from ProcBox import ParaBox
     from GeomBox import init_geom as box_geom
@@ -143,4 +171,5 @@ if __name__ == "__main__":
     for pn, ne in [(3, 2), (3, 4), (4, 2), (2, 3)]:
         geom_fixture(pn, ne)
     basis_linalg_fixture()
+    assembly_ref_linalg_fixture()
     print("fixtures written to", HERE)

@@ -56,3 +56,16 @@ def test_compact_line_survives_failed_and_missing_extras():
     bare = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                 "vs_baseline", "dtype", "data", "config")}
     assert len(bench.compact_record(bare)[1]) < 1500
+
+
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    import numpy as np
+    import pytest
+    import torch
+    y = torch.arange(12, dtype=torch.float64).reshape(3, 4) / 7
+    bench.dump_outputs(str(tmp_path / "d"), {"umat_y": y})
+    back = np.load(tmp_path / "d" / "umat_y.npy")
+    assert back.dtype == np.float64 and np.array_equal(back, y.numpy())
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": torch.zeros(bench.DUMP_CAP_BYTES // 8 + 1, dtype=torch.float64)})
+    assert not (tmp_path / "e").exists()

@@ -81,22 +81,25 @@ def test_known_answers(oracle):
         assert np.allclose(w @ t["ejxi"], np.ones(n), atol=1e-13)
 
 
-def test_live_reference_library_matches(oracle):
-    """If oracle/_ref is built here, the whole assembly restatement is re-run with the reference's
-    compiled dense kernels plugged in and must not change by a single bit."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference on this box)")
-    rng = np.random.default_rng(7)
+def test_live_reference_library_matches(oracle, golden_dir):
+    """The whole assembly restatement re-run with the reference's compiled dense kernels plugged in must
+    not change by a single bit: against the stored result of that run (tests/golden/assembly_ref_linalg.npz),
+    and against the live oracle/_ref library as well where it is built."""
+    R = np.load(os.path.join(golden_dir, "assembly_ref_linalg.npz"))
+    det, J, h2, u1, q0, rt = (R[k] for k in ("det", "J", "h2", "u1", "q0", "rt"))
     P = oracle.Patch(3, 3, 2, 2)
-    det = rng.uniform(0.5, 2.0, (P.nEl, P.mp12)); J = rng.standard_normal((P.nEl, P.mp12, 4))
     P.set_metric(det, J)
-    P.set_levels(np.cumsum(rng.uniform(1, 2, (3, P.n0q)), axis=0))
-    h2 = rng.standard_normal(P.n2); u1 = rng.standard_normal(P.n1); q0 = rng.standard_normal(P.n0)
+    P.set_levels(R["levels"])
     cases = [("UMAT", 1, None), ("WMAT", 1, None), ("UHMAT", 1, h2), ("ROTMAT", 0, q0), ("WTQUMAT", 0, u1),
              ("WHMAT", 1, h2), ("PMAT", 0, None), ("WMATINV", 0, None), ("UTQWMAT", 0, u1)]
     own = [P.op_elmats(op, 1, 1e8, fl, f) for op, fl, f in cases]
-    rt = np.abs(rng.standard_normal(P.nk * P.n2e)) + 1.0
     own_col = P.colop_dense("EOS_BLOCK", 1, 0, f1=rt)
+    for (op, _, _), a in zip(cases, own):
+        assert np.array_equal(R[f"elmats_{op}"], a), op
+    assert np.array_equal(R["colop_EOS_BLOCK"], own_col)
+    assert own_col.shape == (P.nk * P.n2e, P.nk * P.n2e)
+    if oracle.ref_lib() is None:
+        return
     assert oracle.use_reference_linalg(True)
     try:
         P2 = oracle.Patch(3, 3, 2, 2)      # tables rebuilt through the reference's Tran_IP
@@ -106,4 +109,3 @@ def test_live_reference_library_matches(oracle):
         assert np.array_equal(P2.colop_dense("EOS_BLOCK", 1, 0, f1=rt), own_col)
     finally:
         oracle.use_reference_linalg(False)
-    assert own_col.shape == (P.nk * P.n2e, P.nk * P.n2e)
