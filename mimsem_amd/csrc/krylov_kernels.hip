@@ -257,14 +257,14 @@ __global__ __launch_bounds__(256) void k_rowdot_fused(long long n, long long chu
     __syncthreads();
     if (!last || wave != 0) return;
     double v = 0.0;
-    for (int i = lane; i < nb; i += 64) v += __hip_atomic_load(part + (size_t)row*nb + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (nb <= 64: one term per lane)
+    for (int i = lane; i < nb; i += 64) v += __hip_atomic_load(part + (size_t)row*nb + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (lane l sums partials l, l + 64, ...: any nb up to 1 024)
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     if (lane == 0) { out[row] = v; __hip_atomic_store(counters + row, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 }
 __global__ __launch_bounds__(64) void k_rowdot_final(int nb, const double* __restrict__ part, double* __restrict__ out) {
     const int row = blockIdx.x, lane = threadIdx.x;
     double s = 0.0;
-    for (int i = lane; i < nb; i += 64) s += part[(size_t)row*nb + i];      // (nb <= 64: one term per lane, as before rows longer than 262 144 got more blocks)
+    for (int i = lane; i < nb; i += 64) s += part[(size_t)row*nb + i];      // (lane l sums partials l, l + 64, ...: more than one per lane once rows pass 524 288 entries)
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
     if (lane == 0) out[row] = s;
 }

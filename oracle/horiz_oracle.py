@@ -3,10 +3,12 @@
 
 Every PETSc Mat of the reference becomes a DENSE global numpy matrix filled from the C oracle's element matrices with the
 reference's MatSetValues(ADD_VALUES) pattern; every KSPSolve becomes a dense LU solve ("direct solve to round-off",
-SURVEY 8(c)).  Sized for small spheres.  eul/ flavour: SCALE = 1e8, layer thickness, |det|."""
+SURVEY 8(c)).  Sized for small spheres; sparse=True assembles the same element blocks into scipy.sparse CSR matrices and
+solves with sparse LU (oracle/globalmat.py) for the benchmark spheres.  eul/ flavour: SCALE = 1e8, layer thickness, |det|."""
 import numpy as np
 
 from . import pyoracle
+from .globalmat import GlobalMat, Solver
 
 SCALE = 1.0e+8
 OMEGA = 7.29212e-5            # eul/HorizSolve.cpp:23
@@ -14,10 +16,12 @@ RAD_EARTH = 6371220.0
 
 
 class GlobalDense:
-    """dense global matrices of the Assembly.cpp operator classes on a whole (small) cubed sphere"""
+    """global matrices of the Assembly.cpp operator classes on a whole cubed sphere: dense (small spheres) or, with sparse=True,
+    scipy.sparse CSR"""
 
-    def __init__(self, sphere, topos, geoms, coords, levs):
+    def __init__(self, sphere, topos, geoms, coords, levs, sparse=False):
         self.cs, self.topos, self.geoms = sphere, topos, geoms
+        self.sparse = sparse
         self.nk = levs.shape[0] - 1
         pn = topos[0].elOrd
         self.N0, self.N1, self.N2 = sphere.nDofs0G, sphere.nDofs1G, sphere.nDofs2G
@@ -33,6 +37,8 @@ class GlobalDense:
             self.xq[g.loc0] = coords[g.loc0]
         self.E21 = self._e21(); self.E10 = self._e10()
         self.E12 = -self.E21.T; self.E01 = -self.E10.T
+        if sparse:
+            self.E12, self.E01 = self.E12.tocsr(), self.E01.tocsr()
 
     # local views of global fields
     def l1(self, t, u): return np.ascontiguousarray(u[t.loc1])
@@ -45,50 +51,49 @@ class GlobalDense:
                   WHMAT=(2, 2, 2), PMAT=(0, 0, None), PHMAT=(0, 0, 2), WTQUMAT=(2, 1, 1), WTQDUDZ=(2, 1, 1), UTQWMAT=(1, 2, 1))[op]
         rows, cols, fs = sp
         N = {0: self.N0, 1: self.N1, 2: self.N2}
-        M = np.zeros((N[rows], N[cols]))
+        M = GlobalMat((N[rows], N[cols]), self.sparse)
         for t, P in zip(self.topos, self.P):
             f = None if fs is None else {0: self.l0, 1: self.l1, 2: self.l2}[fs](t, field)
             em = P.op_elmats(op, lev, scale, flag, f)
             gx, gy, g2, g0 = t.all_inds1x_g(), t.all_inds1y_g(), t.all_inds2_g(), t.all_inds0_g()
-            n1e, n2e, n0e = P.n1e, P.n2e, P.n0e
-            for e in range(P.nEl):
-                if op == "ROTMAT":
-                    b = em[e].reshape(2, n1e, n1e)
-                    M[np.ix_(gx[e], gy[e])] += b[0]; M[np.ix_(gy[e], gx[e])] += b[1]
-                elif rows == 1 and cols == 1:
-                    b = em[e].reshape(4, n1e, n1e)
-                    M[np.ix_(gx[e], gx[e])] += b[0]; M[np.ix_(gx[e], gy[e])] += b[1]
-                    M[np.ix_(gy[e], gx[e])] += b[2]; M[np.ix_(gy[e], gy[e])] += b[3]
-                elif rows == 2 and cols == 2:
-                    M[np.ix_(g2[e], g2[e])] += em[e].reshape(n2e, n2e)
-                elif rows == 0:
-                    M[np.ix_(g0[e], g0[e])] += em[e].reshape(n0e, n0e)
-                elif rows == 2 and cols == 1:
-                    b = em[e].reshape(2, n2e, n1e)
-                    M[np.ix_(g2[e], gx[e])] += b[0]; M[np.ix_(g2[e], gy[e])] += b[1]
-                else:                                   # 1 x 2
-                    b = em[e].reshape(2, n1e, n2e)
-                    M[np.ix_(gx[e], g2[e])] += b[0]; M[np.ix_(gy[e], g2[e])] += b[1]
-        return M
+            n1e, n2e, n0e, nEl = P.n1e, P.n2e, P.n0e, P.nEl
+            if op == "ROTMAT":
+                b = em.reshape(nEl, 2, n1e, n1e)
+                M.add(gx, gy, b[:, 0]); M.add(gy, gx, b[:, 1])
+            elif rows == 1 and cols == 1:
+                b = em.reshape(nEl, 4, n1e, n1e)
+                M.add(gx, gx, b[:, 0]); M.add(gx, gy, b[:, 1])
+                M.add(gy, gx, b[:, 2]); M.add(gy, gy, b[:, 3])
+            elif rows == 2 and cols == 2:
+                M.add(g2, g2, em.reshape(nEl, n2e, n2e))
+            elif rows == 0:
+                M.add(g0, g0, em.reshape(nEl, n0e, n0e))
+            elif rows == 2 and cols == 1:
+                b = em.reshape(nEl, 2, n2e, n1e)
+                M.add(g2, gx, b[:, 0]); M.add(g2, gy, b[:, 1])
+            else:                                       # 1 x 2
+                b = em.reshape(nEl, 2, n1e, n2e)
+                M.add(gx, g2, b[:, 0]); M.add(gy, g2, b[:, 1])
+        return M.done()
 
     def _e21(self):
-        E = np.zeros((self.N2, self.N1))
+        E = GlobalMat((self.N2, self.N1), self.sparse)
         for t, P in zip(self.topos, self.P):
             g2 = t.pi * t.n2 + np.arange(t.n2)
             for j in range(P.n1):
                 x = np.zeros(P.n1); x[j] = 1.0
                 col = P.e21(x); nz = np.nonzero(col)[0]
-                E[g2[nz], t.loc1[j]] = col[nz]
-        return E
+                E.insert(g2[nz], t.loc1[j], col[nz])
+        return E.done()
 
     def _e10(self):
-        E = np.zeros((self.N1, self.N0))
+        E = GlobalMat((self.N1, self.N0), self.sparse)
         for t, P in zip(self.topos, self.P):
             for j in range(P.n0):
                 x = np.zeros(P.n0); x[j] = 1.0
                 col = P.e10(x); nz = np.nonzero(col)[0]
-                E[t.loc1[nz], t.loc0[j]] = col[nz]
-        return E
+                E.insert(t.loc1[nz], t.loc0[j], col[nz])
+        return E.done()
 
     def uvec_hu(self, lev, u, rho, fac):
         """Uvec::assemble_hu(lev, SCALE, ul, rho, ., fac) on every patch + the gtol_1 REVERSE/ADD  (eul/Assembly.cpp:2198-2279)"""
@@ -106,10 +111,11 @@ class GlobalDense:
 
 
 class HorizOracle:
-    """eul/HorizSolve.cpp on dense matrices; vectors are global, one row per level"""
+    """eul/HorizSolve.cpp on the global matrices of a GlobalDense (dense or sparse); vectors are global, one row per level"""
 
     def __init__(self, gd, do_visc=True):
         self.g, self.nk, self.do_visc = gd, gd.nk, do_visc
+        self._solve = Solver(gd.sparse)
         ae = 4.0 * np.pi * RAD_EARTH * RAD_EARTH                      # viscosity() :112-120
         dx = np.sqrt(ae / gd.N0)
         self.del2 = -np.sqrt(0.072 * dx ** 3.2)
@@ -122,13 +128,13 @@ class HorizOracle:
         """:124-161  fg[k] = M0(k, scale 1)^-1 PtQ f"""
         lat = np.arcsin(self.g.xq[:, 2] / RAD_EARTH)
         b = self.g.project0(2.0 * OMEGA * np.sin(lat))
-        self.fg = np.stack([np.linalg.solve(self.g.mat("PMAT", k, 0, scale=1.0), b) for k in range(self.nk)])
+        self.fg = np.stack([self._solve(self.g.mat("PMAT", k, 0, scale=1.0), b) for k in range(self.nk)])
 
     def grad(self, phi, lev):
-        return np.linalg.solve(self.M1[lev], self.g.E12 @ (self.M2[lev] @ phi))                   # :208-228
+        return self._solve(self.M1[lev], self.g.E12 @ (self.M2[lev] @ phi), ("M1", lev))                   # :208-228
 
     def curl(self, u, lev, add_f=False):
-        w = np.linalg.solve(self.M0[lev], self.g.E01 @ (self.M1[lev] @ u))                        # :233-254
+        w = self._solve(self.M0[lev], self.g.E01 @ (self.M1[lev] @ u), ("M0", lev))                        # :233-254
         return w + self.fg[lev] if add_f else w
 
     def laplacian(self, u, lev):
@@ -141,8 +147,8 @@ class HorizOracle:
         g = self.g
         hu = g.uvec_hu(lev, u1, h1, 1.0 / 3.0) + g.uvec_hu(lev, u1, h2, 1.0 / 6.0) \
             + g.uvec_hu(lev, u2, h1, 1.0 / 6.0) + g.uvec_hu(lev, u2, h2, 1.0 / 3.0)                   # m1->assemble_hu x4, :300-305
-        F = np.linalg.solve(self.M1[lev], hu)
-        G = np.linalg.solve(self.M1[lev], g.mat("UHMAT", lev, 1, theta[lev]) @ F)
+        F = self._solve(self.M1[lev], hu, ("M1", lev))
+        G = self._solve(self.M1[lev], g.mat("UHMAT", lev, 1, theta[lev]) @ F, ("M1", lev))
         return F, G
 
     def advection_rhs_ec(self, u1, u2, h1, h2, theta):
@@ -181,7 +187,7 @@ class HorizOracle:
         g = self.g
         rhs = g.E01 @ (self.M1[lev] @ u)                 # m1->assemble(level, SCALE, true, ul): Uvec = M1 u
         rhs = rhs + self.M0[lev] @ self.fg[lev]
-        return np.linalg.solve(g.mat("PHMAT", lev, 0, rho), rhs)
+        return self._solve(g.mat("PHMAT", lev, 0, rho), rhs)
 
     def momentum_rhs_ec(self, lev, theta, dudz1, dudz2, velz1, velz2, Pi, velx1, velx2, rho1, rho2, Fx=None, Fz=None,
                         dwdx1=None, dwdx2=None, Fk=None):
@@ -199,7 +205,7 @@ class HorizOracle:
         if Fx is None:
             dp = g.uvec_hu(lev, velx1, rho1, 1.0 / 3.0) + g.uvec_hu(lev, velx2, rho1, 1.0 / 6.0) \
                 + g.uvec_hu(lev, velx1, rho2, 1.0 / 6.0) + g.uvec_hu(lev, velx2, rho2, 1.0 / 3.0)       # :675-682
-            dp = R @ np.linalg.solve(self.M1[lev], dp)
+            dp = R @ self._solve(self.M1[lev], dp, ("M1", lev))
         else:
             dp = R @ Fx
         fu = fu + dp

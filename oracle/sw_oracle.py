@@ -4,11 +4,13 @@ mimsem_amd/.
 
 Every PETSc Mat of the reference becomes a DENSE global numpy matrix, filled from the C oracle's element matrices with the
 reference's MatSetValues(ADD_VALUES) pattern (global indices Topo::elInds*_g); every KSPSolve (GMRES, rtol 1e-16) becomes a
-dense LU solve -- "direct solve to round-off", SURVEY 8(c).  Sized for small spheres (a few hundred DoFs).
+dense LU solve -- "direct solve to round-off", SURVEY 8(c).  Sized for small spheres (a few hundred DoFs).  sparse=True: the same
+element blocks and index pattern into scipy.sparse CSR matrices, sparse LU for the solves (oracle/globalmat.py) -- the benchmark spheres.
 src/ flavour: scale 1, unit thickness (nk = 1, levels 0 and 1), signed Jacobian determinant (src/Geom.cpp:248-252)."""
 import numpy as np
 
 from . import pyoracle
+from .globalmat import GlobalMat, Solver, block2x2
 
 RAD_EARTH = 6371220.0
 RAD_SPHERE = 6371220.0
@@ -18,10 +20,11 @@ UP_TAU = 0.5             # :30
 
 
 class SWOracle:
-    def __init__(self, sphere, topos, geoms, coords):
+    def __init__(self, sphere, topos, geoms, coords, sparse=False):
         """sphere: mimsem_amd.mesh.CubedSphere (sizes only); topos/geoms: one per patch (index tables only); coords: the global
-        quadrature-grid coordinate table (geom_*.txt content)."""
+        quadrature-grid coordinate table (geom_*.txt content); sparse: scipy.sparse matrices and sparse LU instead of dense."""
         self.cs, self.topos, self.geoms = sphere, topos, geoms
+        self.sparse, self._solve = sparse, Solver(sparse)
         pn = sphere.pn if hasattr(sphere, "pn") else topos[0].elOrd
         self.N0, self.N1, self.N2 = sphere.nDofs0G, sphere.nDofs1G, sphere.nDofs2G
         self.P = []
@@ -44,6 +47,8 @@ class SWOracle:
         self.E10 = self._e10()
         self.E12 = -self.E21.T                       # E21mat: E12 = -E21^T (eul/Assembly.cpp:1209-1213 / src twin)
         self.E01 = -self.E10.T
+        if sparse:
+            self.E12, self.E01 = self.E12.tocsr(), self.E01.tocsr()
         self.E01M1 = self.E01 @ self.M1              # :73
         self.E12M2 = self.E12 @ self.M2              # :74
         self.coriolis()
@@ -56,71 +61,66 @@ class SWOracle:
     def _add11(self, M, t, P, em):
         gx, gy = t.all_inds1x_g(), t.all_inds1y_g()
         b = em.reshape(P.nEl, 4, P.n1e, P.n1e)
-        for e in range(P.nEl):
-            M[np.ix_(gx[e], gx[e])] += b[e, 0]; M[np.ix_(gx[e], gy[e])] += b[e, 1]
-            M[np.ix_(gy[e], gx[e])] += b[e, 2]; M[np.ix_(gy[e], gy[e])] += b[e, 3]
+        M.add(gx, gx, b[:, 0]); M.add(gx, gy, b[:, 1])
+        M.add(gy, gx, b[:, 2]); M.add(gy, gy, b[:, 3])
 
     def _assemble1(self, op, field=None, space=None):
-        M = np.zeros((self.N1, self.N1))
+        M = GlobalMat((self.N1, self.N1), self.sparse)
         for t, P in zip(self.topos, self.P):
             f = None if field is None else (self._local2(t, field) if space == 2 else self._local0(t, field))
             em = P.op_elmats(op, 0, 1.0, 0, f)
             if op == "ROTMAT":                       # blocks UtQV (x rows, y cols), VtQU (y rows, x cols)
                 gx, gy = t.all_inds1x_g(), t.all_inds1y_g()
                 b = em.reshape(P.nEl, 2, P.n1e, P.n1e)
-                for e in range(P.nEl):
-                    M[np.ix_(gx[e], gy[e])] += b[e, 0]; M[np.ix_(gy[e], gx[e])] += b[e, 1]
+                M.add(gx, gy, b[:, 0]); M.add(gy, gx, b[:, 1])
             else:
                 self._add11(M, t, P, em)
-        return M
+        return M.done()
 
     def _assemble2(self, op):
-        M = np.zeros((self.N2, self.N2))
+        M = GlobalMat((self.N2, self.N2), self.sparse)
         for t, P in zip(self.topos, self.P):
             g2 = t.all_inds2_g(); em = P.op_elmats(op, 0, 1.0, 0).reshape(P.nEl, P.n2e, P.n2e)
-            for e in range(P.nEl):
-                M[np.ix_(g2[e], g2[e])] += em[e]
-        return M
+            M.add(g2, g2, em)
+        return M.done()
 
     def _assemble0(self, op, h=None):
-        M = np.zeros((self.N0, self.N0))
+        M = GlobalMat((self.N0, self.N0), self.sparse)
         for t, P in zip(self.topos, self.P):
             g0 = t.all_inds0_g()
             em = P.op_elmats(op, 0, 1.0, 0, None if h is None else self._local2(t, h)).reshape(P.nEl, P.n0e, P.n0e)
-            for e in range(P.nEl):
-                M[np.ix_(g0[e], g0[e])] += em[e]
-        return M
+            M.add(g0, g0, em)
+        return M.done()
 
     def _e21(self):
-        E = np.zeros((self.N2, self.N1))
+        E = GlobalMat((self.N2, self.N1), self.sparse)
         for t, P in zip(self.topos, self.P):
             g2 = t.pi * t.n2 + np.arange(t.n2)
             for j in range(P.n1):
                 x = np.zeros(P.n1); x[j] = 1.0
                 col = P.e21(x)
                 nz = np.nonzero(col)[0]
-                E[g2[nz], t.loc1[j]] = col[nz]       # every face row is owned by exactly one patch: plain insert
-        return E
+                E.insert(g2[nz], t.loc1[j], col[nz])     # every face row is owned by exactly one patch: plain insert
+        return E.done()
 
     def _e10(self):
-        E = np.zeros((self.N1, self.N0))
+        E = GlobalMat((self.N1, self.N0), self.sparse)
         for t, P in zip(self.topos, self.P):
             for j in range(P.n0):
                 x = np.zeros(P.n0); x[j] = 1.0
                 col = P.e10(x)
                 nz = np.nonzero(col)[0]
-                E[t.loc1[nz], t.loc0[j]] = col[nz]   # rows of the patch's own edges only (Assembly.cpp:1102-1162)
-        return E
+                E.insert(t.loc1[nz], t.loc0[j], col[nz])  # rows of the patch's own edges only (Assembly.cpp:1102-1162)
+        return E.done()
 
     def K(self, ug):
         """WtQUmat::assemble(ul)  src/Assembly.cpp:1172-1299"""
-        M = np.zeros((self.N2, self.N1))
+        M = GlobalMat((self.N2, self.N1), self.sparse)
         for t, P in zip(self.topos, self.P):
             gx, gy, g2 = t.all_inds1x_g(), t.all_inds1y_g(), t.all_inds2_g()
             em = P.op_elmats("WTQUMAT", 0, 1.0, 0, self._local1(t, ug)).reshape(P.nEl, 2, P.n2e, P.n1e)
-            for e in range(P.nEl):
-                M[np.ix_(g2[e], gx[e])] += em[e, 0]; M[np.ix_(g2[e], gy[e])] += em[e, 1]
-        return M
+            M.add(g2, gx, em[:, 0]); M.add(g2, gy, em[:, 1])
+        return M.done()
 
     def M1h(self, hg): return self._assemble1("UHMAT", hg, 2)        # Uhmat::assemble(h)  src/Assembly.cpp:675-750
     def R(self, qg): return self._assemble1("ROTMAT", qg, 0)         # RotMat::assemble(q) src/Assembly.cpp:1346-1396
@@ -128,24 +128,22 @@ class SWOracle:
 
     def R_up(self, qg, ug, dt):
         """RotMat_up::assemble(q0, ul, fac, dt)  src/Assembly.cpp:1784-1853"""
-        M = np.zeros((self.N1, self.N1))
+        M = GlobalMat((self.N1, self.N1), self.sparse)
         for t, P in zip(self.topos, self.P):
             _, em = P.apply_up(1, np.zeros(P.n1), UP_TAU, dt, self._local0(t, qg), self._local1(t, ug))
             gx, gy = t.all_inds1x_g(), t.all_inds1y_g()
             b = em.reshape(P.nEl, 2, P.n1e, P.n1e)
-            for e in range(P.nEl):
-                M[np.ix_(gx[e], gy[e])] += b[e, 0]; M[np.ix_(gy[e], gx[e])] += b[e, 1]
-        return M
+            M.add(gx, gy, b[:, 0]); M.add(gy, gx, b[:, 1])
+        return M.done()
 
     def M0h_up(self, ug, hg, dt):
         """Phmat::assemble_up(ul, hl, fac, dt)  src/Assembly.cpp:499-567"""
-        M = np.zeros((self.N0, self.N0))
+        M = GlobalMat((self.N0, self.N0), self.sparse)
         for t, P in zip(self.topos, self.P):
             _, em = P.apply_up(0, np.zeros(P.n0), UP_TAU, dt, self._local2(t, hg), self._local1(t, ug))
             g0 = t.all_inds0_g(); b = em.reshape(P.nEl, P.n0e, P.n0e)
-            for e in range(P.nEl):
-                M[np.ix_(g0[e], g0[e])] += b[e]
-        return M
+            M.add(g0, g0, b)
+        return M.done()
 
     def project(self, which, fq):
         """WtQmat / PtQmat / UtQmat applied to a global quad-grid field (which 0/1/2)"""
@@ -162,10 +160,10 @@ class SWOracle:
         """:186-233"""
         lat = np.arcsin(self.xq[:, 2] / RAD_SPHERE)
         fq = 2.0 * self.omega * np.sin(lat)
-        self.fg = np.linalg.solve(self.M0, self.project(1, fq))
+        self.fg = self._solve(self.M0, self.project(1, fq), "M0")
 
     def curl(self, u):
-        return np.linalg.solve(self.M0, self.E01M1 @ u)                  # :236-250
+        return self._solve(self.M0, self.E01M1 @ u, "M0")                  # :236-250
 
     def diagnose_F(self, ui, uj, hi, hj):
         """:253-284"""
@@ -174,7 +172,7 @@ class SWOracle:
         hu += (1.0 / 3.0) * (M @ ui); hu += (1.0 / 6.0) * (M @ uj)
         M = self.M1h(hj)
         hu += (1.0 / 6.0) * (M @ ui); hu += (1.0 / 3.0) * (M @ uj)
-        return np.linalg.solve(self.M1, hu)
+        return self._solve(self.M1, hu, "M1")
 
     def diagnose_Phi(self, ui, uj, hi, hj):
         """:289-320"""
@@ -190,7 +188,7 @@ class SWOracle:
         """:322-341"""
         rhs = self.M0 @ self.fg + self.E01M1 @ u
         M = self.M0h_up(u, h, dt) if dt > 1.0e-6 else self.M0h(h)
-        return np.linalg.solve(M, rhs)
+        return self._solve(M, rhs)
 
     def assemble_residual(self, ui, hi, uj, hj, dt, q_exact=False, bot=None):
         """:402-607; returns (f_u, f_h)"""
@@ -212,12 +210,8 @@ class SWOracle:
     def assemble_operator(self, dt):
         """:609-725"""
         a = ROS_ALPHA * dt
-        A = np.zeros((self.N1 + self.N2, self.N1 + self.N2))
-        A[:self.N1, :self.N1] = self.M1 + a * self.R(self.fg)
-        A[:self.N1, self.N1:] = (a * self.grav) * (self.E12 @ self.M2)
-        A[self.N1:, :self.N1] = (a * H_MEAN) * (self.M2 @ self.E21)
-        A[self.N1:, self.N1:] = self.M2
-        return A
+        return block2x2(self.M1 + a * self.R(self.fg), (a * self.grav) * (self.E12 @ self.M2),
+                        (a * H_MEAN) * (self.M2 @ self.E21), self.M2, self.sparse)
 
     def solve(self, un, hn, dt, nits=99, q_exact=False, bot=None):
         """:727-791"""
@@ -228,7 +222,7 @@ class SWOracle:
         it, hist = 0, []
         while True:
             fu, fh = self.assemble_residual(ui, hi, uj, hj, dt, q_exact, bot)
-            dx = np.linalg.solve(A, -np.concatenate([fu, fh]))
+            dx = self._solve(A, -np.concatenate([fu, fh]), ("A", dt))
             x = x + dx
             uj, hj = x[:self.N1].copy(), x[self.N1:].copy()
             norm = np.linalg.norm(dx) / np.linalg.norm(x)
@@ -289,7 +283,7 @@ class SWOracle:
         return [l1[0] / l1[1], np.sqrt(l2[0] / l2[1]), li[0] / li[1]]
 
     def init1(self, uq):
-        return np.linalg.solve(self.M1, self.project(2, uq))             # :880-932
+        return self._solve(self.M1, self.project(2, uq), "M1")             # :880-932
 
     def init2(self, hq):
-        return np.linalg.solve(self.M2, self.project(0, hq))             # :934-975
+        return self._solve(self.M2, self.project(0, hq), "M2")             # :934-975

@@ -3,10 +3,12 @@
 // its three modes -- KSP objects (as the reference: src/SWEqn_Picard.cpp:727-791), fixed-length Chebyshev solves issued eagerly, and the same
 // recorded as one hipGraph per Picard iteration.  The states after `nsteps` steps go back to the wrapper, which compares them with the numpy
 // oracle's (oracle/sw_oracle.py); the three modes are compared with each other here.
-//   usage: test_sw <in.bin> <out.bin>
+// With "no-half-step" the states go back after the `nsteps` steps at dt alone (the benchmark-size fixtures of tests/golden/ hold one step).
+//   usage: test_sw <in.bin> <out.bin> [no-half-step]
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "../../mimsem_amd/host/mimsem_sweqn.hpp"
 #include "../../mimsem_amd/host/sw_io.hpp"
@@ -20,7 +22,8 @@ static double rel_l2(const std::vector<double>& a, const std::vector<double>& b)
 }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { std::fprintf(stderr, "usage: test_sw in.bin out.bin\n"); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: test_sw in.bin out.bin [no-half-step]\n"); return 2; }
+    const bool half_step = !(argc > 3 && std::strcmp(argv[3], "no-half-step") == 0);
     int fails = 0;
     std::vector<double> out[4][2];
     int n1 = 0, n2 = 0;
@@ -40,12 +43,12 @@ int main(int argc, char** argv) {
             for (int s = 0; s < nsteps; s++) {
                 sw.solve(un, hn, dt, false, nits, q_exact, bot);
                 std::printf("mode %d step %d:", mode, s);
-                for (double v : sw.history) std::printf(" %.6e", v);
+                for (double v : sw.history) std::printf(" %.15e", v);
                 std::printf("\n");
             }
             // ... and one step with HALF the time step: the [u|h] operator, its blocks, the spectral regions and the recorded graphs belong to a dt
             // (SWEqn::solve re-assembles A when dt changes, src/SWEqn_Picard.cpp:732-734) -- the set-up must notice
-            sw.solve(un, hn, 0.5*dt, false, nits, q_exact, bot);
+            if (half_step) sw.solve(un, hn, 0.5*dt, false, nits, q_exact, bot);
             out[mode][0].resize(n1); out[mode][1].resize(n2);
             mesh.to_host(out[mode][0].data(), un, n1); mesh.to_host(out[mode][1].data(), hn, n2);
             std::printf("mode %d: Chebyshev steps [u|h] %d, M1 %d, q %d; iterations handed to the KSP objects: %d\n", mode, sw.steps_A, sw.steps_M1, sw.steps_q, sw.fallbacks);

@@ -82,3 +82,54 @@ def solve_error_budget(L_hip, rhs_hip, d_hip, L_orc, rhs_orc, d_orc):
     return {"rel_L": rel_l2(L_hip, L_orc), "rel_rhs": rel_l2(rhs_hip, rhs_orc), "cond": float(np.linalg.cond(L_orc)),
             "hip_vs_own_system": _rel_ld(d_hip, x_h), "oracle_vs_own_system": _rel_ld(d_orc, x_o),
             "diff_of_exact_solutions": _rel_ld(x_h, x_o), "diff": rel_l2(d_hip, d_orc)}
+
+
+# ---- hashed inputs and sketched outputs for the benchmark-size fixtures (tests/golden/make_step_fixtures.py) ---------------------
+# An integer hash, not numpy's rng: the GPU-side test rebuilds the inputs and the probe matrix bit for bit from (seed, index) alone,
+# so neither has to be stored; only K numbers per output are.
+SKETCH_K = 64
+
+
+def _splitmix64(x):
+    x = np.asarray(x, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = x + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def hash_uniform(seed, shape, lo=0.0, hi=1.0):
+    """uniform numbers in [lo, hi): splitmix64 of (seed << 40) + i for the flat index i, top 53 bits"""
+    n = int(np.prod(shape))
+    z = _splitmix64((np.uint64(seed) << np.uint64(40)) + np.arange(n, dtype=np.uint64))
+    u = (z >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+    return (lo + (hi - lo) * u).reshape(shape)
+
+
+_PROBES = {}
+
+
+def probe_matrix(n, K=SKETCH_K):
+    """the K x n sketching matrix S: S[j, i] = +-1/sqrt(K) from the low bit of splitmix64(j*n + i) (kept as int8 signs; 1/sqrt(K) applied
+    by sketch())"""
+    if (K, n) not in _PROBES:
+        S = np.empty((K, n), dtype=np.int8)
+        i = np.arange(n, dtype=np.uint64)
+        for j in range(K):
+            S[j] = 1 - 2 * (_splitmix64(np.uint64(j) * np.uint64(n) + i) & np.uint64(1)).astype(np.int8)
+        _PROBES[(K, n)] = S
+    return _PROBES[(K, n)]
+
+
+def sketch(y, K=SKETCH_K):
+    """S y for the flattened y: a random projection that keeps |S e| close to |e| for any error e fixed before S is drawn
+    (a single-entry error exactly: every column of S has norm 1)"""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    S = probe_matrix(y.size, K)
+    return np.array([np.dot(S[j].astype(np.float64), y) for j in range(K)]) / np.sqrt(K)
+
+
+def sketch_rel_err(y, s_ref, norm_ref):
+    """|S y - S y_ref| / |y_ref| from the stored sketch S y_ref and norm |y_ref|"""
+    return float(np.linalg.norm(sketch(y, len(s_ref)) - s_ref) / norm_ref)

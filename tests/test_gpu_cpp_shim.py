@@ -6,6 +6,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MOMENTUM_TOL = 1e-10    # HorizSolve::momentum_rhs_ec per level, relative L2 (and the kinetic-to-internal exchange term)
 
 
 def _build(tmp, name="test_shim", extra=()):
@@ -54,7 +55,7 @@ def test_ksp_call_sites_match_dense_solves(tmp_path, oracle):
 def test_sw_step_driven_from_cpp(tmp_path, oracle, q_exact, nits, dt, topo, pn):
     """SWEqn::solve (src/SWEqn_Picard.cpp:727-791) orchestrated in C++ (mimsem_amd/host/mimsem_sweqn.hpp: KSP objects, fixed-length
     Chebyshev solves, the same as one hipGraph per Picard iteration) on the cubed sphere of tests/test_gpu_sweqn.py, against the numpy
-    oracle's step (oracle/sw_oracle.py: dense matrices, LU for every KSPSolve).  Tolerance 1e-9 as for the Python host."""
+    oracle's step (oracle/sw_oracle.py: dense matrices, LU for every KSPSolve).  Tolerance 1e-10 as for the Python host."""
     import numpy as np
     from mimsem_amd.device import DeviceMesh
     from mimsem_amd.geom import Geom
@@ -88,8 +89,10 @@ def test_sw_step_driven_from_cpp(tmp_path, oracle, q_exact, nits, dt, topo, pn):
         ur, hr = O.solve(ur, hr, dt, nits=nits, q_exact=q_exact, bot=bot)
     ur, hr = O.solve(ur, hr, 0.5 * dt, nits=nits, q_exact=q_exact, bot=bot)       # (the C++ test ends with a step at half the time step)
     res = np.fromfile(fout, dtype=np.float64).reshape(4, dm.n1 + dm.n2)
-    for mode in range(4):
-        assert rel_l2(res[mode, :dm.n1], ur) < 1e-9 and rel_l2(res[mode, dm.n1:], hr) < 1e-9, mode
+    errs = [(rel_l2(res[mode, :dm.n1], ur), rel_l2(res[mode, dm.n1:], hr)) for mode in range(4)]
+    print("C++ SW steps vs sw_oracle, modes 0-3 (u, h): " + "  ".join("%.2e %.2e" % e for e in errs))
+    for mode, (eu, eh) in enumerate(errs):
+        assert eu < 1e-10 and eh < 1e-10, mode
 
 
 @pytest.mark.gpu
@@ -154,15 +157,19 @@ def test_horizsolve_driven_from_cpp(tmp_path, oracle, m1, pn):
         assert rel(gPhi[lev], H.diagnose_Phi(lev, u1[lev], u2[lev], velz, velz2)) < 1e-10
         assert rel(gq[lev], H.diagnose_q(lev, h1[lev], u1[lev])) < 1e-10
     for got, k2i_got, use_F, use_w in ((fuA, k2iA, False, False), (fuB, k2iB, True, False), (fuC, None, True, True)):
-        k2i = 0.0
+        k2i, errs = 0.0, []
         for lev in range(nk):
             want, k = H.momentum_rhs_ec(lev, th[lev], dudz, dudz2, velz, velz2, Pi[lev], u1[lev], u2[lev], h1[lev], h2[lev],
                                         Fx=Fk[lev] if use_F else None, Fz=Fz if use_F else None, Fk=Fk[lev],
                                         dwdx1=dwdx if use_w else None, dwdx2=dwdx2 if use_w else None)
             k2i += k
-            assert rel(got[lev], want) < 1e-8, (lev, use_F, use_w)
-        if k2i_got is not None:
-            assert abs(k2i_got - k2i) < 1e-8 * abs(k2i)
+            errs.append(rel(got[lev], want))
+        ek2i = abs(k2i_got - k2i) / abs(k2i) if k2i_got is not None else 0.0
+        print("momentum_rhs_ec (Fx %s, dwdx %s) vs oracle per level: %s  k2i %s" % (use_F, use_w, " ".join("%.2e" % e for e in errs),
+                                                                                  "%.2e" % ek2i if k2i_got is not None else "-"))
+        for lev, e in enumerate(errs):
+            assert e < MOMENTUM_TOL, (lev, use_F, use_w)
+        assert ek2i < MOMENTUM_TOL
     assert rel(fuC, fuB) > 1e-6                      # the dwdx term is not lost in the noise of the comparison
 
 

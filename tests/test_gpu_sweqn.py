@@ -1,6 +1,6 @@
 """N3: the shallow-water Picard step on the device (mimsem_amd/sweqn.py, mirror of src/SWEqn_Picard.cpp) against the numpy
 restatement oracle/sw_oracle.py (dense global matrices from the C oracle's element blocks, LU for every KSPSolve) on a
-small cubed sphere.  Tolerance: fields within 1e-10 relative L2 per operator; 1e-9 after the nested Krylov solves."""
+small cubed sphere.  Tolerance: fields within 1e-10 relative L2, per operator and after the nested Krylov solves."""
 import numpy as np
 import pytest
 
@@ -60,7 +60,9 @@ def test_sw_diagnostics(sw):
     for qe in (False, True):
         fu, fh = O.assemble_residual(u0, h0, u1, h1, dt, q_exact=qe)
         f = S.assemble_residual(tu0, th0, tu1, th1, dt, q_exact=qe)[0].cpu().numpy()
-        assert rel_l2(f[:O.N1], fu) < 1e-9 and rel_l2(f[O.N1:], fh) < 1e-9
+        eu, eh = rel_l2(f[:O.N1], fu), rel_l2(f[O.N1:], fh)
+        print("residual vs sw_oracle (q_exact=%s): f_u %.2e  f_h %.2e" % (qe, eu, eh))
+        assert eu < N3_TOL and eh < N3_TOL
     A = O.assemble_operator(dt)
     x = r.standard_normal(O.N1 + O.N2)
     assert rel_l2(S.apply_A(_t(eng, x), dt)[0].cpu().numpy(), A @ x) < 1e-10
