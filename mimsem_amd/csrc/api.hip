@@ -464,6 +464,124 @@ int build_wave_plan(int order, int n1, int nEl, int n1e, int n0e, int G, const i
     return MIMSEM_OK;
 }
 
+// Owner-computes form (k_apply_wave<3, UMAT, LCT, ACCUM, false, true>, p = 3): every aligned store pair {2k, 2k+1} gets exactly ONE
+// owner group, and the owner computes the contribution of a neighbour element to the pair's slots itself, so that it writes the FINISHED
+// value straight into y -- no partial sums, no perimeter pass.  At p = 3 the quadrature points are the GLL nodes: an edge slot on a side
+// of an element depends on the 4 points of that side only (its 3 side DoFs, the 12 cross-edge DoFs of the point rows, metric and thickInv
+// at the 4 points).  A "ghost side" = (neighbour element, which of its 4 sides) is a virtual element row of the owner's wavefront: 16
+// lanes laid out as the neighbour's, which run the element algebra on the side's 15 DoFs (gathered, one per lane) and zeros elsewhere.
+//   gh [g][64] lane of ghost row r = lane/16 {metric record of the neighbour's point (wave-group order), element*16 + point, staged
+//              position of the lane's X | of its Y << 8 | y-normal side << 16 (WGX: the strip's zero)}
+//   gx [g][64] slot gathered by lane t into position t of the strip
+// The side's slots come out of lanes (qx0, j) / (i, qy0) of the row with the bits of the neighbour's own lanes; the owner's store pair
+// adds them to its own contribution (position WGR + lane of the strip).
+constexpr int WGX = MIMSEM_WGX;     // gathered DoFs of a group (one 8-byte gather per lane and level); position WGX holds 0
+constexpr int WGS = 4;              // ghost sides of a group: rows of the wavefront
+struct WaveOwn {
+    std::vector<int4> plan, gh; std::vector<int> gx;
+    int ndirect = 0, nsides = 0, maxsides = 0, maxgx = 0;
+};
+int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, const int* iy, const WavePlan& P, WaveOwn& W) {
+    if (order != 3 || G != 4 || n1e != 12 || (n1 & 1) || P.ntiles || P.nbgroups) return MIMSEM_ERR_UNSUPPORTED;
+    const int nd = 2*n1e, lpe = 16;
+    const unsigned ZERO = (unsigned)(G*nd + 128), WGR = (unsigned)(G*nd + 136);      // as k_apply_wave: the strip's zero, ghost results
+    auto slot_of = [&](int e, int j) { return j < n1e ? ix[(size_t)e*n1e + j] : iy[(size_t)e*n1e + j - n1e]; };
+    std::vector<int> own((size_t)n1*2, -1), ownj((size_t)n1*2, -1), cnt(n1, 0), grp(nEl, -1), kin(nEl, -1);
+    for (int e = 0; e < nEl; e++) for (int j = 0; j < nd; j++) {
+        const int s = slot_of(e, j);
+        if (s < 0 || s >= n1 || cnt[s] >= 2) return MIMSEM_ERR_UNSUPPORTED;
+        own[(size_t)s*2 + cnt[s]] = e; ownj[(size_t)s*2 + cnt[s]] = j; cnt[s]++;
+    }
+    for (int s = 0; s < n1; s++) if (!cnt[s]) return MIMSEM_ERR_UNSUPPORTED;      // a slot nobody touches: only the perimeter pass zeroes it
+    for (int g = 0; g < P.ngroups; g++) for (int k = 0; k < G; k++) { const int e = P.perm[(size_t)g*G + k]; if (e >= 0) { grp[e] = g; kin[e] = k; } }
+    // side of local DoF j (-1: interior).  Sides: 0 / 1 the x-normal ones at qx = 0 / 3 (x-edge DoFs j = row*4 + col), 2 / 3 the
+    // y-normal ones at qy = 0 / 3 (y-edge DoFs j - 12 = row*3 + col)
+    auto side_of = [&](int j) {
+        if (j < n1e) { const int col = j%4; return col == 0 ? 0 : (col == 3 ? 1 : -1); }
+        const int row = (j - n1e)/3; return row == 0 ? 2 : (row == 3 ? 3 : -1);
+    };
+    // ---- ownership: the candidate owners of a pair are the groups of its contributors; the one needing the fewest new ghost sides
+    // wins (then the one with fewer sides so far, then the lower group) ----
+    std::vector<std::vector<int>> gsides(P.ngroups);            // ghost side keys e*4 + side
+    std::vector<int> owner(n1/2, -1);
+    auto need = [&](int p, int g, int* keys) {                  // new ghost sides pair p needs in group g (-1: impossible)
+        int nk = 0;
+        for (int t = 0; t < 4; t++) {
+            const int s = 2*p + t/2, e = own[(size_t)s*2 + t%2]; if (e < 0 || grp[e] == g) continue;
+            const int sd = side_of(ownj[(size_t)s*2 + t%2]);
+            if (sd < 0) return -1;
+            const int key = e*4 + sd;
+            if (std::find(gsides[g].begin(), gsides[g].end(), key) == gsides[g].end() && std::find(keys, keys + nk, key) == keys + nk) keys[nk++] = key;
+        }
+        return nk;
+    };
+    for (int p = 0; p < n1/2; p++) {
+        int best = -1, bnew = 0, bsz = 0, keys[4];
+        for (int c = 0; c < 4; c++) {
+            const int e = own[(size_t)(2*p + c/2)*2 + c%2]; if (e < 0) continue;
+            const int g = grp[e], nnew = need(p, g, keys), sz = (int)gsides[g].size();
+            if (nnew < 0 || sz + nnew > WGS) continue;
+            if (best < 0 || nnew < bnew || (nnew == bnew && (sz < bsz || (sz == bsz && g < best)))) { best = g; bnew = nnew; bsz = sz; }
+        }
+        if (best < 0) return MIMSEM_ERR_UNSUPPORTED;           // (a numbering this form does not fit: the caller keeps the two launches)
+        owner[p] = best;
+        const int nnew = need(p, best, keys);
+        gsides[best].insert(gsides[best].end(), keys, keys + nnew);
+    }
+    // ---- per group: ghost rows, gathered DoFs, store entries ----
+    W.plan.assign((size_t)P.ngroups*64, int4{0, 0, 0, 0});
+    W.gh.assign((size_t)P.ngroups*64, int4{0, 0, 0, 0});
+    W.gx.assign((size_t)P.ngroups*64, 0);
+    std::vector<std::vector<int>> owned(P.ngroups);
+    for (int p = 0; p < n1/2; p++) owned[owner[p]].push_back(p);
+    for (int g = 0; g < P.ngroups; g++) {
+        std::vector<int>& sides = gsides[g];
+        std::sort(sides.begin(), sides.end());
+        std::vector<int> gslots;                                   // gathered DoFs (distinct slots)
+        auto gpos = [&](int s) -> unsigned {
+            for (size_t t = 0; t < gslots.size(); t++) if (gslots[t] == s) return (unsigned)t;
+            gslots.push_back(s); return (unsigned)(gslots.size() - 1);
+        };
+        const int e0 = std::max(P.perm[(size_t)g*G], 0);
+        for (int l = 0; l < 64; l++)                               // idle rows: the group's first element, operands = the zero
+            W.gh[(size_t)g*64 + l] = int4{g*64 + l%lpe, e0*lpe + l%lpe, (int)(WGX | WGX << 8), 0};
+        for (size_t si = 0; si < sides.size(); si++) {
+            const int e = sides[si]/4, sd = sides[si]%4;
+            const bool yn = sd >= 2; const int c0 = (sd & 1) ? 3 : 0;          // qx0 (x-normal) or qy0 (y-normal)
+            for (int q = 0; q < lpe; q++) {
+                const int qx = q%4, qy = q/4;
+                // X of the lane = x-edge DoF q (q < 12), Y = y-edge DoF qy*3 + qx (qx < 3): staged where a side point of the row reads them
+                const bool wx = q < n1e && (yn || qx == c0), wy = qx < 3 && (!yn || qy == c0);
+                const unsigned px = wx ? gpos(slot_of(e, q)) : (unsigned)WGX, py = wy ? gpos(slot_of(e, n1e + qy*3 + qx)) : (unsigned)WGX;
+                W.gh[(size_t)g*64 + si*lpe + q] = int4{grp[e]*64 + kin[e]*lpe + q, e*lpe + q, (int)(px | py << 8 | (unsigned)yn << 16), 0};
+            }
+        }
+        if ((int)gslots.size() > WGX) return MIMSEM_ERR_UNSUPPORTED;
+        const int lane0slot = P.lane[(size_t)g*64].y;
+        for (int l = 0; l < 64; l++) W.gx[(size_t)g*64 + l] = l < (int)gslots.size() ? gslots[l] : lane0slot;     // idle lanes re-read a pair of the group
+        // store entries of the owned pairs; a contribution from outside the group comes from a lane of its ghost row
+        std::vector<int4> ent;
+        auto contrib = [&](int s, int w) -> unsigned {
+            const int e = own[(size_t)s*2 + w]; if (e < 0) return ZERO;
+            const int j = ownj[(size_t)s*2 + w];
+            if (grp[e] == g) return (unsigned)(kin[e]*nd + j);
+            const int si = (int)(std::find(sides.begin(), sides.end(), e*4 + side_of(j)) - sides.begin());
+            const int q = j < n1e ? j : ((j - n1e)/3)*4 + (j - n1e)%3;      // the lane of the row holding the DoF's result
+            return WGR + (unsigned)(si*lpe + q);
+        };
+        for (int p : owned[g]) {
+            ent.push_back(int4{2*p, (int)(contrib(2*p, 0) | contrib(2*p, 1) << 16), (int)(contrib(2*p + 1, 0) | contrib(2*p + 1, 1) << 16), 0});
+            W.ndirect += 2;
+        }
+        // unused lanes repeat one of the group's own entries (same address, same value); a group owning no pair is not expected
+        if (ent.empty() || ent.size() > 64) return MIMSEM_ERR_UNSUPPORTED;
+        for (int t = 0; t < 64; t++) W.plan[(size_t)g*64 + t] = ent[t%ent.size()];
+        W.nsides += (int)sides.size(); W.maxsides = std::max(W.maxsides, (int)sides.size());
+        W.maxgx = std::max(W.maxgx, (int)gslots.size());
+    }
+    return MIMSEM_OK;
+}
+
 // levels per work item of the element kernel: keep >= ~6 workgroups per CU in flight, otherwise amortise as much as possible
 int level_chunk(const mimsem_ctx* c, int nlev) {
     const ElemSizes& es = c->es;
@@ -614,7 +732,14 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
         rc = build_wave_plan(es.n, c->n1, c->nEl, es.n1e, es.n0e, 64/lpe, c->h_i1x.data(), c->h_i1y.data(), c->h_i0.data(), singles, mixed, marked, P, false);
     }
     if (rc) return rc;
-    void* old[] = {c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin};
+    // owner-computes form on the same groups (Umat at p = 3, no halo split; MIMSEM_WAVE_OWN=0: today's two launches)
+    WaveOwn W;
+    const bool want_own = !marked && es.n == 3 && !want_fin && !want_tile && !singles && mixed &&
+                          !(getenv("MIMSEM_WAVE_OWN") && atoi(getenv("MIMSEM_WAVE_OWN")) == 0);
+    const bool own = want_own && build_wave_own(es.n, c->n1, c->nEl, es.n1e, 64/lpe, c->h_i1x.data(), c->h_i1y.data(), P, W) == MIMSEM_OK;
+    void* old[] = {c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin,
+                   c->d_woplan, c->d_wgh, c->d_wgx};
+    c->d_woplan = nullptr; c->d_wgh = nullptr; c->d_wgx = nullptr; c->w_own = false;
     c->d_wtfin = nullptr; c->w_ntiles = 0;
     for (void* p : old) if (p) c->retired.push_back(p);
     c->d_wlane = nullptr; c->d_wplan = nullptr; c->d_wprec = nullptr; c->d_wnode = nullptr; c->d_wsing = nullptr; c->d_wG = nullptr; c->d_wR = nullptr;
@@ -628,6 +753,12 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
         if ((rc = upload(&c->d_wprec, rec.data(), rec.size(), c))) return rc;
     }
     if ((rc = upload(&c->d_wnode, P.node.data(), P.node.size(), c))) return rc;
+    if (own) {
+        if ((rc = upload(&c->d_woplan, W.plan.data(), W.plan.size(), c))) return rc;
+        if ((rc = upload(&c->d_wgh, W.gh.data(), W.gh.size(), c))) return rc;
+        if ((rc = upload(&c->d_wgx, W.gx.data(), W.gx.size(), c))) return rc;
+        c->w_own = true;
+    }
     if (P.nsing && (rc = upload(&c->d_wsing, P.sing.data(), P.sing.size(), c))) return rc;
     if ((rc = upload(&c->d_wfin, P.fin.data(), P.fin.size(), c))) return rc;
     if ((rc = upload(&c->d_wsslot, P.sslot.data(), P.sslot.size(), c))) return rc;
@@ -671,6 +802,9 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
         fprintf(stderr, "[mimsem] wave plan: %d groups of %d elements (%d on the halo boundary), %d perimeter slots (%d partials in %d sides) of %d; "
                         "in-kernel finishing %s; tiles %d (%d inner slots finished in LDS, widest LDS row %d doubles)\n", P.ngroups, 64/lpe, P.nbgroups, P.nps,
                 P.npwritten, P.nsides, c->n1, c->w_fin ? "on" : "off", P.ntiles, P.ninner, P.tpmax);
+    if (getenv("MIMSEM_VERBOSE") && own)
+        fprintf(stderr, "[mimsem] owner-computes form: %d pairs, %d ghost sides (at most %d per group), at most %d gathered DoFs per group\n",
+                c->n1/2, W.nsides, W.maxsides, W.maxgx);
     return MIMSEM_OK;
 }
 
@@ -898,7 +1032,7 @@ void mimsem_ctx_destroy(mimsem_ctx* c) {
     (void)hipSetDevice(c->device);
     orphan_graphs(c);
     void* ptrs[] = {c->d_xn, c->d_E, c->d_w, c->d_U, c->d_V, c->d_W, c->d_P, c->d_J, c->d_det, c->d_th, c->d_tI, c->d_tIp, c->d_tIn,
-                    c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_iq, c->d_fperm, c->d_flid, c->d_fslot, c->d_fcnt, c->d_pslot, c->d_ppart, c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin, c->d_wpart, c->d_wsplit, c->d_colstat, c->d_forceflag, c->d_rdcnt, c->d_cheb, c->d_colratio, c->d_g1, c->d_bplan, c->d_g0, c->d_ye, c->d_col, c->d_lu, c->d_kry,
+                    c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_iq, c->d_fperm, c->d_flid, c->d_fslot, c->d_fcnt, c->d_pslot, c->d_ppart, c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin, c->d_woplan, c->d_wgh, c->d_wgx, c->d_wpart, c->d_wsplit, c->d_colstat, c->d_forceflag, c->d_rdcnt, c->d_cheb, c->d_colratio, c->d_g1, c->d_bplan, c->d_g0, c->d_ye, c->d_col, c->d_lu, c->d_kry,
                     c->d_d0, c->d_d1x, c->d_d1y, c->d_sh0, c->d_sh1};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (void* p : c->retired) (void)hipFree(p);
@@ -991,6 +1125,7 @@ int mimsem_op_wave_stats(const mimsem_ctx* c, int nlev, int out[5]) {
     for (int i = 0; i < 5; i++) out[i] = 0;
     if (!c->wave1) return 0;
     out[0] = c->w_ngroups; out[1] = c->w_ndirect; out[2] = c->w_npwritten; out[3] = c->w_nps;
+    if (c->w_own) { out[1] = c->n1; out[2] = 0; out[3] = 0; }     // the headline operator's form: every slot written once, no partial sums
     { const int lch = wave_level_chunk(c, nlev); out[4] = lch*wave_chunks_per_item(c, nlev, lch, c->w_ngroups); }
     return 1;
 }
@@ -1182,7 +1317,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
 
     const ElemSizes& es = c->es;
     ElemArgs a;
-    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0;
+    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0; a.wgh = nullptr; a.wgx = nullptr;
     a.nEl = c->nEl; a.nlev = nlev; a.lev0 = geom_lev0; a.total = c->nEl*nlev;
     a.flags = flags; a.scale = scale; a.alpha = alpha;
     a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*c->es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;
@@ -1255,11 +1390,14 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
                            (long long)c->nEl*es.mp12 < (1LL << 28);
     if (c->wave1 && wave_fits && wave_op) {
         // wave-level fused path: complete slots straight into y, one partial per perimeter slot into the workspace, perimeter pass
-        const long long prow = (long long)c->w_npart + 128;              // partial sums of a level + the dump tail (64 lanes x 16 bytes)
+        // owner-computes (Umat at p = 3, a whole apply): one launch; the workspace row keeps only its dump tail (a ragged last chunk)
+        const bool own = c->w_own && !splits && op == MIMSEM_OP_UMAT && es.n == 3 && !c->d_tIn && c->w_ntiles == 0;
+        const long long prow = (own ? 0LL : (long long)c->w_npart) + 128;  // partial sums of a level + the dump tail (64 lanes x 16 bytes)
         int g0 = 0, g1 = c->w_ngroups, r0 = 0, r1 = c->w_nps;
         if (splits && part == MIMSEM_PART_BOUNDARY) { g1 = c->w_nbgroups; r1 = c->w_nbrec; }
         if (splits && part == MIMSEM_PART_INTERIOR) { g0 = c->w_nbgroups; r0 = c->w_nbrec; }
-        a.wlane = c->d_wlane; a.wplan = c->d_wplan; a.wgroups = g1 - g0; a.wg0 = g0; a.wdump = c->w_npart;
+        a.wlane = c->d_wlane; a.wplan = own ? c->d_woplan : c->d_wplan; a.wgroups = g1 - g0; a.wg0 = g0; a.wdump = own ? 0 : c->w_npart;
+        a.wgh = own ? c->d_wgh : nullptr; a.wgx = c->d_wgx;
         a.wsing = c->w_nsing ? c->d_wsing : nullptr; a.wnode = c->d_wnode; a.wG = c->d_wG; a.wR = c->d_wR;
         if (c->d_tIn) { a.tIp = c->d_tIn; a.tps = (long long)c->n0*2; a.tnode = 1; }     // (MIMSEM_WAVE_TNODE=1: thickInv per node)
         a.lch = wave_level_chunk(c, nlev);
@@ -1274,7 +1412,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
         }
         // the whole operator in ONE launch: each side of the perimeter is finished by the group that reaches it second (not for the
         // parts of a split apply: their partial sums wait for the other part, and the perimeter pass finishes them)
-        const bool fin = c->w_fin && !splits && !a.wtfin && (nlev + a.lch*a.wcpp - 1)/(a.lch*a.wcpp) <= std::max(c->nk, 1);
+        const bool fin = !own && c->w_fin && !splits && !a.wtfin && (nlev + a.lch*a.wcpp - 1)/(a.lch*a.wcpp) <= std::max(c->nk, 1);
         a.wfin = fin ? c->d_wfin : nullptr; a.wsslot = c->d_wsslot; a.wcnt = c->d_wcnt;
         a.wfence = (fin && c->w_partmem == 2 && exp_env("MIMSEM_WAVE_FIN_FENCE") && atoi(exp_env("MIMSEM_WAVE_FIN_FENCE")) != 0) ? 1 : 0;
         if (splits) {
@@ -1320,7 +1458,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
             }
         }
 #endif
-        if (!rc && !fin) rc = launch_wave_perim(c, nlev, prt, prow, a.accum, y, ys, r0, r1);
+        if (!rc && !fin && !own) rc = launch_wave_perim(c, nlev, prt, prow, a.accum, y, ys, r0, r1);
         if (splits && !rc) {
             if (part == MIMSEM_PART_BOUNDARY) { c->split.pending = true; c->split.op = op; c->split.lev0 = geom_lev0; c->split.nlev = nlev;
                                                 c->split.flags = flags; c->split.y = y; c->split.ys = ys; }
@@ -1521,7 +1659,7 @@ int mimsem_block_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev,
     if ((rc = c->ensure_cheb((pend ? 3 : 1)*n1*nlev))) return rc;
     double* ye = c->d_ye; double* ze = c->d_ye + per*nlev;
     ElemArgs a;
-    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0;
+    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0; a.wgh = nullptr; a.wgx = nullptr;
     a.nEl = c->nEl; a.nlev = nlev; a.lev0 = geom_lev0; a.total = c->nEl*nlev;
     a.flags = flags; a.scale = scale; a.alpha = 1.0;
     a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;
@@ -1615,7 +1753,7 @@ int mimsem_sw_chebyshev_flush(mimsem_ctx* c, int nlev, double ca, double cb, dou
 
 // the element-pass arguments of a single-level sweep on the src/ flavour (scale 1, no thickness), as op_apply_core fills them for its epilogue path
 static void sweep_elem_args(mimsem_ctx* c, ElemArgs& a, const double* f, const double* f2, double param, const double* x, double* out, long long os) {
-    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0;
+    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0; a.wgh = nullptr; a.wgx = nullptr;
     a.nEl = c->nEl; a.nlev = 1; a.lev0 = 0; a.total = c->nEl;
     a.flags = 0; a.scale = 1.0; a.alpha = 1.0;
     a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*c->es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;

@@ -1671,9 +1671,14 @@ static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     constexpr bool TILEABLE = kExperiments && (N == 3 || N == 4) && WNW == 4;      // (tile mode: a closed experiment)
     const bool tile = a.wtfin != nullptr;
     if (tile && (!TILEABLE || a.wgroups%4 != 0 || a.wg0 != 0 || a.lch*a.wcpp > MIMSEM_WTLEV)) return MIMSEM_ERR_STATE;
+    const bool own = a.wgh != nullptr;                   // owner-computes form (Umat at p = 3): one launch, no perimeter pass
+    if (own && (N != 3 || op != MIMSEM_OP_UMAT || tile)) return MIMSEM_ERR_STATE;
+#define MIMSEM_WL2(OPV, LCT, ACC, TL, OW) \
+        if (c->ev_k1[0]) hipExtLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL, OW>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
+        else hipLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL, OW>), dim3(grid), dim3(64*WNW), 0, c->stream, a)
 #define MIMSEM_WL1(OPV, LCT, ACC, TL) \
-        if (c->ev_k1[0]) hipExtLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
-        else hipLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL>), dim3(grid), dim3(64*WNW), 0, c->stream, a)
+        if constexpr (N == 3 && OPV == MIMSEM_OP_UMAT && !TL) { if (own) { MIMSEM_WL2(OPV, LCT, ACC, TL, true); } else { MIMSEM_WL2(OPV, LCT, ACC, TL, false); } } \
+        else { MIMSEM_WL2(OPV, LCT, ACC, TL, false); }
 #define MIMSEM_WL(OPV, LCT, ACC) \
         if constexpr (TILEABLE) { if (tile) { MIMSEM_WL1(OPV, LCT, ACC, true); } else { MIMSEM_WL1(OPV, LCT, ACC, false); } } \
         else { MIMSEM_WL1(OPV, LCT, ACC, false); }
@@ -1689,6 +1694,7 @@ static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
 #undef MIMSEM_WCASE
 #undef MIMSEM_WL
 #undef MIMSEM_WL1
+#undef MIMSEM_WL2
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }

@@ -117,8 +117,14 @@ __device__ __forceinline__ double2 wload2(const void* p) { return *(const double
 // barrier per work item the workgroup adds the pairs and stores the slots straight into y -- the perimeter pass then only sees the tile's
 // OUTER perimeter (half the partial sums, half the slots).  Round 1's workgroup-level form had a barrier per LEVEL (+27 % on the element
 // kernel); this one has a barrier per <= 32 levels.
-template <int N, int OP, int LCT, bool ACCUM, bool TILE = false>
-__global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits<OP>::cf == SN ? 4 : 3, 8))) void k_apply_wave(ElemArgs a) {
+// OWN (round 7, a.wgh; build_wave_own): owner-computes.  Every store pair has one owner group, which also computes the contribution of
+// the neighbour element across each of its (<= 4) GHOST SIDES: a ghost side is a second, virtual element row of the wavefront -- the
+// neighbour's lanes, holding its DoFs on the side and across it (one 8-byte gather per lane and level) and zeros elsewhere -- that runs
+// the element's own DPP algebra with the neighbour's metric and thickInv.  At p = 3 a slot on a side depends on the side's 4 points
+// only, so the side's slots come out with the neighbour's bits; they join the group's sums in the strip.  Every pair is written
+// finished into y by its owner: no partial sums and no perimeter pass.
+template <int N, int OP, int LCT, bool ACCUM, bool TILE = false, bool OWN = false>
+__global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 : (OpTraits<OP>::cf == SN ? 4 : 3), 8))) void k_apply_wave(ElemArgs a) {
     using D = Dims<N>;
     using T = OpTraits<OP>;
     static_assert(T::in == S1 && T::out == S1 && !T::up && T::cf2 == SN, "1-form -> 1-form operators without upwinding");
@@ -127,7 +133,8 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
     constexpr int RS = D::mp1 + (D::mp1 & 1);            // padded row of the y-edge DoFs: 16-byte aligned rows
     constexpr int XT = D::n1e + D::mp1*RS;               // staged DoFs of an element; XT of element 0 is the staging dump
     constexpr int SXE = XT + 2*(LPE - D::n1e) + ((XT + 2*(LPE - D::n1e)) & 1);       // (build_wave_plan uses the same numbers)
-    constexpr int SW = (EPW*SXE > NACC + 136) ? EPW*SXE : NACC + 136;     // strip of one level: staged x, later its summed results
+    constexpr int WGR = NACC + 136;                      // owner-computes: the ghost results of the 64 lanes (build_wave_own uses the same number)
+    constexpr int SW = (EPW*SXE > WGR + (OWN ? 64 : 0)) ? EPW*SXE : WGR + (OWN ? 64 : 0);     // strip of one level: staged x, later its summed results
     constexpr int LB = LCT >= MIMSEM_WLB ? MIMSEM_WLB : (LCT >= 2 ? 2 : LCT);      // levels in lock-step
     static_assert(LCT%LB == 0, "whole batches");
     __shared__ double sE[NW][D::mp1*N];                  // edge-basis table, wave-private copy (written from SGPRs: no load, no barrier)
@@ -138,6 +145,9 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
     __shared__ double s_b[LDSAB ? NW : 1][LDSAB ? LB : 1][LDSAB ? EPW : 1][LDSAB ? LPE : 1];
     static_assert(!TILE || NW == 4, "a tile is the four wavefronts of a workgroup");
     __shared__ double s_t[TILE ? MIMSEM_WTLEV : 1][TILE ? MIMSEM_WTP : 2];      // tile mode: pairs of partial sums of the inner slots, per level of the work item
+    static_assert(!OWN || (N == 3 && OP == MIMSEM_OP_UMAT && !TILE), "owner-computes: Umat at p = 3");
+    constexpr int WGX = MIMSEM_WGX;
+    __shared__ double s_g[OWN ? NW : 1][OWN ? LB : 1][OWN ? WGX + 2 : 1];      // owner-computes: the gathered ghost DoFs of a level | a zero | pad
 
 #ifdef MIMSEM_STAMPS
     const long long t_entry = (long long)__builtin_amdgcn_s_memtime();
@@ -160,6 +170,17 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
 #endif
     const int4 wl = a.wlane[(size_t)g*64 + lane];        // {element, load pair, its staging positions}
     const int4 wp = a.wplan[(size_t)g*64 + lane];        // {store pair destination, result positions}
+    // owner-computes: {metric record, element*16 + point, staged positions of the lane's X | Y << 8 | y-normal side << 16} of the lane in
+    // its ghost row, the slot it gathers
+    int4 gh = {0, 0, 0, 0}; int gxs = 0;
+    double hgaa = 0.0, hgab = 0.0, hgbb = 0.0;
+    if constexpr (OWN) {
+        gh = a.wgh[(size_t)g*64 + lane]; gxs = a.wgx[(size_t)g*64 + lane];
+        const double2* hp = (const double2*)(a.wG + (size_t)gh.x*4);
+        const double2 h01 = hp[0], h23 = hp[1];
+        hgaa = a.scale*h01.x; hgab = a.scale*h01.y; hgbb = a.scale*h23.x;
+    }
+    const unsigned gxo = 8u*(unsigned)gxs, gqg = (unsigned)gh.y;
     // the metric is stored in wave-group order: its address needs no table, so it travels together with the tables
     double gaa = 0.0, gab = 0.0, gbb = 0.0, rdet = 0.0, rr = 0.0;
     if constexpr (OP == MIMSEM_OP_ROTMAT) rr = a.scale*a.wR[(size_t)g*64 + lane];
@@ -188,6 +209,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
     // issuing every level up front put the whole launch's loads in front of the texture addresser before anybody computed
     // (s_memtime stamps: 5.7k of a wave's 20k cycles went into ISSUING 16 loads) ----
     double2 px[LCT]; double pf0[T::cf != SN ? LCT : 1], pt0[LCT], pt1[OP == MIMSEM_OP_UTMAT ? LCT : 1];
+    double pg[OWN ? LCT : 1], ptg[OWN ? LCT : 1];        // owner-computes: the lane's gathered ghost DoF, thickInv of its ghost point
     const size_t lstride = (size_t)a.nEl*D::mp12;
     // the loads run AHEAD batches in front of the computed one, circularly over the LCT levels of a chunk and on into the next chunk
     // of the work item (register r holds level lbeg + r of this chunk, or lbeg + LCT + r of the next once level r is consumed)
@@ -204,6 +226,10 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
                 const int L = a.lev0 + min(lev0_ + i, a.nlev - 1);   // (a level beyond the range reads a valid pair; nothing is stored for it)
                 const double2 tp = WLOAD(double2, (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps) + to);
                 pt0[r0 + i] = tp.x; pt0[r0 + i + 1] = tp.y;
+                if constexpr (OWN) {
+                    const double2 tq = WLOAD(double2, (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps) + 16u*gqg);
+                    ptg[r0 + i] = tq.x; ptg[r0 + i + 1] = tq.y;
+                }
             }
         }
 #pragma unroll
@@ -216,6 +242,10 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
                 const char* tb = (const char*)(a.th + (size_t)(a.lev0 + lev)*lstride);
                 pt0[r] = *(const double*)(tb + 8u*gq); pt1[r] = *(const double*)(tb + 8*lstride + 8u*gq);
             } else if constexpr (!TPAIR) pt0[r] = *(const double*)((const char*)(a.tI + (size_t)(a.lev0 + lev)*lstride) + 8u*gq);
+            if constexpr (OWN) {
+                pg[r] = *(const double*)((const char*)(a.x + (size_t)lev*a.xs) + gxo);
+                if constexpr (!TPAIR) ptg[r] = *(const double*)((const char*)(a.tI + (size_t)(a.lev0 + lev)*lstride) + 8u*gqg);
+            }
         }
     };
     constexpr int AHEAD = (LCT/LB > MIMSEM_WAHEAD) ? MIMSEM_WAHEAD : LCT/LB - 1;      // batches requested ahead of the computed one
@@ -269,7 +299,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
     const long long wst = tin ? 0 : 8*(wy ? a.ys : a.os);
     // optional 8-byte round (MIMSEM_WAVE_SINGLES=1): complete slots without a complete partner, straight into y
     int sp0 = ZERO, sp1 = ZERO; gchar* so = nullptr;
-    if (a.wsing) {
+    if (!OWN && a.wsing) {
         const int2 w = a.wsing[(size_t)g*64 + lane];
         sp0 = w.y & 0xFFFF; sp1 = (w.y >> 16) & 0xFFFF;
         so = (gchar*)(w.x >= 0 ? a.y + (size_t)lbeg*a.ys + w.x : a.out + a.wdump + lane);
@@ -280,7 +310,10 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
     WSTAMP(3);                                           // level loads issued
     static_assert(ZERO >= EPW*SXE && ZERO < SW, "the zero entry lies beyond the staged x and the results: written once");
 #pragma unroll
-    for (int i = 0; i < LB; i++) s_x[wv][i][ZERO] = 0.0;     // every lane, same value: the second operand of single-contributor sums
+    for (int i = 0; i < LB; i++) {
+        s_x[wv][i][ZERO] = 0.0;                           // every lane, same value: the second operand of single-contributor sums
+        if constexpr (OWN) s_g[wv][i][WGX] = 0.0;         // X / Y of a ghost-row lane that no point of the side reads (as the element's zeros)
+    }
     gchar* const dumpp = (gchar*)(a.out + a.wdump + 2*lane);   // tail of the first partial-sum row
     gchar* const dumps = (gchar*)(a.out + a.wdump + lane);
     for (int cc = 0; cc < a.wcpp; cc++, lbeg += a.lch) {
@@ -296,9 +329,10 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
             double* st = s_x[wv][i];
             st[xd00] = px[b0 + i].x; st[xd01] = px[b0 + i].x; st[xd10] = px[b0 + i].y; st[xd11] = px[b0 + i].y;
             if constexpr (T::cf == S2 && !DPP) s_f[wv][i][el][q] = pf0[b0 + i];
+            if constexpr (OWN) s_g[wv][i][lane] = pg[b0 + i];
         }
         wave_fence();
-        double yxr[LB], yyr[LB];
+        double yxr[LB], yyr[LB], gyr[OWN ? LB : 1];
 #pragma unroll
         for (int i = 0; i < LB; i++) {
             const int l = b0 + i;
@@ -340,6 +374,14 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
             else { ra = fac*fma(gab, v, gaa*u); rb = fac*fma(gbb, v, gab*u); }      // explicit fma: identical bits in every instantiation
             if constexpr (DPP) { yxr[i] = dpp_rows(cp, ra); yyr[i] = dpp_quad<4>(pq, rb); }
             else { s_a[wv][i][el][q] = ra; s_b[wv][i][el][q] = rb; }
+            if constexpr (OWN) {                          // the ghost row: the same algebra on the neighbour's operands, metric and thickInv
+                const double GX = s_g[wv][i][gh.z & 0xFF], GY = s_g[wv][i][(gh.z >> 8) & 0xFF];
+                const double gu_ = dpp_rows(cu, GX), gv_ = dpp_quad<3>(Ex, GY);
+                const double gf = vert ? ptg[l] : 1.0;
+                const double gra = gf*fma(hgab, gv_, hgaa*gu_), grb = gf*fma(hgbb, gv_, hgab*gu_);
+                const double gyx = dpp_rows(cp, gra), gyy = dpp_quad<4>(pq, grb);
+                gyr[i] = (gh.z >> 16) ? gyy : gyx;         // the slots of a y-normal side are y-edge DoFs, of an x-normal one x-edge DoFs
+            }
         }
         wave_fence();                                     // (DPP form: every lane has read its DoFs: the strips may take the results)
 #pragma unroll
@@ -357,6 +399,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
             }
             double* sacc = s_x[wv][i];                    // the level's x is spent: its strip takes the results
             sacc[aci0] = yx; sacc[aci1] = yy;
+            if constexpr (OWN) sacc[WGR + lane] = gyr[i];  // the neighbour's contribution to the ghost slot of this lane
         }
         wave_fence();
 #pragma unroll
@@ -378,7 +421,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
                 if (tin) { double* td = &s_t[cc*a.lch + l][tpo]; td[0] = val.x; td[1] = val.y; }      // an LDS store under the lane's mask: no vmcnt involved
             }
             wo += wst;
-            if (a.wsing) {                                // wave-uniform; off by default
+            if (!OWN && a.wsing) {                        // wave-uniform; off by default
                 const double v1 = sacc[sp0] + sacc[sp1];
                 gdouble* o1 = (gdouble*)(l < nl ? so : dumps);
                 if constexpr (ACCUM) *o1 = (sst ? *o1 : 0.0) + v1; else *o1 = v1;
@@ -414,7 +457,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OpTraits
     // 16-byte load and one 8-byte store per lane (64 lanes = 4 entry pairs x 8 levels x 2 parts).  Nobody waits for anybody: a group
     // that arrives first simply leaves.  The finishing wave sets the counter back to 0.  Every y slot is written by exactly one
     // wavefront of the launch (a complete pair by its group, an entry of a side by the side's finisher).
-    if (a.wfin) {                                          // wave-uniform
+    if (!OWN && a.wfin) {                                  // wave-uniform (the owner-computes form has nothing to finish)
         WSTAMP(11);                                        // chunks done, stores issued
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // (round 4, the fifth way: plain memory + ONE release fence -- buffer_wbl2 sc1, the XCD's dirty lines written back in bulk -- instead of
