@@ -692,13 +692,24 @@ int  mimsem_halo_set_loopback(mimsem_halo* plan);
  * communication stream on the critical path, recordable in a hipGraph (mimsem_graph_begin/_end) with the solver around it.  Set-up, once
  * per plan: every rank calls _peer_export, the host exchanges the blobs (MPI_Allgather of MIMSEM_HALO_PEER_BLOB bytes per rank and plan),
  * then every rank calls _set_peer with its neighbours' blobs in the plan's neighbour order.  Ranks of one node, one process per rank
- * (a rank may list itself: its own buffer).  The wait is bounded (~2 s): _peer_status reports an exchange that gave up.
+ * (a rank may list itself: its own buffer).  The wait is bounded (~2 s): the unpack then sets the plan's error word and unpacks what the buffer
+ * holds -- a STALE halo.  _peer_status reports it; the hosts (C++: Shard::use_peer + src::SWEqn / HorizSolve; Python: DistEngine) read it with
+ * every Picard iteration's (evaluation's) one all-reduce and stop every rank together (HaloTimeout).  The C++ host's set-up is Shard::use_peer
+ * (mimsem_amd/host/mimsem_shard.hpp: export, one all-gather of the blobs, _set_peer on the pair and node plans).
  * Status: verified between processes on ONE GPU, bit-equal to the callback transport; not yet A/B-ed against RCCL between GPUs --
  * RCCL stays the default transport of the hosts.                                                                                       */
 #define MIMSEM_HALO_PEER_BLOB 1024
 int  mimsem_halo_peer_export(mimsem_halo* plan, int my_rank, void* blob /* MIMSEM_HALO_PEER_BLOB bytes, host */);
 int  mimsem_halo_set_peer(mimsem_halo* plan, int my_rank, const void* neighbour_blobs /* nneigh x MIMSEM_HALO_PEER_BLOB bytes, host */);
 int  mimsem_halo_peer_status(mimsem_halo* plan, unsigned long long* timed_out_seq);
+/* What _peer_export got for the plan's receive buffer: *uncached = 1 for uncached device memory (what a neighbour GPU writes over xGMI is seen
+ * by a kernel that is already running here), 0 for the ordinary-memory fallback when the runtime refuses the flag (coherent between GPUs at
+ * kernel boundaries only: fine for ranks on ONE GPU, not between GPUs).  MIMSEM_ERR_STATE before the first _peer_export.                   */
+int  mimsem_halo_peer_info(mimsem_halo* plan, int* uncached);
+/* Test infrastructure of the status path (replaces nothing in the reference): writes `seq` into the plan's error word from the host, as if
+ * exchange `seq` had given up its wait -- _peer_status then reports it, and the hosts' status checks must stop every rank.
+ * No kernel waits and nothing on the GPU faults.  Synchronises the context's stream.  MIMSEM_ERR_STATE before the first _peer_export.      */
+int  mimsem_halo_peer_mark_for_test(mimsem_halo* plan, unsigned long long seq);
 int  mimsem_halo_begin(mimsem_halo* plan, int mode, int nlev, double* v, long long v_stride);
 int  mimsem_halo_end(mimsem_halo* plan);
 

@@ -147,6 +147,8 @@ _SIGS = {
     "mimsem_halo_peer_export": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mimsem_halo_set_peer": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mimsem_halo_peer_status": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "mimsem_halo_peer_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "mimsem_halo_peer_mark_for_test": (C.c_int, [C.c_void_p, C.c_ulonglong]),
     "mimsem_hessenberg_eigenvalues": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mimsem_column_flag_for_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "mimsem_krylov_chebyshev_update": (C.c_int, [C.c_void_p, C.c_int, c_ll, C.c_double, C.c_double, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),

@@ -44,6 +44,7 @@ struct mimsem_halo {
     long long peer_off[MIMSEM_HALO_MAX_SEGMENTS] = {};       // where MY message starts in neighbour i's buffer (slots per level)
     int peer_slot[MIMSEM_HALO_MAX_SEGMENTS] = {};            // which of neighbour i's flags is mine
     int my_rank = -1;
+    int peer_uncached = -1;                                  // -1 not exported yet, else whether d_peer is UNCACHED device memory
     mimsem_halo_transport_fn fn = nullptr; void* user = nullptr;
     void* nccl_comm = nullptr;
     // state of the exchange in flight
@@ -262,6 +263,7 @@ int mimsem_halo_peer_export(mimsem_halo* h, int my_rank, void* blob) {
             MIMSEM_HIP_TRY(hipMalloc((void**)&h->d_peer, bytes));
         }
         if (getenv("MIMSEM_VERBOSE")) fprintf(stderr, "[mimsem] halo plan %p: one-sided receive buffer %zu bytes, %s device memory\n", (void*)h, bytes, uncached ? "UNCACHED" : "ordinary (hipExtMallocWithFlags refused)");
+        h->peer_uncached = uncached ? 1 : 0;
         MIMSEM_HIP_TRY(hipMemset(h->d_peer, 0, bytes));
         h->d_flags = (unsigned long long*)(h->d_peer + 2*h->peer_half);
     }
@@ -393,6 +395,24 @@ int mimsem_halo_peer_status(mimsem_halo* h, unsigned long long* timed_out_seq) {
     if (h->transport != 4 || !h->d_flags) return MIMSEM_OK;
     MIMSEM_HIP_TRY(hipStreamSynchronize(h->c->stream));
     MIMSEM_HIP_TRY(hipMemcpy(timed_out_seq, h->d_flags + PEER_ERR, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return MIMSEM_OK;
+}
+// what _peer_export got for the receive buffer: 1 = uncached device memory, 0 = the ordinary-memory fallback (not coherent between GPUs
+// while a kernel runs); MIMSEM_ERR_STATE before the first export
+int mimsem_halo_peer_info(mimsem_halo* h, int* uncached) {
+    if (!h || !uncached) return MIMSEM_ERR_ARG;
+    if (h->peer_uncached < 0) return MIMSEM_ERR_STATE;
+    *uncached = h->peer_uncached;
+    return MIMSEM_OK;
+}
+// test infrastructure: write `seq` into the error word from the host, as if exchange `seq` had given up waiting (the status path of the hosts
+// is tested through this; nothing waits and nothing faults).  Synchronises the context's stream first.  MIMSEM_ERR_STATE before an export.
+int mimsem_halo_peer_mark_for_test(mimsem_halo* h, unsigned long long seq) {
+    if (!h) return MIMSEM_ERR_ARG;
+    if (!h->d_flags) return MIMSEM_ERR_STATE;
+    MIMSEM_HIP_TRY(hipSetDevice(h->c->device));
+    MIMSEM_HIP_TRY(hipStreamSynchronize(h->c->stream));
+    MIMSEM_HIP_TRY(hipMemcpy(h->d_flags + PEER_ERR, &seq, sizeof seq, hipMemcpyHostToDevice));
     return MIMSEM_OK;
 }
 

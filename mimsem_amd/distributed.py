@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 
 from .device import Engine
-from .partition import CHalo, HaloExchanger, build_plans
+from .partition import CHalo, HaloExchanger, HaloTimeout, build_plans  # noqa: F401 -- HaloTimeout: raised by the hosts that fold peer_timeouts()
 
 
 class RcclComm:
@@ -160,6 +160,24 @@ class DistEngine:
         self.chalo = self.chalo0 = None
         if self.rccl is not None:
             self.rccl.close(); self.rccl = None
+
+    def peer_timeouts(self):
+        """one-sided transport: how many of this rank's C-ABI plans report an exchange that gave up waiting (0 on any other transport).  A host
+        folds it into an all-reduce it does anyway and raises HaloTimeout on a non-zero sum: every rank then stops after the same collective."""
+        if getattr(self, "transport", None) != "peer":
+            return 0
+        return sum(len(h.peer_timeouts()) for h in (self.chalo, self.chalo0) if h is not None)
+
+    def allreduce_checked(self, t, op="sum"):
+        """allreduce() of t with this rank's peer_timeouts() folded in as one more entry: raises HaloTimeout on every rank when any rank's
+        exchange timed out; returns the reduced t"""
+        ext = torch.cat([t.reshape(-1), torch.tensor([float(self.peer_timeouts())], dtype=t.dtype, device=t.device)])
+        self.allreduce(ext, op)
+        n = float(ext[-1])
+        if n != 0.0:
+            raise HaloTimeout("%d halo plan(s) gave up waiting for an exchange of the one-sided transport: the halo is stale" % int(n))
+        t.copy_(ext[:-1].reshape(t.shape))
+        return t
 
     def allreduce(self, t, op="sum"):
         if self.world == 1:

@@ -9,7 +9,8 @@
 // SHARDED (round 6): with a Shard (mimsem_shard.hpp) every 0/1-form result is completed over the halo -- one exchange per operator result,
 // accumulations (MIMSEM_FLAG_ACCUM) through a completed temporary --, the ksp1 solves are the fixed-length Chebyshev iteration with both
 // element-local sums of a sweep completed (no inner product: no all-reduce inside a solve), their spectral interval comes from Shard::ritz,
-// the check log is ownership-weighted and all-reduced ONCE by verify(), and k2i() is an all-reduced weighted sum.
+// the check log is ownership-weighted and all-reduced ONCE by verify(), and k2i() is an all-reduced weighted sum.  On the one-sided transport
+// (Shard::use_peer; eager here) verify()'s all-reduce also carries the rank's count of exchanges that gave up waiting: HaloTimeout on every rank.
 #pragma once
 #include <cmath>
 #include <utility>
@@ -112,9 +113,16 @@ public:
     // contraction lies between it and the result).  false: fixed_length is off now -- redo the evaluation (it then runs the CG).  Synchronises.
     bool verify() {
         if (!fixed_length && slot == 0) return true;
-        double v[2*MAXLOG];
+        double v[2*MAXLOG + 1];
         mesh->to_host(v, chk, 2*MAXLOG);
-        if (sh) sh->allreduce(v, 2*MAXLOG);                          // ONE all-reduce for every solve since the last call
+        if (sh) {                                                    // ONE all-reduce for every solve since the last call, with this rank's count of
+            v[2*MAXLOG] = (double)sh->peer_timeouts();               // one-sided plans that gave up waiting (every rank sees any rank's time-out)
+            sh->allreduce(v, 2*MAXLOG + 1);
+            if (v[2*MAXLOG] != 0.0) {
+                check(mimsem_memset(mesh->ctx, chk, 0, 2*MAXLOG*8), "mimsem_memset"); slot = 0;
+                throw HaloTimeout("HorizSolve (sharded): " + std::to_string((long)v[2*MAXLOG]) + " halo plan(s) gave up waiting for an exchange of the one-sided transport: the halo is stale");
+            }
+        }
         check(mimsem_memset(mesh->ctx, chk, 0, 2*MAXLOG*8), "mimsem_memset");
         slot = 0;
         bool ok = true;

@@ -7,9 +7,15 @@
 #include <cmath>
 #include <functional>
 #include <random>
+#include <stdexcept>
 #include "mimsem_shim.hpp"
 
 namespace mimsem_host {
+
+// An exchange of the one-sided transport gave up its bounded wait on some rank (a neighbour that never published): the halo it unpacked is
+// stale.  Thrown by src::SWEqn and HorizSolve on EVERY rank after the same all-reduce (the time-out count rides in it), so no rank is left
+// waiting in an exchange or a collective.
+struct HaloTimeout : std::runtime_error { using std::runtime_error::runtime_error; };
 
 // A rank's share of the exchanges and reductions when the mesh is dealt to several ranks: what replaces VecScatter on gtol_0 /
 // gtol_1 (eul/Topo.cpp:145-155) and MPI_Allreduce in the reference's distributed solves.  Slot lists as for VecScatterHalo: per neighbour
@@ -25,7 +31,7 @@ public:
     Shard(Mesh* m, const std::vector<int>& ranks, const std::vector<int>& ghost1, const std::vector<int>& ghost1_off, const std::vector<int>& mirror1,
           const std::vector<int>& mirror1_off, const std::vector<int>& ghost0, const std::vector<int>& ghost0_off, const std::vector<int>& mirror0,
           const std::vector<int>& mirror0_off, const std::vector<double>& own0_host, const std::vector<double>& own1_host, allreduce_fn ar, void* ar_user)
-        : mesh(m), nodes(m, 0, ranks, ghost0, ghost0_off, mirror0, mirror0_off), reduce(ar), user(ar_user) {
+        : mesh(m), nodes(m, 0, ranks, ghost0, ghost0_off, mirror0, mirror0_off), ranks_(ranks), reduce(ar), user(ar_user) {
         const int nn = (int)ranks.size();
         std::vector<int> pidx, poff(1, 0);
         for (int i = 0; i < nn; i++) {                                  // every slot shared with neighbour i, in slot (= global) order on both sides
@@ -47,6 +53,21 @@ public:
     Shard(const Shard&) = delete; Shard& operator=(const Shard&) = delete;
     void use_transport(mimsem_halo_transport_fn fn, void* u) { nodes.use_transport(fn, u); check(mimsem_halo_set_transport(pair, fn, u), "set_transport"); }
     void use_rccl(void* nccl_comm) { nodes.use_rccl(nccl_comm); check(mimsem_halo_set_rccl(pair, nccl_comm), "set_rccl"); }
+    // the ONE-SIDED transport on all three plans (pair, node REVERSE, node FORWARD): kernels only, so src::SWEqn records its sharded Picard
+    // iteration as a hipGraph.  allgather: VecScatterHalo::allgather_fn (the host's MPI_Allgather), called once; world 0 = asked of the all-reduce
+    void use_peer(int my_rank, VecScatterHalo::allgather_fn allgather, void* u, int world = 0) {
+        if (world <= 0) {
+            double w = 1.0;
+            if (!reduce || reduce(user, &w, 1) != 0) throw std::runtime_error("Shard::use_peer: the host's all-reduce failed");
+            world = (int)std::lround(w);
+        }
+        VecScatterHalo::connect_peer({pair, nodes.reverse_plan(), nodes.forward_plan()}, ranks_, my_rank, allgather, u, world);
+        peer_ = true;
+    }
+    bool peer() const { return peer_; }                                  // the one-sided transport is in use
+    bool uncached() const { return peer_ && VecScatterHalo::plan_uncached(pair) && nodes.uncached(); }      // every plan's receive buffer uncached
+    // plans whose error word is set (an exchange that gave up waiting); 0 off the one-sided transport.  Synchronises the context's stream.
+    int peer_timeouts() const { return peer_ ? VecScatterHalo::plan_timed_out(pair) + nodes.peer_timeouts() : 0; }
     // complete a vector of element-local partial sums: nlev level rows, n1 (n0) doubles apart
     void complete1(double* v, int nlev = 1) { exchanges++; check(mimsem_halo_begin(pair, MIMSEM_HALO_ADD, nlev, v, mesh->n1), "halo_begin"); check(mimsem_halo_end(pair), "halo_end"); }
     void complete0(double* v, int nlev = 1) { exchanges += 2; nodes.reverse_add(v, nlev, mesh->n0); nodes.forward_insert(v, nlev, mesh->n0); }
@@ -103,10 +124,11 @@ public:
         } catch (...) { mimsem_free(V); mimsem_free(w); mimsem_free(tmp); mimsem_free(h); throw; }
         mimsem_free(V); mimsem_free(w); mimsem_free(tmp); mimsem_free(h);
     }
-    Mesh* mesh; VecScatterHalo nodes; mimsem_halo* pair = nullptr;
+    Mesh* mesh; VecScatterHalo nodes; std::vector<int> ranks_; mimsem_halo* pair = nullptr;
     double *own0 = nullptr, *own1 = nullptr, *ownx = nullptr;
     long exchanges = 0, allreduces = 0;                                 // counters (tests: no all-reduce inside a solve)
 private:
+    bool peer_ = false;
     allreduce_fn reduce; void* user;
 };
 

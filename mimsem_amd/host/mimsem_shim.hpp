@@ -12,7 +12,9 @@
 // Topo / Geom here are minimal stand-ins exposing exactly the public members the operator classes read
 // (eul/Topo.h:5-51, eul/Geom.h:8-36); a maintainer passes the real objects instead.
 #pragma once
+#include <algorithm>
 #include <cstddef>
+#include <cstring>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -182,6 +184,7 @@ public:
                                  nslots, m->nk_, &rev), "mimsem_halo_create(reverse)");
         check(mimsem_halo_create(m->ctx, nn, ranks.data(), mirror_idx.data(), mirror_off.data(), ghost_idx.data(), ghost_off.data(),
                                  nslots, m->nk_, &fwd), "mimsem_halo_create(forward)");
+        ranks_ = ranks;
         if (form == 1) {                       // the slots that travel: their element groups go first in the operators' plans
             std::vector<int> shared(ghost_idx); shared.insert(shared.end(), mirror_idx.begin(), mirror_idx.end());
             check(mimsem_ctx_set_halo_slots(m->ctx, 1, shared.data(), (int)shared.size()), "mimsem_ctx_set_halo_slots");
@@ -196,6 +199,36 @@ public:
     static int use_rccl_library(void* dl_handle) { return mimsem_halo_use_rccl_library(dl_handle); }
     void use_transport(mimsem_halo_transport_fn fn, void* user) { check(mimsem_halo_set_transport(rev, fn, user), "set_transport"); check(mimsem_halo_set_transport(fwd, fn, user), "set_transport"); }
     void use_loopback() { check(mimsem_halo_set_loopback(rev), "set_loopback"); check(mimsem_halo_set_loopback(fwd), "set_loopback"); }
+    // ONE-SIDED transport (mimsem_halo_peer_export / _set_peer): allgather(user, mine, all, bytes) stands where the host calls MPI_Allgather --
+    // `bytes` from every rank into `all` ([world][bytes], rank order), 0 = ok.  Collective: every rank calls it, the same number of times.
+    // world: the ranks of the host's communicator (the size of `all`); 0 = one more than the largest rank this plan names (itself included).
+    using allgather_fn = int (*)(void* user, const void* mine, void* all, int bytes);
+    void use_peer(int my_rank, allgather_fn allgather, void* user, int world = 0) { connect_peer({rev, fwd}, ranks_, my_rank, allgather, user, world); }
+    // the set-up of the one-sided transport for plans over the same neighbour list: every plan exported, ONE all-gather of the blobs, each plan
+    // handed its neighbours' blobs in its neighbour order (what CHalo(transport="peer") of mimsem_amd/partition.py does over torch.distributed)
+    static void connect_peer(const std::vector<mimsem_halo*>& plans, const std::vector<int>& ranks, int my_rank, allgather_fn allgather, void* user, int world) {
+        const size_t B = MIMSEM_HALO_PEER_BLOB, np_ = plans.size();
+        if (!allgather) throw std::runtime_error("use_peer: no all-gather");
+        int named = my_rank;
+        for (int r : ranks) named = std::max(named, r);
+        if (world <= 0) world = named + 1;
+        if (my_rank < 0 || named >= world) throw std::runtime_error("use_peer: a rank outside the world");
+        std::vector<char> mine(np_*B), all((size_t)world*np_*B), theirs(std::max<size_t>(ranks.size(), 1)*B);
+        for (size_t p = 0; p < np_; p++) check(mimsem_halo_peer_export(plans[p], my_rank, mine.data() + p*B), "mimsem_halo_peer_export");
+        if (allgather(user, mine.data(), all.data(), (int)(np_*B)) != 0) throw std::runtime_error("use_peer: the host's all-gather failed");
+        for (size_t p = 0; p < np_; p++) {
+            for (size_t i = 0; i < ranks.size(); i++) std::memcpy(theirs.data() + i*B, all.data() + ((size_t)ranks[i]*np_ + p)*B, B);
+            check(mimsem_halo_set_peer(plans[p], my_rank, ranks.empty() ? nullptr : theirs.data()), "mimsem_halo_set_peer");
+        }
+    }
+    // one-sided transport: whether every plan's receive buffer is uncached device memory / how many plans' error words are set (an exchange
+    // whose wait gave up after ~2 s; reading it synchronises the context's stream)
+    bool uncached() const { return plan_uncached(rev) && plan_uncached(fwd); }
+    int peer_timeouts() const { return plan_timed_out(rev) + plan_timed_out(fwd); }
+    static bool plan_uncached(mimsem_halo* h) { int u = 0; return mimsem_halo_peer_info(h, &u) == MIMSEM_OK && u == 1; }
+    static int plan_timed_out(mimsem_halo* h) { unsigned long long s = 0; check(mimsem_halo_peer_status(h, &s), "mimsem_halo_peer_status"); return s != 0; }
+    mimsem_halo* reverse_plan() const { return rev; }
+    mimsem_halo* forward_plan() const { return fwd; }
     void begin_reverse_add(double* v, int nlev, long long stride) { check(mimsem_halo_begin(rev, MIMSEM_HALO_ADD, nlev, v, stride), "halo_begin"); }
     void end_reverse_add() { check(mimsem_halo_end(rev), "halo_end"); }
     void begin_forward_insert(double* v, int nlev, long long stride) { check(mimsem_halo_begin(fwd, MIMSEM_HALO_INSERT, nlev, v, stride), "halo_begin"); }
@@ -203,7 +236,7 @@ public:
     void reverse_add(double* v, int nlev, long long stride) { begin_reverse_add(v, nlev, stride); end_reverse_add(); }
     void forward_insert(double* v, int nlev, long long stride) { begin_forward_insert(v, nlev, stride); end_forward_insert(); }
 private:
-    Mesh* mesh; mimsem_halo *rev = nullptr, *fwd = nullptr;
+    Mesh* mesh; mimsem_halo *rev = nullptr, *fwd = nullptr; std::vector<int> ranks_;
 };
 
 // A recorded launch sequence (mimsem_graph_*): the reference's per-level loops -- for (kk ...) { M1->assemble(kk, SCALE, true);

@@ -15,6 +15,9 @@
 //                 iteration, ownership-weighted partial sums, are reduced ONCE (Shard::allreduce: the host's MPI_Allreduce).  The spectral
 //                 regions come from an Arnoldi process of the host's own (Shard::ritz: weighted, all-reduced inner products, once per dt).
 //                 The reference's distributed step: src/SWEqn_Picard.cpp:751-765, gtol_x :131-153, :341-400, ghost updates :422-425.
+//                 On the one-sided transport (Shard::use_peer: every exchange two kernels) the sharded iteration is recorded and replayed like the
+//                 one-context one; the all-reduce of its check norms carries one more slot, the rank's count of exchanges that gave up waiting --
+//                 any rank's time-out stops every rank after that same all-reduce (HaloTimeout).
 // Header-only, C++17, no HIP toolchain needed (everything goes through include/mimsem_hip.h).
 #pragma once
 #include <algorithm>
@@ -23,6 +26,7 @@
 #include <cstdlib>
 #include <functional>
 #include <random>
+#include <string>
 #include <utility>
 #include "mimsem_shard.hpp"
 
@@ -69,14 +73,17 @@ public:
     int fallbacks = 0;                   // Picard iterations the fixed mode handed to the krylov mode
     int steps_A = 0, steps_M1 = 0, steps_q = 0;
     int graph_nodes(bool first) const { return have_graph[first ? 0 : 1] ? gr[first ? 0 : 1].nodes() : 0; }      // launches of a recorded Picard iteration (0: not recorded)
+    long exchanges_per_iteration(bool first) const { return exch_of[first ? 0 : 1]; }      // (sharded) halo exchanges of the last eager iteration of that kind
     double us_submit = 0.0, us_wait = 0.0; long replays = 0;      // host time inside the graph submissions / waiting for the check norms
 
     // fg: the Coriolis 0-form (SWEqn::coriolis, src/SWEqn_Picard.cpp:95-140), device, n0 entries; it must outlive the object
     // shard (optional): this rank's exchanges and reductions when the sphere is dealt to several ranks -- fixed-length mode only (the KSP objects
-    // of the krylov mode iterate inside the library on one context's operator), eager launches with the exchanges in between (no graph)
+    // of the krylov mode iterate inside the library on one context's operator).  On the callback or RCCL transport: eager launches with the
+    // exchanges in between (no graph); on the one-sided transport (Shard::use_peer, BEFORE this constructor) every exchange is two kernels and
+    // the Picard iteration is recorded as on one context
     SWEqn(Mesh* m, const double* fg_dev, Shard* shard = nullptr) : mesh(m), fg(fg_dev), sh(shard), ksp1(m, KSP::CG), ksp0(m, KSP::GMRES), kspA(m, KSP::GMRES), M1(m), gr{Graph(m), Graph(m)} {
         n0 = m->n0; n1 = m->n1; n2 = m->n2; N = (long long)n1 + n2;
-        if (sh) use_graph = false;
+        if (sh && !sh->peer()) use_graph = false;
         if (std::getenv("MIMSEM_EXPERIMENTS") && std::atoi(std::getenv("MIMSEM_EXPERIMENTS"))) {      // (closed experiments; A/B: scripts/ab_sw_cpp.sh)
             if (const char* e = std::getenv("MIMSEM_SW_STEP2")) two_launch_steps = std::atoi(e) != 0;
             if (const char* e = std::getenv("MIMSEM_SW_DUAL")) dual_solves = std::atoi(e) != 0;
@@ -204,7 +211,7 @@ private:
     const double *blocksA = nullptr, *blocks1 = nullptr, *escale1 = nullptr;
     std::vector<std::pair<double, double>> coefM, qcoef; double thetaA = 1.0, deltaA = 1.0;
     bool inline_fixed = false, can_fix = false;
-    int slot = 0; int kinds[NSLOT] = {0}; int kinds_of[2][NSLOT] = {{0}}; int nslots_of[2] = {0, 0};
+    int slot = 0; int kinds[NSLOT] = {0}; int kinds_of[2][NSLOT] = {{0}}; int nslots_of[2] = {0, 0}; long exch_of[2] = {0, 0};
     const double *q_h = nullptr, *q_u = nullptr; double q_tau = 0.0;
 
     static size_t even(long long n) { return (size_t)((n + 1) & ~1LL); }
@@ -493,7 +500,7 @@ private:
     // one Picard iteration; returns |dx| / |x|
     double iteration(bool first) {
         const int g = first ? 0 : 1;
-        double v[2*NSLOT];
+        double v[2*NSLOT + 1];
         if (fixed_length && can_fix) {
             inline_fixed = true;
             const auto t0 = std::chrono::steady_clock::now();
@@ -501,14 +508,24 @@ private:
             const bool replay = use_graph && have_graph[g];
             if (replay) { gr[g].launch(); t1 = std::chrono::steady_clock::now(); }
             else {
+                const long e0 = sh ? sh->exchanges : 0;
                 body(first);                                   // eagerly the first time (the library's workspaces get their sizes) ...
+                exch_of[g] = sh ? sh->exchanges - e0 : 0;
                 for (int k = 0; k < slot; k++) kinds_of[g][k] = kinds[k];
                 nslots_of[g] = slot;
                 warm[g] = true;
             }
             inline_fixed = false;
             mesh->to_host(v, chk, 2*NSLOT);
-            if (sh) sh->allreduce(v, 2*nslots_of[g]);          // the ONE all-reduce of a Picard iteration: every check norm was a rank-local, ownership-weighted sum
+            if (sh) {
+                // the ONE all-reduce of a Picard iteration: every check norm was a rank-local, ownership-weighted sum -- and one more slot, this rank's
+                // count of one-sided plans whose exchange gave up waiting (read beside the norms: the stream is idle already), so that EVERY rank
+                // sees ANY rank's time-out after the same all-reduce and all of them stop here together
+                const int n = 2*nslots_of[g];
+                v[n] = (double)sh->peer_timeouts();
+                sh->allreduce(v, n + 1);
+                if (v[n] != 0.0) throw HaloTimeout("SWEqn (sharded): " + std::to_string((long)v[n]) + " halo plan(s) gave up waiting for an exchange of the one-sided transport: the halo is stale");
+            }
             if (replay) {
                 const auto t2 = std::chrono::steady_clock::now();
                 us_submit += std::chrono::duration<double, std::micro>(t1 - t0).count(); us_wait += std::chrono::duration<double, std::micro>(t2 - t1).count();

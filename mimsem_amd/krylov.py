@@ -324,7 +324,7 @@ class MassSolver:
         if self._log is None or self._slot == 0:
             return True
         if self.dist:
-            self.eng.allreduce(self._log)                       # ONE all-reduce for every solve since the last call
+            self.eng.allreduce_checked(self._log)               # ONE all-reduce for every solve since the last call (+ the halo time-outs: HaloTimeout)
         v = self._log.cpu().numpy()
         self._log.zero_(); self._slot = 0
         nlev = v.shape[1] // 2

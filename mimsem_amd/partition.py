@@ -282,6 +282,11 @@ def rank_mesh(sphere, geoms_or_none, world, rank, nk, coords=None):
     return pids, topos, geoms
 
 
+class HaloTimeout(RuntimeError):
+    """An exchange of the one-sided transport gave up its bounded wait on some rank (a neighbour that never published): the halo it unpacked
+    is stale.  Raised on EVERY rank after the same all-reduce (the time-out count rides in it), so no rank is left waiting in a collective."""
+
+
 class CHalo:
     """The same exchanges through the C ABI (mimsem_halo_create / _begin / _end, include/mimsem_hip.h): what a C++ host binds instead
     of VecScatterBegin/End.  Pack, transport and unpack are driven by the library; this class only builds the slot lists from a
@@ -399,6 +404,22 @@ class CHalo:
             if v.value:
                 out[name] = v.value
         return out
+
+    def uncached(self):
+        """one-sided transport: True when every plan's receive buffer is uncached device memory (False: the ordinary-memory fallback,
+        coherent between GPUs at kernel boundaries only; None: not on the one-sided transport)"""
+        C = self.C
+        vals = []
+        for h in self.handles.values():
+            v = C.c_int(0)
+            if self.L.mimsem_halo_peer_info(h, C.byref(v)) != 0:
+                return None
+            vals.append(v.value == 1)
+        return all(vals)
+
+    def mark_for_test(self, name="pair", seq=1):
+        """test infrastructure: write `seq` into plan `name`'s error word as if that exchange had timed out (nothing waits, nothing faults)"""
+        self._check(self.L.mimsem_halo_peer_mark_for_test(self.handles[name], seq), "halo_peer_mark_for_test")
 
     def close(self):
         for h in self.handles.values():

@@ -904,8 +904,7 @@ class _PicardGraph:
             finally:
                 S._inline = None
             self.graphs[first] = (None, dict(self.names), self.nslots)
-            S.eng.allreduce(self.chk)
-            return self.chk.tolist()
+            return self._reduce()
         if first not in self.graphs:
             keep = self.x.clone()
             S._inline = self
@@ -917,7 +916,13 @@ class _PicardGraph:
         g, _, _ = self.graphs[first]
         g.replay()
         if self.dist:
-            S.eng.allreduce(self.chk)
+            return self._reduce()
+        return self.chk.tolist()
+
+    def _reduce(self):
+        """the ONE all-reduce of a sharded Picard iteration: the check norms, with this rank's count of one-sided halo plans whose exchange gave
+        up waiting folded in (DistEngine.allreduce_checked) -- every rank sees any rank's time-out after the same collective and raises HaloTimeout"""
+        self.S.eng.allreduce_checked(self.chk)
         return self.chk.tolist()
 
     def verify(self, vals, first):
