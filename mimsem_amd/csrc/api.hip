@@ -468,18 +468,22 @@ int build_wave_plan(int order, int n1, int nEl, int n1e, int n0e, int G, const i
 // owner group, and the owner computes the contribution of a neighbour element to the pair's slots itself, so that it writes the FINISHED
 // value straight into y -- no partial sums, no perimeter pass.  At p = 3 the quadrature points are the GLL nodes: an edge slot on a side
 // of an element depends on the 4 points of that side only (its 3 side DoFs, the 12 cross-edge DoFs of the point rows, metric and thickInv
-// at the 4 points).  A "ghost side" = (neighbour element, which of its 4 sides) is a virtual element row of the owner's wavefront: 16
-// lanes laid out as the neighbour's, which run the element algebra on the side's 15 DoFs (gathered, one per lane) and zeros elsewhere.
-//   gh [g][64] lane of ghost row r = lane/16 {metric record of the neighbour's point (wave-group order), element*16 + point, staged
-//              position of the lane's X | of its Y << 8 | y-normal side << 16 (WGX: the strip's zero)}
-//   gx [g][64] slot gathered by lane t into position t of the strip
-// The side's slots come out of lanes (qx0, j) / (i, qy0) of the row with the bits of the neighbour's own lanes; the owner's store pair
-// adds them to its own contribution (position WGR + lane of the strip).
-constexpr int WGX = MIMSEM_WGX;     // gathered DoFs of a group (one 8-byte gather per lane and level); position WGX holds 0
-constexpr int WGS = 4;              // ghost sides of a group: rows of the wavefront
+// at the 4 points).  A "ghost side" = (neighbour element, which of its 4 sides); the kernel computes its 4 points on PACKED ghost lanes:
+// per level one DPP row of the x-normal sides (side = column, point = row) and one of the y-normal sides (point = column, side = row),
+// so that the along-side operations are the element's own.  Side block b = the side's index in the group's list.
+//   gh [g][32] lane of the x-normal row (qy*4 + qx = point*4 + side), then of the y-normal row (side*4 + point): {metric record of the
+//              neighbour's point (wave-group order), element*16 + point, its qy0 (x-normal: qx0) = 3 << 1 | the point has no side
+//              DoF << 2, position b*16 + point*4 of its quadruple in the gathered strip | its result position (b*4 + point; an idle
+//              lane: 16 + its lane of the row) << 8}
+//   gx [g][64] slot gathered into position b*16 + point*4 + t of the level's strip (one 8-byte gather per lane and level): t < 3 the
+//              point's cross-edge DoFs in the order the neighbour's fma chain reads them, t = 3 the point's DoF on the side
+// The side's slots come out of the ghost lanes with the bits of the neighbour's own lanes; the owner's store pair adds them to its own
+// contribution (position WGR + b*4 + point of the level's strip).
+constexpr int WGX = MIMSEM_WGX;     // gathered DoFs of a group: 16 per ghost side
+constexpr int WGS = 4;              // ghost sides of a group: 16-position blocks of the gathered strip
 struct WaveOwn {
     std::vector<int4> plan, gh; std::vector<int> gx;
-    int ndirect = 0, nsides = 0, maxsides = 0, maxgx = 0;
+    int ndirect = 0, nsides = 0, maxsides = 0, maxgx = 0, nfull = 0;      // nfull: groups with 4 ghost sides of both kinds
 };
 int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, const int* iy, const WavePlan& P, WaveOwn& W) {
     if (order != 3 || G != 4 || n1e != 12 || (n1 & 1) || P.ntiles || P.nbgroups) return MIMSEM_ERR_UNSUPPORTED;
@@ -530,35 +534,38 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
     }
     // ---- per group: ghost rows, gathered DoFs, store entries ----
     W.plan.assign((size_t)P.ngroups*64, int4{0, 0, 0, 0});
-    W.gh.assign((size_t)P.ngroups*64, int4{0, 0, 0, 0});
+    W.gh.assign((size_t)P.ngroups*32, int4{0, 0, 0, 0});
     W.gx.assign((size_t)P.ngroups*64, 0);
     std::vector<std::vector<int>> owned(P.ngroups);
     for (int p = 0; p < n1/2; p++) owned[owner[p]].push_back(p);
     for (int g = 0; g < P.ngroups; g++) {
         std::vector<int>& sides = gsides[g];
         std::sort(sides.begin(), sides.end());
-        std::vector<int> gslots;                                   // gathered DoFs (distinct slots)
-        auto gpos = [&](int s) -> unsigned {
-            for (size_t t = 0; t < gslots.size(); t++) if (gslots[t] == s) return (unsigned)t;
-            gslots.push_back(s); return (unsigned)(gslots.size() - 1);
-        };
         const int e0 = std::max(P.perm[(size_t)g*G], 0);
-        for (int l = 0; l < 64; l++)                               // idle rows: the group's first element, operands = the zero
-            W.gh[(size_t)g*64 + l] = int4{g*64 + l%lpe, e0*lpe + l%lpe, (int)(WGX | WGX << 8), 0};
+        const int lane0slot = P.lane[(size_t)g*64].y;
+        for (int l = 0; l < 32; l++)                               // idle lanes: points of the group's first element, results into a dump
+            W.gh[(size_t)g*32 + l] = int4{g*64 + l%lpe, e0*lpe + l%lpe, 0, (16 + l%lpe) << 8};
+        int nxs = 0, nys = 0;                                      // x-normal sides (columns of their row), y-normal ones (rows)
+        for (int l = 0; l < 64; l++) W.gx[(size_t)g*64 + l] = lane0slot;     // positions nobody reads re-read a pair of the group
         for (size_t si = 0; si < sides.size(); si++) {
             const int e = sides[si]/4, sd = sides[si]%4;
             const bool yn = sd >= 2; const int c0 = (sd & 1) ? 3 : 0;          // qx0 (x-normal) or qy0 (y-normal)
-            for (int q = 0; q < lpe; q++) {
-                const int qx = q%4, qy = q/4;
-                // X of the lane = x-edge DoF q (q < 12), Y = y-edge DoF qy*3 + qx (qx < 3): staged where a side point of the row reads them
-                const bool wx = q < n1e && (yn || qx == c0), wy = qx < 3 && (!yn || qy == c0);
-                const unsigned px = wx ? gpos(slot_of(e, q)) : (unsigned)WGX, py = wy ? gpos(slot_of(e, n1e + qy*3 + qx)) : (unsigned)WGX;
-                W.gh[(size_t)g*64 + si*lpe + q] = int4{grp[e]*64 + kin[e]*lpe + q, e*lpe + q, (int)(px | py << 8 | (unsigned)yn << 16), 0};
+            for (int pt = 0; pt < 4; pt++) {
+                const int q = yn ? c0*4 + pt : pt*4 + c0;                       // the neighbour's lane of the side point
+                const int l = yn ? 16 + nys*4 + pt : pt*4 + nxs;
+                W.gh[(size_t)g*32 + l] = int4{grp[e]*64 + kin[e]*lpe + q, e*lpe + q, (c0 == 3 ? 2 : 0) | (!yn && pt == 3 ? 4 : 0),
+                                              (int)(si*16 + pt*4) | (int)(si*4 + pt) << 8};
+                int* gxp = &W.gx[(size_t)g*64 + si*16 + pt*4];
+                for (int t = 0; t < 3; t++) {
+                    // x-normal: Y(t, pt) for t = 0, 1, 2 (dpp_quad order); y-normal: X(pt, row) in dpp_rows rotation order from row c0
+                    // (the row-3 zero dropped): rows 0, 2, 1 (c0 = 0) or 2, 1, 0 (c0 = 3)
+                    const int row = c0 == 0 ? (t == 0 ? 0 : 3 - t) : 2 - t;
+                    gxp[t] = yn ? slot_of(e, row*4 + pt) : slot_of(e, n1e + pt*3 + t);
+                }
+                if (pt < 3) gxp[3] = yn ? slot_of(e, n1e + c0*3 + pt) : slot_of(e, pt*4 + c0);
             }
+            (yn ? nys : nxs)++;
         }
-        if ((int)gslots.size() > WGX) return MIMSEM_ERR_UNSUPPORTED;
-        const int lane0slot = P.lane[(size_t)g*64].y;
-        for (int l = 0; l < 64; l++) W.gx[(size_t)g*64 + l] = l < (int)gslots.size() ? gslots[l] : lane0slot;     // idle lanes re-read a pair of the group
         // store entries of the owned pairs; a contribution from outside the group comes from a lane of its ghost row
         std::vector<int4> ent;
         auto contrib = [&](int s, int w) -> unsigned {
@@ -566,8 +573,8 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
             const int j = ownj[(size_t)s*2 + w];
             if (grp[e] == g) return (unsigned)(kin[e]*nd + j);
             const int si = (int)(std::find(sides.begin(), sides.end(), e*4 + side_of(j)) - sides.begin());
-            const int q = j < n1e ? j : ((j - n1e)/3)*4 + (j - n1e)%3;      // the lane of the row holding the DoF's result
-            return WGR + (unsigned)(si*lpe + q);
+            const int pt = j < n1e ? j/4 : (j - n1e)%3;      // the DoF's point along the side: its ghost lane holds the result
+            return WGR + (unsigned)(si*4 + pt);
         };
         for (int p : owned[g]) {
             ent.push_back(int4{2*p, (int)(contrib(2*p, 0) | contrib(2*p, 1) << 16), (int)(contrib(2*p + 1, 0) | contrib(2*p + 1, 1) << 16), 0});
@@ -577,7 +584,8 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
         if (ent.empty() || ent.size() > 64) return MIMSEM_ERR_UNSUPPORTED;
         for (int t = 0; t < 64; t++) W.plan[(size_t)g*64 + t] = ent[t%ent.size()];
         W.nsides += (int)sides.size(); W.maxsides = std::max(W.maxsides, (int)sides.size());
-        W.maxgx = std::max(W.maxgx, (int)gslots.size());
+        if (sides.size() == 4 && nxs > 0 && nys > 0) W.nfull++;
+        W.maxgx = std::max(W.maxgx, 16*(int)sides.size());
     }
     return MIMSEM_OK;
 }
@@ -803,8 +811,8 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
                         "in-kernel finishing %s; tiles %d (%d inner slots finished in LDS, widest LDS row %d doubles)\n", P.ngroups, 64/lpe, P.nbgroups, P.nps,
                 P.npwritten, P.nsides, c->n1, c->w_fin ? "on" : "off", P.ntiles, P.ninner, P.tpmax);
     if (getenv("MIMSEM_VERBOSE") && own)
-        fprintf(stderr, "[mimsem] owner-computes form: %d pairs, %d ghost sides (at most %d per group), at most %d gathered DoFs per group\n",
-                c->n1/2, W.nsides, W.maxsides, W.maxgx);
+        fprintf(stderr, "[mimsem] owner-computes form: %d pairs, %d ghost sides (at most %d per group; %d groups with 4 of both kinds), "
+                        "at most %d gathered DoFs per group\n", c->n1/2, W.nsides, W.maxsides, W.nfull, W.maxgx);
     return MIMSEM_OK;
 }
 

@@ -124,8 +124,8 @@ struct mimsem_ctx {
     // its one owner group, which computes the neighbour's contribution across its ghost sides -- one launch, no perimeter pass
     bool w_own = false;
     int4* d_woplan = nullptr;           // [w_ngroups][64] store pairs of the form (as d_wplan; every destination in y)
-    int4* d_wgh = nullptr;              // [w_ngroups][64] lanes of the ghost rows
-    int* d_wgx = nullptr;               // [w_ngroups][64] slot the lane gathers per level
+    int4* d_wgh = nullptr;              // [w_ngroups][16] packed ghost lanes (side*4 + point; round 9)
+    int* d_wgx = nullptr;               // [w_ngroups][64] slot the lane gathers per level (16 per ghost side)
     int4* d_wtfin = nullptr; int w_ntiles = 0, w_ninner = 0;      // tile mode (round 5): [w_ntiles][64] {slot, LDS position of part A, of part B, 0}
     int4* d_wplan = nullptr;            // [w_ngroups][64] store pair {dst, result positions of its first and second slot (2 x 16 bit, the
                                         //   strip's zero for a missing contributor), 0}: dst >= 0: y[dst], y[dst+1]; dst <= -2: partial sums
@@ -188,7 +188,8 @@ struct mimsem_ctx {
 
 // tile mode of the wave-level kernel (round 5): finishing entries per tile, doubles of a tile's LDS row, levels the LDS rows hold
 constexpr int MIMSEM_WTF = 64, MIMSEM_WTP = 64, MIMSEM_WTLEV = 32;
-// owner-computes form of the wave-level kernel (round 7): gathered ghost DoFs of a wave-group (one 8-byte gather per lane and level)
+// owner-computes form of the wave-level kernel (round 7): gathered ghost DoFs of a wave-group (one 8-byte gather per lane and level;
+// round 9: 16 per ghost side, a quadruple per side point)
 constexpr int MIMSEM_WGX = 64;
 
 // kernels (elem_kernels.hip / column_kernels.hip) ---------------------------------------------------
@@ -215,7 +216,7 @@ struct ElemArgs {
     const int4* wlane; const int4* wplan; const int2* wsing; const int* wnode; const double* wG; const double* wR; int wgroups; int wg0; int wdump; int wcpp;
     const int4* wfin; const int* wsslot; int* wcnt;      // finishing phase (null: the perimeter pass follows)
     const int4* wtfin; int wtile;                        // tile mode: finishing entries per tile (stride wtile), or null
-    const int4* wgh; const int* wgx;                     // owner-computes form: ghost row lanes, gathered slots (build_wave_own), or null
+    const int4* wgh; const int* wgx;                     // owner-computes form: packed ghost lanes, gathered slots (build_wave_own), or null
     int wfence;                      // finishing phase, experiment: partial sums in PLAIN memory, one agent-scope release fence per wavefront before its arrival
     double Etab[20];                 // edge-basis table E[mp1][n] by value (orders <= 4): SGPRs, no load in the kernel
     double Wq[5];                    // GLL weights by value (orders <= 4)

@@ -118,11 +118,19 @@ __device__ __forceinline__ double2 wload2(const void* p) { return *(const double
 // OUTER perimeter (half the partial sums, half the slots).  Round 1's workgroup-level form had a barrier per LEVEL (+27 % on the element
 // kernel); this one has a barrier per <= 32 levels.
 // OWN (round 7, a.wgh; build_wave_own): owner-computes.  Every store pair has one owner group, which also computes the contribution of
-// the neighbour element across each of its (<= 4) GHOST SIDES: a ghost side is a second, virtual element row of the wavefront -- the
-// neighbour's lanes, holding its DoFs on the side and across it (one 8-byte gather per lane and level) and zeros elsewhere -- that runs
-// the element's own DPP algebra with the neighbour's metric and thickInv.  At p = 3 a slot on a side depends on the side's 4 points
+// the neighbour element across each of its (<= 4) GHOST SIDES (round 7: a second, virtual element row of the wavefront per side, laid
+// out as the neighbour's lanes, running the element's whole DPP algebra per level; round 9: packed ghost lanes, below), with the
+// neighbour's DoFs (one 8-byte gather per lane and level), metric and thickInv.  At p = 3 a slot on a side depends on the side's 4 points
 // only, so the side's slots come out with the neighbour's bits; they join the group's sums in the strip.  Every pair is written
 // finished into y by its owner: no partial sums and no perimeter pass.
+// Round 9: PACKED ghost lanes.  A ghost lane is one (side, point along it, level): ONE ghost pass covers two levels, in four DPP rows
+// -- x-normal sides of level 0 | y-normal sides of level 0 | the same for level 1 -- (round 7 ran a whole 64-lane element row per side
+// and level, 16 of 64 lanes producing slots).  In an x-normal row the side is the column (qx) and the point along it the row (qy); in
+// a y-normal row the point is the column and the side the row: the point along the side then sits where the element's coefficients
+// of that point are (cu, cp in qy; Ex, pq in qx), and the along-side operations ARE the element's -- dpp_rows for x-normal sides,
+// dpp_quad for y-normal ones, the same rotations, broadcasts and fma order.  The plan gathers, per side point, its 3 cross-edge DoFs in
+// the order the neighbour's chain reads them and its DoF on the side: one 16-byte-aligned quadruple, two ds_read_b128.  The cross-side
+// interpolation is a local chain of the 3 cross DoFs.  Every slot comes out of the very fma sequence of the neighbour's own lanes.
 template <int N, int OP, int LCT, bool ACCUM, bool TILE = false, bool OWN = false>
 __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 : (OpTraits<OP>::cf == SN ? 4 : 3), 8))) void k_apply_wave(ElemArgs a) {
     using D = Dims<N>;
@@ -133,8 +141,8 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
     constexpr int RS = D::mp1 + (D::mp1 & 1);            // padded row of the y-edge DoFs: 16-byte aligned rows
     constexpr int XT = D::n1e + D::mp1*RS;               // staged DoFs of an element; XT of element 0 is the staging dump
     constexpr int SXE = XT + 2*(LPE - D::n1e) + ((XT + 2*(LPE - D::n1e)) & 1);       // (build_wave_plan uses the same numbers)
-    constexpr int WGR = NACC + 136;                      // owner-computes: the ghost results of the 64 lanes (build_wave_own uses the same number)
-    constexpr int SW = (EPW*SXE > WGR + (OWN ? 64 : 0)) ? EPW*SXE : WGR + (OWN ? 64 : 0);     // strip of one level: staged x, later its summed results
+    constexpr int WGR = NACC + 136;                      // owner-computes: the ghost results of a level, side*4 + point (build_wave_own uses the same number)
+    constexpr int SW = (EPW*SXE > WGR + (OWN ? 32 : 0)) ? EPW*SXE : WGR + (OWN ? 32 : 0);     // strip of one level: staged x, later its summed results
     constexpr int LB = LCT >= MIMSEM_WLB ? MIMSEM_WLB : (LCT >= 2 ? 2 : LCT);      // levels in lock-step
     static_assert(LCT%LB == 0, "whole batches");
     __shared__ double sE[NW][D::mp1*N];                  // edge-basis table, wave-private copy (written from SGPRs: no load, no barrier)
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
     __shared__ double s_t[TILE ? MIMSEM_WTLEV : 1][TILE ? MIMSEM_WTP : 2];      // tile mode: pairs of partial sums of the inner slots, per level of the work item
     static_assert(!OWN || (N == 3 && OP == MIMSEM_OP_UMAT && !TILE), "owner-computes: Umat at p = 3");
     constexpr int WGX = MIMSEM_WGX;
-    __shared__ double s_g[OWN ? NW : 1][OWN ? LB : 1][OWN ? WGX + 2 : 1];      // owner-computes: the gathered ghost DoFs of a level | a zero | pad
+    __shared__ __attribute__((aligned(16))) double s_g[OWN ? NW : 1][OWN ? LB : 1][OWN ? WGX : 1];      // owner-computes: the gathered ghost DoFs of a level (16 B quadruples)
 
 #ifdef MIMSEM_STAMPS
     const long long t_entry = (long long)__builtin_amdgcn_s_memtime();
@@ -170,16 +178,21 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
 #endif
     const int4 wl = a.wlane[(size_t)g*64 + lane];        // {element, load pair, its staging positions}
     const int4 wp = a.wplan[(size_t)g*64 + lane];        // {store pair destination, result positions}
-    // owner-computes: {metric record, element*16 + point, staged positions of the lane's X | Y << 8 | y-normal side << 16} of the lane in
-    // its ghost row, the slot it gathers
+    // owner-computes: the lane's packed ghost lane -- DPP row 2*gl + y-normal, level gl of a pass (LB = 1: rows 2, 3 repeat rows 0, 1)
+    // {metric record of the neighbour's point, its element*16 + point, qy0 (y-normal) or qx0 (x-normal) = 3 << 1 | no side DoF << 2,
+    // position of its quadruple in the gathered strip | of its result (WGR + ..) << 8} -- and the slot the lane gathers per level
+    constexpr int NGP = (LB + 1)/2;                      // ghost passes per batch (two levels each)
+    const bool gyn = ((lane >> 4) & 1) != 0;
+    const int gl = LB >= 2 ? (lane >> 5) : 0;
     int4 gh = {0, 0, 0, 0}; int gxs = 0;
-    double hgaa = 0.0, hgab = 0.0, hgbb = 0.0;
+    double2 h01 = {0.0, 0.0}, h23 = {0.0, 0.0};
     if constexpr (OWN) {
-        gh = a.wgh[(size_t)g*64 + lane]; gxs = a.wgx[(size_t)g*64 + lane];
+        gh = a.wgh[(size_t)g*32 + (lane & 31)]; gxs = a.wgx[(size_t)g*64 + lane];
         const double2* hp = (const double2*)(a.wG + (size_t)gh.x*4);
-        const double2 h01 = hp[0], h23 = hp[1];
-        hgaa = a.scale*h01.x; hgab = a.scale*h01.y; hgbb = a.scale*h23.x;
+        h01 = hp[0]; h23 = hp[1];
     }
+    const bool gsz = (gh.z & 4) != 0;
+    const int gc0 = (gh.z & 2) ? 3 : 0;
     const unsigned gxo = 8u*(unsigned)gxs, gqg = (unsigned)gh.y;
     // the metric is stored in wave-group order: its address needs no table, so it travels together with the tables
     double gaa = 0.0, gab = 0.0, gbb = 0.0, rdet = 0.0, rr = 0.0;
@@ -209,7 +222,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
     // issuing every level up front put the whole launch's loads in front of the texture addresser before anybody computed
     // (s_memtime stamps: 5.7k of a wave's 20k cycles went into ISSUING 16 loads) ----
     double2 px[LCT]; double pf0[T::cf != SN ? LCT : 1], pt0[LCT], pt1[OP == MIMSEM_OP_UTMAT ? LCT : 1];
-    double pg[OWN ? LCT : 1], ptg[OWN ? LCT : 1];        // owner-computes: the lane's gathered ghost DoF, thickInv of its ghost point
+    double pg[OWN ? LCT : 1], ptg[OWN ? (LCT/LB)*((LB + 1)/2) : 1];     // owner-computes: the lane's gathered ghost DoF; thickInv of its ghost lane (per pass)
     const size_t lstride = (size_t)a.nEl*D::mp12;
     // the loads run AHEAD batches in front of the computed one, circularly over the LCT levels of a chunk and on into the next chunk
     // of the work item (register r holds level lbeg + r of this chunk, or lbeg + LCT + r of the next once level r is consumed)
@@ -226,10 +239,19 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
                 const int L = a.lev0 + min(lev0_ + i, a.nlev - 1);   // (a level beyond the range reads a valid pair; nothing is stored for it)
                 const double2 tp = WLOAD(double2, (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps) + to);
                 pt0[r0 + i] = tp.x; pt0[r0 + i + 1] = tp.y;
-                if constexpr (OWN) {
-                    const double2 tq = WLOAD(double2, (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps) + 16u*gqg);
-                    ptg[r0 + i] = tq.x; ptg[r0 + i + 1] = tq.y;
+            }
+            if constexpr (OWN) {                             // ONE load per ghost pass: the ghost lane's level, from the pair table
+#pragma unroll
+                for (int t = 0; t < NGP; t++) {
+                    const int L = a.lev0 + min(lev0_ + 2*t, a.nlev - 1);
+                    ptg[(r0/LB)*NGP + t] = *(const double*)((const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps) + 16u*gqg + 8u*(unsigned)gl);
                 }
+            }
+        } else if constexpr (OWN) {                          // the ghost lane's level only
+#pragma unroll
+            for (int t = 0; t < NGP; t++) {
+                const int lev = min(lev0_ + 2*t + gl, a.nlev - 1);
+                ptg[(r0/LB)*NGP + t] = *(const double*)((const char*)(a.tI + (size_t)(a.lev0 + lev)*lstride) + 8u*gqg);
             }
         }
 #pragma unroll
@@ -242,10 +264,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
                 const char* tb = (const char*)(a.th + (size_t)(a.lev0 + lev)*lstride);
                 pt0[r] = *(const double*)(tb + 8u*gq); pt1[r] = *(const double*)(tb + 8*lstride + 8u*gq);
             } else if constexpr (!TPAIR) pt0[r] = *(const double*)((const char*)(a.tI + (size_t)(a.lev0 + lev)*lstride) + 8u*gq);
-            if constexpr (OWN) {
-                pg[r] = *(const double*)((const char*)(a.x + (size_t)lev*a.xs) + gxo);
-                if constexpr (!TPAIR) ptg[r] = *(const double*)((const char*)(a.tI + (size_t)(a.lev0 + lev)*lstride) + 8u*gqg);
-            }
+            if constexpr (OWN) pg[r] = *(const double*)((const char*)(a.x + (size_t)lev*a.xs) + gxo);
         }
     };
     constexpr int AHEAD = (LCT/LB > MIMSEM_WAHEAD) ? MIMSEM_WAHEAD : LCT/LB - 1;      // batches requested ahead of the computed one
@@ -283,6 +302,25 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
             pq[k] = qx < 3 ? a.alpha*sE[wv][k*N + qx] : 0.0;            // y_y(dof (qx, qy)) = sum_k E[k][qx] b(k, qy),  qx < 3
         }
     }
+    // owner-computes, per packed ghost lane: the element's own coefficients of its point serve the along-side terms (see the header); the
+    // cross chain over the lane's 3 gathered cross DoFs takes kc = E[c0][t], t the edge function of the operand, in the neighbour's
+    // order (x-normal: Y(t, point), dpp_quad; y-normal: X(point, t), dpp_rows rotation order from row c0, the zero row-3 term folded into
+    // the chain's start: +0 instead of the -0 that makes fma(k, x, -0) the plain product); gm0, gm1 = the metric pair of the side's
+    // slots, {gaa, gab} (ra, x-normal) or {gab, gbb} (rb, y-normal), times scale
+    double kc[3] = {0.0, 0.0, 0.0}, gm0 = 0.0, gm1 = 0.0;
+    const double* sgl = nullptr;                          // the ghost lane's quadruple {cross 0, cross 1, cross 2, side DoF}
+    double* sgr = nullptr;                                // where its result goes: WGR + side block*4 + point of its level's strip
+    if constexpr (OWN) {
+        const double hgaa = a.scale*h01.x, hgab = a.scale*h01.y, hgbb = a.scale*h23.x;
+        gm0 = gyn ? hgab : hgaa; gm1 = gyn ? hgbb : hgab;
+#pragma unroll
+        for (int t = 0; t < 3; t++) {
+            const int tt = !gyn ? t : (gc0 == 0 ? (t == 0 ? 0 : 3 - t) : 2 - t);
+            kc[t] = sE[wv][gc0*N + tt];
+        }
+        sgl = &s_g[wv][gl][gh.w & 0xFF];
+        sgr = &s_x[wv][gl][WGR + (gh.w >> 8)];
+    }
     const int xd00 = wl.z & 0xFFFF, xd01 = (wl.z >> 16) & 0xFFFF, xd10 = wl.w & 0xFFFF, xd11 = (wl.w >> 16) & 0xFFFF;
     const bool hasx = q < D::n1e;
     // result positions in the wave's strip: x-edge DoF q at lane q; y-edge DoF at lane q (LDS form) or, DPP form, DoF qy*3 + qx at
@@ -310,10 +348,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
     WSTAMP(3);                                           // level loads issued
     static_assert(ZERO >= EPW*SXE && ZERO < SW, "the zero entry lies beyond the staged x and the results: written once");
 #pragma unroll
-    for (int i = 0; i < LB; i++) {
-        s_x[wv][i][ZERO] = 0.0;                           // every lane, same value: the second operand of single-contributor sums
-        if constexpr (OWN) s_g[wv][i][WGX] = 0.0;         // X / Y of a ghost-row lane that no point of the side reads (as the element's zeros)
-    }
+    for (int i = 0; i < LB; i++) s_x[wv][i][ZERO] = 0.0;     // every lane, same value: the second operand of single-contributor sums
     gchar* const dumpp = (gchar*)(a.out + a.wdump + 2*lane);   // tail of the first partial-sum row
     gchar* const dumps = (gchar*)(a.out + a.wdump + lane);
     for (int cc = 0; cc < a.wcpp; cc++, lbeg += a.lch) {
@@ -332,7 +367,7 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
             if constexpr (OWN) s_g[wv][i][lane] = pg[b0 + i];
         }
         wave_fence();
-        double yxr[LB], yyr[LB], gyr[OWN ? LB : 1];
+        double yxr[LB], yyr[LB];
 #pragma unroll
         for (int i = 0; i < LB; i++) {
             const int l = b0 + i;
@@ -374,14 +409,21 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
             else { ra = fac*fma(gab, v, gaa*u); rb = fac*fma(gbb, v, gab*u); }      // explicit fma: identical bits in every instantiation
             if constexpr (DPP) { yxr[i] = dpp_rows(cp, ra); yyr[i] = dpp_quad<4>(pq, rb); }
             else { s_a[wv][i][el][q] = ra; s_b[wv][i][el][q] = rb; }
-            if constexpr (OWN) {                          // the ghost row: the same algebra on the neighbour's operands, metric and thickInv
-                const double GX = s_g[wv][i][gh.z & 0xFF], GY = s_g[wv][i][(gh.z >> 8) & 0xFF];
-                const double gu_ = dpp_rows(cu, GX), gv_ = dpp_quad<3>(Ex, GY);
-                const double gf = vert ? ptg[l] : 1.0;
-                const double gra = gf*fma(hgab, gv_, hgaa*gu_), grb = gf*fma(hgbb, gv_, hgab*gu_);
-                const double gyx = dpp_rows(cp, gra), gyy = dpp_quad<4>(pq, grb);
-                gyr[i] = (gh.z >> 16) ? gyy : gyx;         // the slots of a y-normal side are y-edge DoFs, of an x-normal one x-edge DoFs
-            }
+        }
+        double gyr[NGP];
+#pragma unroll
+        for (int t = 0; t < (OWN ? NGP : 0); t++) {       // the ghost passes: every side point of two levels at once
+            const double2 c01 = *(const double2*)(sgl + 2*t*WGX), c2s = *(const double2*)(sgl + 2*t*WGX + 2);
+            const double S = gsz ? 0.0 : c2s.y;           // (x-normal: the side's point 3 has no DoF; the neighbour's lane holds a zero)
+            double C = fma(kc[0], c01.x, gyn ? 0.0 : -0.0);   // across the side: the lane's own operands
+            C = fma(kc[1], c01.y, C);
+            C = fma(kc[2], c2s.x, C);
+            const double Ar = dpp_rows(cu, S), Aq = dpp_quad<3>(Ex, S);      // along the side: the element's interpolation
+            const double gu_ = gyn ? C : Ar, gv_ = gyn ? Aq : C;
+            const double gf = vert ? ptg[(b0/LB)*NGP + t] : 1.0;
+            const double gr = gf*fma(gm1, gv_, gm0*gu_);   // ra (x-normal) or rb (y-normal) of the neighbour's point
+            const double Pr = dpp_rows(cp, gr), Pq = dpp_quad<4>(pq, gr);    // ... and its projection
+            gyr[t] = gyn ? Pq : Pr;
         }
         wave_fence();                                     // (DPP form: every lane has read its DoFs: the strips may take the results)
 #pragma unroll
@@ -399,8 +441,9 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
             }
             double* sacc = s_x[wv][i];                    // the level's x is spent: its strip takes the results
             sacc[aci0] = yx; sacc[aci1] = yy;
-            if constexpr (OWN) sacc[WGR + lane] = gyr[i];  // the neighbour's contribution to the ghost slot of this lane
         }
+#pragma unroll
+        for (int t = 0; t < (OWN ? NGP : 0); t++) sgr[2*t*SW] = gyr[t];     // the neighbour's contribution to the side slot of this ghost lane
         wave_fence();
 #pragma unroll
         for (int i = 0; i < LB; i++) {
