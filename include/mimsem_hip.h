@@ -307,6 +307,38 @@ int mimsem_block_chebyshev_solve(mimsem_ctx* ctx, int op, int geom_lev0, int nle
                                  const double* b, long long b_stride, int nsteps, const double* coef,
                                  double* x, long long x_stride, double* pb, long long pb_stride, double* upd, long long upd_stride);
 
+/* The reference's PCBJACOBI itself: every mass solve runs GMRES + PCBJACOBI with PCBJacobiSetTotalBlocks(size*nElsX*nElsX) (ksp1,
+ * eul/HorizSolve.cpp:77-96; ksp, ksp0, ksp0h, src/SWEqn_Picard.cpp:85-113).  PETSc cuts the global numbering into equal contiguous chunks,
+ * and with the element-contiguous numbering chunk k is the set of slots element k OWNS: for 1-forms its 2 n^2 x-edges of columns 0..n-1 and
+ * y-edges of rows 0..n-1 (west and south sides and interior; east and north sides belong to the neighbours), for 2-forms its n^2 faces.  The
+ * sub-solve is ILU(0) of the chunk's diagonal block of the ASSEMBLED matrix; element blocks are inserted whole (eul/Assembly.cpp:128-131), the
+ * block's pattern is full and ILU(0) is its exact inverse.  Not the overlapping sum of mimsem_ksp_set_pc_bjacobi, which stays the default.
+ * Ownership is read off the element tables (where a slot sits in its element), not off the numbering; row r of block k is the r-th smallest
+ * slot element k owns (the chunk's order in the global numbering).  Slots that no element owns -- ghost slots of a rank-local numbering,
+ * compacted numberings of part of a mesh -- lie outside every block (a sphere's or periodic box's full vector has none).  0-forms:
+ * MIMSEM_ERR_UNSUPPORTED (M0 is diagonal; mimsem_ksp_set_pc_bjacobi's Jacobi is exact).  MIMSEM_ERR_ARG when two elements would own one slot.
+ * mimsem_owned_blocks_build: the ASSEMBLED owned blocks of operator op (1-forms: UMAT, UHMAT, UTMAT, UTMAT_H; 2-forms: WMAT, WHMAT) on geometry
+ *   levels [geom_lev0, geom_lev0 + nlev), arguments as mimsem_op_element_matrices (f: level rows f_stride doubles apart); out: device
+ *   [nlev][nEl][nd][nd] row-major, nd = 2 n^2 (1-forms) or n^2 (2-forms).  Block k sums, in a fixed order (owner first, then the neighbour that
+ *   shares a side), the entries of the element matrices whose two slots are both owned by k: two builds give the same bits.  Set-up call:
+ *   synchronises, not inside a stream capture (MIMSEM_ERR_STATE).  Invert with mimsem_block_inverse(ctx, nlev * nEl, nd, out): it takes every
+ *   order (nd <= 98 at order 7).
+ * mimsem_owned_blocks_apply: y[block k's slots] = B_k x[block k's slots] for every block and nlev rows in ONE launch, blocks (the inverses) as
+ *   built, blocks_level_stride doubles apart per level (0: one set for all levels, read once per chunk of levels).  Every owned slot of y is
+ *   written exactly once, slots outside every block are NOT touched; no gather plan, no partial sums.  x != y.
+ * mimsem_owned_block_chebyshev_solve: mimsem_block_chebyshev_solve with this preconditioner -- a fixed-length Chebyshev solve of Umat x = b from
+ *   x = 0; each step is the element pass plus ONE owned-block pass that gathers b - A x at the block's slots, applies B_k and writes z, p and x
+ *   directly (two launches per step, the first step has no element pass).  coef, pb, upd, flags and the order limit (<= 5) as that entry;
+ *   MIMSEM_ERR_UNSUPPORTED when some 1-form slot lies outside every block.  Capturable once the context's workspaces have the size.          */
+int mimsem_owned_blocks_build(mimsem_ctx* ctx, int op, int geom_lev0, int nlev, double scale, unsigned flags,
+                              const double* f, long long f_stride, double* out);
+int mimsem_owned_blocks_apply(mimsem_ctx* ctx, int form, int nlev, const double* blocks, long long blocks_level_stride,
+                              const double* x, long long x_stride, double* y, long long y_stride);
+int mimsem_owned_block_chebyshev_solve(mimsem_ctx* ctx, int op, int geom_lev0, int nlev, double scale, unsigned flags,
+                                       const double* blocks, long long blocks_level_stride, const double* b, long long b_stride,
+                                       int nsteps, const double* coef, double* x, long long x_stride,
+                                       double* pb, long long pb_stride, double* upd, long long upd_stride);
+
 /* z = P (A x) for the left-preconditioned Krylov iteration on the shallow-water operator: mimsem_sw_operator_apply followed by
  * mimsem_sw_blocks_apply in three launches instead of four -- the block pass reads the operator's element-local results through
  * the gather plan, the assembled A x is never written. */
@@ -595,6 +627,12 @@ int  mimsem_ksp_set_pc_jacobi(mimsem_ksp* ksp, const double* dinv, long long din
  * level geom_lev0 without its thickness factor, D_e = 1 / (number of elements sharing the edge), times 1 / mean(thickInv) of the
  * element per level when the operator carries the thickness flag (exact where a layer's thickness is uniform over an element).     */
 int  mimsem_ksp_set_pc_bjacobi(mimsem_ksp* ksp);
+/* The reference's PCBJACOBI (PCBJacobiSetTotalBlocks(size*nElsX*nElsX), eul/HorizSolve.cpp:77-96, src/SWEqn_Picard.cpp:85-113): PCSetUp builds
+ * the exact inverses of the assembled owned blocks (mimsem_owned_blocks_build + mimsem_block_inverse) of the operator of mimsem_ksp_set_operator,
+ * one set per level of the operator (one for all levels when the operator has neither the thickness flag nor a field), and applies them with
+ * mimsem_owned_blocks_apply; CG and GMRES.  MIMSEM_ERR_STATE without such an operator or while capturing, MIMSEM_ERR_UNSUPPORTED for 0-forms,
+ * for other operators and when some slot lies outside every block.                                                                    */
+int  mimsem_ksp_set_pc_bjacobi_owned(mimsem_ksp* ksp);
 /* caller-built element blocks, as mimsem_elem_blocks_apply takes them (form 0 / 1 / 2; elem_scale may be NULL)                      */
 int  mimsem_ksp_set_pc_elem_blocks(mimsem_ksp* ksp, int form, const double* blocks, const double* elem_scale, long long elem_scale_stride);
 /* coupled [u|h] element blocks of mimsem_sw_blocks_apply (with the shallow-water operator: the fused z = P A x of

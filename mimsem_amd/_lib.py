@@ -71,6 +71,10 @@ _SIGS = {
                                                c_dp, c_ll, C.c_double, C.c_double, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),
     "mimsem_block_chebyshev_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, c_dp, c_ll, c_dp, c_dp, c_ll,
                                                c_dp, c_ll, C.c_int, C.POINTER(C.c_double), c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),
+    "mimsem_owned_blocks_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, c_dp, c_ll, c_dp]),
+    "mimsem_owned_blocks_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),
+    "mimsem_owned_block_chebyshev_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, c_dp, c_ll, c_dp, c_ll,
+                                                     C.c_int, C.POINTER(C.c_double), c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),
     "mimsem_sw_operator_precond_chebyshev": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, c_dp, c_ll, c_dp, C.c_double, C.c_double,
                                              c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),
     "mimsem_sw_chebyshev_step2": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, c_dp, c_ll, c_dp, C.c_int, C.c_double, C.c_double, C.c_double,
@@ -89,6 +93,7 @@ _SIGS = {
     "mimsem_ksp_set_pc_none": (C.c_int, [C.c_void_p]),
     "mimsem_ksp_set_pc_jacobi": (C.c_int, [C.c_void_p, c_dp, c_ll]),
     "mimsem_ksp_set_pc_bjacobi": (C.c_int, [C.c_void_p]),
+    "mimsem_ksp_set_pc_bjacobi_owned": (C.c_int, [C.c_void_p]),
     "mimsem_ksp_set_pc_elem_blocks": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_ll]),
     "mimsem_ksp_set_pc_sw_blocks": (C.c_int, [C.c_void_p, c_dp]),
     "mimsem_ksp_set_pc_sw_bjacobi": (C.c_int, [C.c_void_p]),

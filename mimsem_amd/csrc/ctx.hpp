@@ -139,6 +139,8 @@ struct mimsem_ctx {
     // workspace
     double* d_ye = nullptr;     // [nk_ws][nEl][max(2*n1e, n0e)] element-local results
     long long ye_doubles = 0;
+    // owned-block preconditioner (owned_blocks.hip): per form 1 / 2, [nEl][rows] {slot, owner position, other position, 0}, built on first use
+    int4* d_own[3] = {nullptr, nullptr, nullptr}; int own_uncovered[3] = {0, 0, 0};      // slots of the form that no element owns
     double* d_cheb = nullptr; long long cheb_doubles = 0;      // mimsem_block_chebyshev_solve: the second iterate and two direction vectors, [3][nlev][n1]
     int ensure_cheb(long long doubles);
     int *d_d0 = nullptr, *d_d1x = nullptr, *d_d1y = nullptr;   // direct-write slots (single-contributor DoFs), see ElemArgs

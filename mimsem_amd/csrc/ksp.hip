@@ -22,9 +22,11 @@
 
 #define KTRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
+int mimsem_owned_covers_all(mimsem_ctx* c, int form);      // owned_blocks.hip
+
 namespace {
 enum { A_NONE = 0, A_OP = 1, A_SW = 2, A_SHELL = 3 };
-enum { P_NONE = 0, P_JACOBI = 1, P_BLOCKS = 2, P_SW = 3, P_SHELL = 4 };
+enum { P_NONE = 0, P_JACOBI = 1, P_BLOCKS = 2, P_SW = 3, P_SHELL = 4, P_OWNED = 5 };
 
 // B'[e][i][j] = d[e][i] B[e][i][j] d[e][j]
 __global__ __launch_bounds__(256) void k_scale_blocks(long long total, int nd, const double* __restrict__ d, double* __restrict__ B) {
@@ -113,6 +115,7 @@ struct mimsem_ksp {
     int pkind = P_NONE; const double* dinv = nullptr; long long dinvs = 0;
     int bform = 1; bool btrans = false; const double* blocks = nullptr; const double* escale = nullptr; long long escales = 0;
     double* own_blocks = nullptr; double* own_escale = nullptr; double* own_dinv = nullptr;
+    long long own_bls = 0;                                   // P_OWNED: doubles between the block sets of two levels (0: one set)
     mimsem_ksp_apply_fn pfn = nullptr; void* puser = nullptr;
     // controls
     double rtol = 1.0e-16, atol = 1.0e-50; int maxit = 1000, restart = 30, check_every = 2; bool guess_nonzero = false;
@@ -157,6 +160,7 @@ struct mimsem_ksp {
         case P_BLOCKS: return mimsem_elem_blocks_apply(c, bform, nlev, btrans ? MIMSEM_FLAG_TRANSPOSE : 0u, blocks, 0, escale, escales, r, rs, z, zs, 1.0);
         case P_SW: return mimsem_sw_blocks_apply(c, nlev, blocks, r, rs, z, zs);
         case P_SHELL: return pfn(puser, nlev, r, rs, z, zs);
+        case P_OWNED: return mimsem_owned_blocks_apply(c, bform, nlev, blocks, own_bls, r, rs, z, zs);
         }
         return MIMSEM_ERR_STATE;
     }
@@ -486,6 +490,34 @@ int mimsem_ksp_set_pc_bjacobi(mimsem_ksp* k) {
     k->pkind = P_BLOCKS; k->bform = form; k->btrans = form == 1; k->blocks = k->own_blocks; k->escale = k->own_escale; k->escales = nEl;
     return MIMSEM_OK;
 }
+// the reference's PCBJACOBI (eul/HorizSolve.cpp:77-96, src/SWEqn_Picard.cpp:85-113): exact inverses of the assembled owned blocks
+// (owned_blocks.hip), one set per level of the operator -- or one for all levels when nothing in the operator depends on the level
+int mimsem_ksp_set_pc_bjacobi_owned(mimsem_ksp* k) {
+    if (!k || k->akind != A_OP || k->form < 0 || k->form > 2) return MIMSEM_ERR_STATE;
+    mimsem_ctx* c = k->c;
+    if (c->is_capturing()) return MIMSEM_ERR_STATE;
+    const int form = k->form;
+    if (form == 0) return MIMSEM_ERR_UNSUPPORTED;
+    if (k->op != MIMSEM_OP_UMAT && k->op != MIMSEM_OP_UHMAT && k->op != MIMSEM_OP_UTMAT && k->op != MIMSEM_OP_UTMAT_H &&
+        k->op != MIMSEM_OP_WMAT && k->op != MIMSEM_OP_WHMAT) return MIMSEM_ERR_UNSUPPORTED;
+    if ((k->flags & 1u) && (!c->have_levels || !c->d_tI)) return MIMSEM_ERR_STATE;
+    if (!mimsem_owned_covers_all(c, form)) return MIMSEM_ERR_UNSUPPORTED;       // (a slot outside every block: P would leave z undefined there)
+    const int nd = form == 1 ? 2*c->es.n*c->es.n : c->es.n2e;
+    const bool shared = !(k->flags & 1u) && !k->f && k->op != MIMSEM_OP_UTMAT && k->op != MIMSEM_OP_UTMAT_H;
+    const int nsets = shared ? 1 : k->nlev;
+    const long long per = (long long)c->nEl*nd*nd;
+    double* blocks = nullptr;
+    if (hipMalloc((void**)&blocks, (size_t)std::max(1LL, per*nsets)*8) != hipSuccess) return MIMSEM_ERR_HIP;
+    int rc = mimsem_owned_blocks_build(c, k->op, k->lev0, nsets, k->scale, k->flags & 1u, k->f, k->fs, blocks);
+    if (!rc) rc = mimsem_block_inverse(c, (long long)nsets*c->nEl, nd, blocks);
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = MIMSEM_ERR_HIP;
+    if (rc) { (void)hipFree(blocks); return rc; }                              // the handle keeps the preconditioner it had
+    if (k->own_blocks) (void)hipFree(k->own_blocks);
+    if (k->own_escale) (void)hipFree(k->own_escale);
+    k->own_blocks = blocks; k->own_escale = nullptr;
+    k->pkind = P_OWNED; k->bform = form; k->blocks = blocks; k->escale = nullptr; k->own_bls = shared ? 0 : per;
+    return MIMSEM_OK;
+}
 // the coupled [u|h] element blocks of the shallow-water operator, built from the operator given to mimsem_ksp_set_operator_sw
 int mimsem_ksp_set_pc_sw_bjacobi(mimsem_ksp* k) {
     if (!k || k->akind != A_SW) return MIMSEM_ERR_STATE;
@@ -534,7 +566,7 @@ int mimsem_ksp_solve(mimsem_ksp* k, const double* b, long long bs, double* x, lo
     if (k->nlev == 1) { bs = std::max(bs, k->n); xs = std::max(xs, k->n); }        // one row: any stride will do (a reference-style single-level solve)
     if (bs < k->n || xs < k->n) return MIMSEM_ERR_ARG;
     if (k->pkind == P_SW && k->akind != A_SW && k->n != (long long)k->c->n1 + k->c->n2) return MIMSEM_ERR_ARG;
-    if (k->pkind == P_BLOCKS) {
+    if (k->pkind == P_BLOCKS || k->pkind == P_OWNED) {
         const long long want = k->bform == 0 ? k->c->n0 : (k->bform == 1 ? k->c->n1 : k->c->n2);
         if (want != k->n) return MIMSEM_ERR_ARG;
     }

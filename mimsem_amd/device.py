@@ -317,6 +317,68 @@ class Engine:
                                                   _ptr(upd), upd.stride(0) if upd is not None else 0), "block_chebyshev_solve(%s)" % op)
         return x
 
+    _OWNED_FORM = {"UMAT": 1, "UHMAT": 1, "UTMAT": 1, "UTMAT_H": 1, "WMAT": 2, "WHMAT": 2}
+
+    def owned_rows(self, form):
+        """rows of an owned block (mimsem_owned_blocks_*): the 2 n^2 edges (1-forms) or n^2 faces (2-forms) an element owns"""
+        return {1: 2 * self.mesh.n * self.mesh.n, 2: self.n2e}[form]
+
+    def owned_covers_all(self, form=1):
+        """True when every slot of the form lies in an owned block (the rule of mimsem_owned_blocks_*: an element owns its x-edges of columns
+        0..n-1 and y-edges of rows 0..n-1; 2-forms: its faces).  Spheres and periodic boxes as a whole: True; a rank-local layout's ghosts: False."""
+        dm, n = self.mesh, self.mesh.n
+        if form == 2:
+            return np.unique(dm.inds2).size == self.sizes[2]
+        l = np.arange(n * (n + 1))
+        own = np.concatenate([np.asarray(dm.inds1x)[:, l % (n + 1) < n], np.asarray(dm.inds1y)[:, l // n < n]], axis=1)
+        return np.unique(own).size == self.sizes[1]
+
+    def owned_blocks(self, op, f=None, lev0=0, nlev=1, scale=1.0, flags=0, invert=False):
+        """the reference's PCBJACOBI blocks (PCBJacobiSetTotalBlocks(size*nElsX*nElsX)): the ASSEMBLED diagonal block of the slots each element
+        owns, [nlev, nEl, nd, nd] row-major for geometry levels lev0.. (mimsem_owned_blocks_build; f: [nlev, n_field] rows); invert: their exact
+        inverses (mimsem_block_inverse), what owned_blocks_apply and owned_block_chebyshev_solve take"""
+        form = self._OWNED_FORM[op]
+        nd = self.owned_rows(form)
+        _need(f is None or (f.dim() == 2 and f.shape[0] == nlev), "owned_blocks: f must be [nlev, n] rows")
+        out = torch.empty(nlev, self.nEl, nd, nd, dtype=torch.float64, device=self.device)
+        check(self.L.mimsem_owned_blocks_build(self.ctx, OPS[op], lev0, nlev, scale, flags, _ptr(f), f.stride(0) if f is not None else 0, _ptr(out)),
+              "mimsem_owned_blocks_build(%s)" % op)
+        if invert:
+            check(self.L.mimsem_block_inverse(self.ctx, nlev * self.nEl, nd, out.data_ptr()), "block_inverse")
+        return out
+
+    def owned_blocks_apply(self, form, blocks, x, out=None):
+        """y[slots of block k] = B_k x[slots of block k] for every owned block and every row of x (mimsem_owned_blocks_apply, one launch); blocks
+        [nEl, nd, nd] (one set for all rows) or [nlev, nEl, nd, nd].  Slots outside every block keep what `out` held (zeros when not given)."""
+        x2 = x if x.dim() == 2 else x.unsqueeze(0)
+        nlev, nd = x2.shape[0], self.owned_rows(form)
+        _need(x2.shape[1] == self.sizes[form] and x2.stride(1) == 1, "owned_blocks_apply: x rows of the form's length")
+        _need(blocks.is_contiguous() and blocks.shape[-3:] == (self.nEl, nd, nd) and (blocks.dim() == 3 or (blocks.dim() == 4 and blocks.shape[0] == nlev)),
+              "owned_blocks_apply: blocks [nEl, nd, nd] or [nlev, nEl, nd, nd]")
+        y = out if out is not None else torch.zeros(nlev, self.sizes[form], dtype=torch.float64, device=self.device)
+        y2 = y if y.dim() == 2 else y.unsqueeze(0)
+        _need(y2.shape == x2.shape and y2.stride(1) == 1, "owned_blocks_apply: out like x")
+        check(self.L.mimsem_owned_blocks_apply(self.ctx, form, nlev, _ptr(blocks), blocks.stride(0) if blocks.dim() == 4 else 0,
+                                               _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0)), "mimsem_owned_blocks_apply")
+        return y if x.dim() == 2 else y2[0]
+
+    def owned_block_chebyshev_solve(self, blocks, b, coef, x=None, lev0=0, scale=1.0, flags=0, pb=None, upd=None):
+        """block_chebyshev_solve with the owned-block preconditioner (mimsem_owned_block_chebyshev_solve): len(coef) steps of {element pass,
+        owned-block pass} from x = 0 on Umat; blocks: the inverses, [nEl, nd, nd] or [nlev, nEl, nd, nd]"""
+        nd = self.owned_rows(1)
+        _need(b.dim() == 2 and b.shape[1] == self.sizes[1] and b.stride(1) == 1, "owned_block_chebyshev_solve: b [nlev, n1]")
+        _need(blocks.is_contiguous() and blocks.shape[-3:] == (self.nEl, nd, nd) and (blocks.dim() == 3 or (blocks.dim() == 4 and blocks.shape[0] == b.shape[0])),
+              "owned_block_chebyshev_solve: blocks [nEl, nd, nd] or [nlev, nEl, nd, nd]")
+        x = torch.empty_like(b) if x is None else x
+        for t in (x, pb, upd):
+            _need(t is None or (t.shape == b.shape and t.stride(1) == 1), "owned_block_chebyshev_solve: x / pb / upd like b")
+        flat = (C.c_double * (2 * len(coef)))(*[v for ab in coef for v in ab])
+        check(self.L.mimsem_owned_block_chebyshev_solve(self.ctx, OPS["UMAT"], lev0, b.shape[0], scale, flags, _ptr(blocks),
+                                                        blocks.stride(0) if blocks.dim() == 4 else 0, _ptr(b), b.stride(0), len(coef), flat,
+                                                        _ptr(x), x.stride(0), _ptr(pb), pb.stride(0) if pb is not None else 0,
+                                                        _ptr(upd), upd.stride(0) if upd is not None else 0), "owned_block_chebyshev_solve")
+        return x
+
     def sw_dual_chebyshev(self, coefA, blocks, b1, p1, x1, upd1, coefB, tau, h, u, b0, dinv, p0, x0, upd0, pb1=None, pb0=None):
         """the 1-form mass solve (len(coefA) block-Chebyshev steps on Umat) and the upwinded lumped 0-form mass solve (len(coefB) Chebyshev steps
         on Phmat_up) of one shallow-water Picard iteration, both from x = 0, in SHARED launches (mimsem_sw_dual_chebyshev): the same bits as the

@@ -347,6 +347,10 @@ public:
         pc_dirty = true;
     }
     void setPCBJacobi() { pc = PC_BJACOBI; pc_dirty = true; }    // PCSetType(pc, PCBJACOBI) + PCBJacobiSetTotalBlocks(one block per element)
+    // the reference's own PCBJACOBI + PCBJacobiSetTotalBlocks(pc, size*nElsX*nElsX, NULL) (eul/HorizSolve.cpp:82-85): exact inverses of the
+    // assembled diagonal blocks of the slots each element owns (mimsem_ksp_set_pc_bjacobi_owned) -- the reference's preconditioned operator
+    // and residual history; setPCBJacobi's overlapping element blocks stay the default of the hosts
+    void setPCBJacobiOwned() { pc = PC_BJACOBI_OWNED; pc_dirty = true; }
     void setPCNone() { pc = PC_NONE; pc_dirty = true; }
     void setPCJacobi(const double* dinv) { pc = PC_JACOBI; pc_dinv = dinv; pc_dirty = true; }     // PCJACOBI with the caller's inverse diagonal (device)
     void setPCShell(mimsem_ksp_apply_fn fn, void* user) { pc = PC_SHELL; pc_fn = fn; pc_user = user; pc_dirty = true; }
@@ -373,7 +377,7 @@ public:
 private:
     static void fail(const char* m) { throw std::runtime_error(m); }
     enum AKind { A_NONE, A_OP, A_SW, A_SHELL };
-    enum PKind { PC_NONE, PC_BJACOBI, PC_SHELL, PC_JACOBI };
+    enum PKind { PC_NONE, PC_BJACOBI, PC_SHELL, PC_JACOBI, PC_BJACOBI_OWNED };
     void attach_operator() {
         switch (akind) {
         case A_OP: check(mimsem_ksp_set_operator(h, a_op, a_lev, 1, a_scale, a_flags, a_field, 0), "mimsem_ksp_set_operator"); break;
@@ -386,6 +390,8 @@ private:
         if (pc == PC_SHELL) check(mimsem_ksp_set_pc_shell(h, pc_fn, pc_user), "mimsem_ksp_set_pc_shell");
         else if (pc == PC_JACOBI) check(mimsem_ksp_set_pc_jacobi(h, pc_dinv, 0), "mimsem_ksp_set_pc_jacobi");
         else if (pc == PC_BJACOBI && akind == A_OP) check(mimsem_ksp_set_pc_bjacobi(h), "mimsem_ksp_set_pc_bjacobi");      // 0-, 1- and 2-form operators
+        else if (pc == PC_BJACOBI_OWNED && akind == A_OP) check(mimsem_ksp_set_pc_bjacobi_owned(h), "mimsem_ksp_set_pc_bjacobi_owned");   // 1- and 2-forms
+        else if (pc == PC_BJACOBI_OWNED) fail("KSP: the owned-block PCBJACOBI needs an engine operator (setOperators)");
         else if (pc == PC_BJACOBI && akind == A_SW) {
             if (sw_blocks) check(mimsem_ksp_set_pc_sw_blocks(h, sw_blocks), "mimsem_ksp_set_pc_sw_blocks");
             else check(mimsem_ksp_set_pc_sw_bjacobi(h), "mimsem_ksp_set_pc_sw_bjacobi");

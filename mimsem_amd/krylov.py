@@ -61,6 +61,8 @@ class KSP:
             self._check(L.mimsem_ksp_set_pc_none(h), "ksp_set_pc_none")
         elif kind == "bjacobi":
             self._check(L.mimsem_ksp_set_pc_bjacobi(h), "ksp_set_pc_bjacobi")
+        elif kind == "bjacobi_owned":      # the reference's PCBJACOBI: exact inverses of the assembled owned blocks (mimsem_ksp_set_pc_bjacobi_owned)
+            self._check(L.mimsem_ksp_set_pc_bjacobi_owned(h), "ksp_set_pc_bjacobi_owned")
         elif kind == "jacobi":
             self._check(L.mimsem_ksp_set_pc_jacobi(h, _ptr(dinv), dinv.stride(0) if dinv.dim() > 1 else 0), "ksp_set_pc_jacobi")
         elif kind == "elem_blocks":
@@ -218,7 +220,9 @@ class MassSolver:
     """M1 u = b on all levels (the ksp1 solves, eul/HorizSolve.cpp:77-96: GMRES + PCBJACOBI with one block per element).
     Preconditioner: element blocks P^-1 = sum_e R_e^T D_e (M1_e)^-1 D_e R_e (D_e = 1/multiplicity of the edge), applied by
     mimsem_elem_blocks_apply -- cond(P^-1 M1) ~ 1.2; built once per thickness field, reused over time steps.
-    precond="jacobi" keeps the diagonal scaling (cond ~ 3)."""
+    precond="jacobi" keeps the diagonal scaling (cond ~ 3).  precond="owned": the reference's own PCBJACOBI -- exact inverses of the
+    assembled diagonal blocks of the edges each element owns, one set per level (mimsem_owned_blocks_build), cond ~ 2; its Chebyshev solve is
+    mimsem_owned_block_chebyshev_solve (two launches per step).  One context only; opt-in, the default stays "blocks"."""
 
     def __init__(self, eng, scale=1.0e8, vert_scale=True, precond="blocks"):
         self.eng, self.scale, self.flags = eng, scale, 1 if vert_scale else 0
@@ -248,6 +252,14 @@ class MassSolver:
                 diag[k].index_add_(0, ix.reshape(-1), torch.diagonal(em[:, 0], dim1=1, dim2=2).reshape(-1))
                 diag[k].index_add_(0, iy.reshape(-1), torch.diagonal(em[:, 3], dim1=1, dim2=2).reshape(-1))
             self.minv = 1.0 / diag
+        elif precond == "owned":
+            if self.dist:
+                raise ValueError("MassSolver(precond='owned') needs a single context (the owned blocks are not sharded)")
+            if not eng.owned_covers_all(1):
+                raise ValueError("MassSolver(precond='owned'): some 1-form slots lie outside every owned block (a rank-local layout)")
+            # one set of inverse blocks per level when the thickness enters the operator, else one set for every level
+            ob = eng.owned_blocks("UMAT", lev0=0, nlev=eng.nk if vert_scale else 1, scale=scale, flags=self.flags, invert=True)
+            self.blocks_owned = ob if vert_scale else ob[0]
         else:
             idx = torch.cat([ix, iy], dim=1)
             mult = torch.zeros(1, dm.n1, dtype=torch.float64, device=eng.device)
@@ -264,7 +276,13 @@ class MassSolver:
                 torch.ones(eng.nk, eng.nEl, dtype=torch.float64, device=eng.device)
             self.escale = (1.0 / tau).contiguous()
 
+    def _owned(self, lev0, nlev):
+        B = self.blocks_owned
+        return B if B.dim() == 3 else B[lev0:lev0 + nlev]
+
     def precond(self, r, lev0=0):
+        if self.kind == "owned":
+            return self.eng.owned_blocks_apply(1, self._owned(lev0, r.shape[0]), r)
         return self.eng.blocks_apply(1, self.blocks, r, transpose=True, elem_scale=self.escale[lev0:lev0 + r.shape[0]])
 
     def _blocks_t(self):
@@ -300,7 +318,8 @@ class MassSolver:
                 mg = tuple(float(v) for v in experiment("MIMSEM_CHEB_MARGIN", "").split(","))
             self.margin = mg
             self._cheb = ChebyshevMass(eng, None, lmin, lmax, rtol=1e-15, margin=mg)
-            self._blocks_cm = self.blocks.transpose(1, 2).contiguous()
+            if self.kind != "owned":
+                self._blocks_cm = self.blocks.transpose(1, 2).contiguous()
         return self._cheb
 
     def _logged_solve(self, ch, b):
@@ -349,12 +368,19 @@ class MassSolver:
         nlev = b.shape[0]
         if self.kind != "jacobi" and self.chebyshev:
             ch = self._chebyshev()
-            es = self.escale[lev0:lev0 + nlev]
-            ch.sweep = lambda x, rhs, p, al, be, upd: self.eng.block_chebyshev_sweep(
-                "UMAT", self._blocks_cm, x, rhs, p, al, be, elem_scale=es, lev0=lev0, scale=self.scale, flags=self.flags, upd=upd)
-            # one context: the whole solve as one call (round 6: no operator pass for the first step, no cleared vectors; MIMSEM_CHEB_WHOLE=0, experiments: a call per sweep)
-            ch.whole = None
-            if not self.dist and hasattr(self.eng, "block_chebyshev_solve") and self.eng.n1e <= 30 and experiment("MIMSEM_CHEB_WHOLE", "1") != "0":
+            if self.kind == "owned":
+                # the owned-block solve exists as a whole solve only: {element pass, owned-block pass} per step, from x = 0
+                ob = self._owned(lev0, nlev)
+                ch.sweep = None
+                ch.whole = lambda rhs, coef, pb, upd: self.eng.owned_block_chebyshev_solve(
+                    ob, rhs, coef, lev0=lev0, scale=self.scale, flags=self.flags, pb=pb, upd=upd)
+            else:
+                es = self.escale[lev0:lev0 + nlev]
+                ch.sweep = lambda x, rhs, p, al, be, upd: self.eng.block_chebyshev_sweep(
+                    "UMAT", self._blocks_cm, x, rhs, p, al, be, elem_scale=es, lev0=lev0, scale=self.scale, flags=self.flags, upd=upd)
+                # one context: the whole solve as one call (round 6: no operator pass for the first step, no cleared vectors; MIMSEM_CHEB_WHOLE=0, experiments: a call per sweep)
+                ch.whole = None
+            if self.kind != "owned" and not self.dist and hasattr(self.eng, "block_chebyshev_solve") and self.eng.n1e <= 30 and experiment("MIMSEM_CHEB_WHOLE", "1") != "0":
                 ch.whole = lambda rhs, coef, pb, upd: self.eng.block_chebyshev_solve(
                     "UMAT", self._blocks_cm, rhs, coef, elem_scale=es, lev0=lev0, scale=self.scale, flags=self.flags, pb=pb, upd=upd)
             # the calibrated step count holds for the tolerance and the level range it was calibrated on (advisor, round 3): a call that asks
@@ -400,6 +426,8 @@ class MassSolver:
                     self._cheb_cal = {"rtol": rtol, "lev0": lev0, "nlev": nlev, "bound_steps": full}
                     x = self._logged_solve(ch, b)
             return x, ch.steps
+        if self.kind == "owned":
+            return pcg(lambda v: self.apply(v, lev0), b, precond=lambda r: self.precond(r, lev0), rtol=rtol, maxit=maxit, check_every=2)
         if self.kind != "jacobi":
             if not hasattr(self.eng, "halo") and not self.fixed_its and os.environ.get("MIMSEM_PCG", "c") == "c":
                 # the batched PCG loop of the C ABI (mimsem_ksp_*, csrc/ksp.hip) with this object's blocks: what a C++ host runs
