@@ -373,6 +373,23 @@ int mimsem_sw_operator_precond_apply(mimsem_ctx* ctx, int nlev, double a, double
 int mimsem_sw_operator_precond_orthogonalize(mimsem_ctx* ctx, double a, double grav, double H, const double* f0, const double* blocks,
                                              const double* x, double* w, int k, const double* V, long long ldv, double alpha, double* h);
 
+/* ---- thermal shallow water: the element-local 2-form half of an SSP-RK3 stage (src/ThermalSW_EEC_2.cpp, DO_THERMAL) ------------------
+ * One context with nk == 1 (the shallow-water stack, src flavour: scale 1, flags 0) at element orders 2..5; other orders
+ * MIMSEM_ERR_UNSUPPORTED, nk != 1 or a null pointer MIMSEM_ERR_ARG.  Vectors are single level rows of the context's numbering; m2inv is
+ * the [nEl][n^2][n^2] output of mimsem_op_element_matrices(WMATINV) (M2_e^-1).  One launch each, no atomics: every output is a 2-form DoF
+ * that one element owns; outputs must not alias inputs (h_j / S_j of the update are read and rewritten in place).
+ * mimsem_tsw_diagnose replaces diagnose_s (:241-251: M2h->assemble(h); KSPSolve(ksp2h, M2 S) -> s), diagnose_Phi (:1019-1043:
+ *   Phi = K(u) u + 1/2 M2 S + 1/4 M2h(s) h) and the h2 of rhs_u (:1078-1080: M2h->assemble(h); KSPSolve(ksp2, M2h h) -> h2):
+ *   the element's Whmat(h) block is assembled at the quadrature points and factored by LU without pivoting (the signed determinant makes
+ *   the block negative definite where det < 0).
+ * mimsem_tsw_update replaces the h and S updates of the three stages (:894-1000) with rhs_S (:1095-1120):
+ *   fS = 1/2 M2 E21 G + 1/2 M2h(s) E21 F + K(grad_s) F,  h_j <- alpha h_i + beta (h_j - dt E21 F),
+ *   S_j <- alpha S_i + beta S_j - beta dt M2^-1 fS  ((alpha, beta) = (0, 1), (3/4, 1/4), (1/3, 2/3) for stages 1..3). */
+int mimsem_tsw_diagnose(mimsem_ctx* ctx, const double* h, const double* S, const double* u, const double* m2inv,
+                        double* s, double* Phi, double* h2);
+int mimsem_tsw_update(mimsem_ctx* ctx, const double* F, const double* G, const double* grad_s, const double* s, const double* m2inv,
+                      const double* h_i, const double* S_i, double* h_j, double* S_j, double alpha, double beta, double dt);
+
 /* ---- vertical / column operators (rows C1..C9), eul/VertOps.h:45-72 ------------------------- */
 enum mimsem_colop {
     MIMSEM_V_CONST = 0, MIMSEM_V_CONST_INV = 1, MIMSEM_V_CONST_RHO = 2, MIMSEM_V_CONST_RHO_INV = 3,

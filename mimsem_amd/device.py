@@ -468,6 +468,31 @@ class Engine:
                                               _ptr(y2), y2.stride(0), alpha), "mimsem_elem_blocks_apply")
         return y if x.dim() == 2 else y2[0]
 
+    def _tsw_vec(self, form, t, what):
+        _need(t is not None and t.dim() == 1 and t.shape[0] == self.sizes[form], "%s: a [%d] row" % (what, self.sizes[form]))
+        return _ptr(t)
+
+    def tsw_diagnose(self, h, S, u, m2inv, s=None, Phi=None, h2=None):
+        """mimsem_tsw_diagnose: s = M2h(h)^-1 M2 S, Phi = K(u) u + 1/2 M2 S + 1/4 M2h(s) h, h2 = M2^-1 M2h(h) h in one launch
+        (src/ThermalSW_EEC_2.cpp diagnose_s, diagnose_Phi, rhs_u).  h, S: 2-form rows, u: a 1-form row, m2inv: the WMATINV element
+        matrices [nEl, n2e * n2e]."""
+        _need(m2inv.numel() == self.nEl * self.n2e * self.n2e, "m2inv: the WMATINV element matrices")
+        s = torch.empty_like(h) if s is None else s
+        Phi = torch.empty_like(h) if Phi is None else Phi
+        h2 = torch.empty_like(h) if h2 is None else h2
+        check(self.L.mimsem_tsw_diagnose(self.ctx, self._tsw_vec(2, h, "h"), self._tsw_vec(2, S, "S"), self._tsw_vec(1, u, "u"), _ptr(m2inv),
+                                         self._tsw_vec(2, s, "s"), self._tsw_vec(2, Phi, "Phi"), self._tsw_vec(2, h2, "h2")), "mimsem_tsw_diagnose")
+        return s, Phi, h2
+
+    def tsw_update(self, F, G, grad_s, s, m2inv, h_i, S_i, h_j, S_j, alpha, beta, dt):
+        """mimsem_tsw_update: h_j <- alpha h_i + beta (h_j - dt E21 F), S_j <- alpha S_i + beta S_j - beta dt M2^-1 fS with
+        fS = 1/2 M2 E21 G + 1/2 M2h(s) E21 F + K(grad_s) F (src/ThermalSW_EEC_2.cpp solve_rk, rhs_S), h_j and S_j in place"""
+        _need(m2inv.numel() == self.nEl * self.n2e * self.n2e, "m2inv: the WMATINV element matrices")
+        check(self.L.mimsem_tsw_update(self.ctx, self._tsw_vec(1, F, "F"), self._tsw_vec(1, G, "G"), self._tsw_vec(1, grad_s, "grad_s"),
+                                       self._tsw_vec(2, s, "s"), _ptr(m2inv), self._tsw_vec(2, h_i, "h_i"), self._tsw_vec(2, S_i, "S_i"),
+                                       self._tsw_vec(2, h_j, "h_j"), self._tsw_vec(2, S_j, "S_j"), alpha, beta, dt), "mimsem_tsw_update")
+        return h_j, S_j
+
     def wvec(self, rho, lev0=0, scale=1.0, vert_scale=True, out=None):
         """Wvec::assemble(lev, scale, vert_scale, rho) (eul/Assembly.cpp:2457-2495; row B18): the matrix-free 2-form right-hand side
         W^T diag(w s/det [thickInv]) W rho -- Wmat applied to rho.  (The reference leaves its Wt table unfilled and has every call

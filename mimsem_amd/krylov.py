@@ -336,15 +336,17 @@ class MassSolver:
         self.eng.rowdot_local(self._pair, self._pair, out=self._log[k], space=1)       # (sharded: this rank's ownership-weighted part; verify() reduces the log once)
         return x
 
-    def verify(self, rtol=1e-14):
+    def verify(self, rtol=1e-14, host_log=None):
         """the checks of every fixed-length solve since the last call in ONE read: True = every level of every solve had its last
         preconditioned residual below 30 rtol |P b| (one more contraction lies between that residual and the result).  False: the
-        Chebyshev mode is switched off (PCG from here on) and the caller redoes its evaluation.  Synchronises."""
+        Chebyshev mode is switched off (PCG from here on) and the caller redoes its evaluation.  Synchronises -- unless the caller read
+        the log itself together with checks of its own (host_log: log().cpu() of that read, single rank)."""
         if self._log is None or self._slot == 0:
             return True
         if self.dist:
             self.eng.allreduce_checked(self._log)               # ONE all-reduce for every solve since the last call (+ the halo time-outs: HaloTimeout)
-        v = self._log.cpu().numpy()
+        import numpy as np
+        v = self._log.cpu().numpy() if host_log is None else np.asarray(host_log).reshape(self._log.shape)
         self._log.zero_(); self._slot = 0
         nlev = v.shape[1] // 2
         ok = True
@@ -363,6 +365,10 @@ class MassSolver:
         if not ok:
             self.chebyshev = False
         return ok
+
+    def log(self):
+        """the device log verify() reads (None before the first fixed-length solve)"""
+        return self._log
 
     def solve(self, b, lev0=0, rtol=1e-14, maxit=300):
         nlev = b.shape[0]
