@@ -7,16 +7,18 @@ the p=3, 24x24x6 cubed sphere with 30 levels (BASELINE config 4 grid, 103 680 pa
 N>1: the 24 patches (12x12 elements) are dealt to the ranks (strong scaling) and each step ends with the
 halo reduce (RCCL send/recv over xGMI) that replaces the reference's VecScatter REVERSE/ADD.
 
-At N = 1 the same line also carries "sw": shallow-water time steps/s (the second half of BASELINE's metric; --no-sw skips it)
-and "column": HEVI column Schur solves/s on the same grid (--no-column skips it).
-Prints ONE compact JSON line (rank 0, < 4 KB: compact_record -- the contract's keys, roofline, roofline_cold, cpu_baseline(+_column,
-+_sw) and one-number summaries); the full object with every extra goes to bench_extras.json (repo root and gpurun_out/).
+A plain run does only what the headline needs: set-up, --warmup steps, the --steps timed steps, --dump-outputs, and ONE compact JSON
+line (rank 0, < 4 KB: compact_record) with the contract's keys and the roofline of the live kernel durations sampled inside the timed
+region.  Everything else is measured with --full only: the timed region repeated (ms_per_step_median), roofline_cold, the operator
+families, the p=4 box, "sw" (shallow-water time steps/s, the second half of BASELINE's metric), "column" (HEVI column Schur solves/s),
+HorizSolve, the batch sweep, the PMC passes, cpu_baseline(+_column, +_sw) and the N > 1 companions; the line then carries their
+one-number summaries and the full object with every extra goes to bench_extras.json (repo root and the output directory).
 --dump-outputs DIR writes the result of the last timed step (y of the Umat apply, float64) to DIR/umat_y.npy (N > 1: each rank its
 own patches, DIR/umat_y_rank<r>.npy); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 `python bench.py --gpus N` started without WORLD_SIZE launches its own N ranks as a child torch.distributed.run.  roofline: dominant kernel k_elem_apply<3,UMAT>, HIP-event timed inside the timed
 region, against the launch's COMPULSORY bytes (b1_launch_bytes: frac <= 1 by construction; SURVEY 8(d)'s per-unit
 figure rides along as `algorithmic_reference` only).  The headline workload is Infinity-Cache resident
-(`cache_resident: true`); `roofline_cold` repeats the step on 8 independent spheres (829 440 units, ~1 GB working
+(`cache_resident: true`); `roofline_cold` (--full) repeats the step on 8 independent spheres (829 440 units, ~1 GB working
 set) -- that one is the HBM statement.  cpu_baseline: the oracle's reference-structure (assemble CSR + SpMV) path on
 host cores; cpu_baseline_column: the oracle's solve_schur_column_eta column by column; cpu_baseline_sw: the assemble + MatMult work of one
 shallow-water Picard iteration (Krylov solves excluded: an upper bound of the CPU's steps/s).
@@ -981,6 +983,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="measure beyond the headline: the repeated timed regions, the extras (each on by "
+                                                        "default at N = 1 unless its --no-* option skips it) and bench_extras.json; every "
+                                                        "option but --gpus, --steps, --warmup and --dump-outputs acts only with --full")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--families", action="store_true", help="(default at N = 1) every operator family with its roofline fraction, the p=4 box, the local layouts")
     ap.add_argument("--no-families", action="store_true", help="skip the per-family / box_p4 / reference_local_layout extras")
@@ -1003,6 +1008,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's result (the Umat apply's y, float64) as DIR/<name>.npy")
     a = ap.parse_args()
+    opted_in = [f for f in ("families", "box", "column", "horiz", "sweep", "sw", "pcie") if getattr(a, f)]
+    if opted_in and not a.full:
+        ap.error("--%s measures beyond the headline: add --full" % " --".join(opted_in))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -1126,9 +1134,9 @@ def main():
         # what the caller of the timed step holds after its last step (N > 1: the rank's patches, shared edges complete)
         dump_outputs(a.dump_outputs, {"umat_y" if world == 1 else "umat_y_rank%d" % rank: y})
     # `value` is the contract's number: EXACTLY `steps` steps, once.  At the driver's --steps 20 that is a 0.4 ms sample, so the same timed
-    # region is repeated a few more times (same step count, same fences, max over ranks each) and the median is reported BESIDE it
+    # region is repeated a few more times under --full (same step count, same fences, max over ranks each) and the median is reported BESIDE it
     rep_dts = [dt]
-    for _ in range(max(0, int(os.environ.get("MIMSEM_BENCH_REPEATS", "7")) - 1)):
+    for _ in range(max(0, int(os.environ.get("MIMSEM_BENCH_REPEATS", "7")) - 1) if a.full else 0):
         fence()
         tr0 = time.perf_counter()
         for _ in range(a.steps):
@@ -1151,9 +1159,6 @@ def main():
     out = {
         "metric": "element operator-applies/sec", "value": value, "unit": "element operator-applies/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
-        "ms_per_step_median": 1e3 * dt_median / a.steps, "value_median": units_total * a.steps / dt_median,
-        "timed_region_repeats": {"count": len(rep_dts), "ms_per_step_min": 1e3 * rep_sorted[0] / a.steps, "ms_per_step_max": 1e3 * rep_sorted[-1] / a.steps,
-                                 "note": "the first repeat is the contract's timed region (value, ms_per_step); the others repeat it unchanged"},
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": "Umat (B1, 1-form mass) matrix-free apply over every (element, level) pair of the "
                                "p=3 24x24x6 cubed sphere x 30 levels (BASELINE config 4 grid); N>1: patches dealt to the ranks, boundary "
@@ -1161,6 +1166,11 @@ def main():
                    "order": PN, "elements": cs.ne * cs.ne * 6, "levels": NK, "units_per_step": units_total,
                    "patches": NPATCH, "patches_per_gpu": len(pids), "scale": SCALE, "level_chunk": None},
     }
+    if a.full:
+        out.update({"ms_per_step_median": 1e3 * dt_median / a.steps, "value_median": units_total * a.steps / dt_median,
+                    "timed_region_repeats": {"count": len(rep_dts), "ms_per_step_min": 1e3 * rep_sorted[0] / a.steps,
+                                             "ms_per_step_max": 1e3 * rep_sorted[-1] / a.steps,
+                                             "note": "the first repeat is the contract's timed region (value, ms_per_step); the others repeat it unchanged"}})
     if safe_line is not None:
         out["config"]["same_step_over_torch_all_to_all_ms"] = safe_line["ms_per_step"]        # (the safety net's measurement, beside the C ABI's)
     if deng is not None:
@@ -1180,7 +1190,8 @@ def main():
                                          note="working set (~35 MB fields + metric) sits inside the 256 MiB Infinity Cache and is re-read "
                                               "every step: see roofline_cold for the HBM-resident workload", kname=kname, k2name=k2name)
         if world == 1:
-            out["roofline"]["whole_operator"]["copy_of_the_same_bytes_us"] = copy_reference_us(bm["op_compulsory"], torch, eng.device)
+            if a.full:
+                out["roofline"]["whole_operator"]["copy_of_the_same_bytes_us"] = copy_reference_us(bm["op_compulsory"], torch, eng.device)
             # NOT measured in this run: the PMC passes need rocprofv3 (scripts/pmc_traffic.py); the committed summary of the
             # same 103 680-unit launch is quoted for orientation only
             try:
@@ -1191,6 +1202,14 @@ def main():
                     "constant, not an observation of this run"}
             except Exception:
                 pass
+    if not a.full:
+        # the headline is complete: the extras below take runs of their own and wait for --full
+        if rank == 0:
+            sys.stdout.write(compact_record(out)[1] + "\n"); sys.stdout.flush()
+        if use_dist:
+            dist.destroy_process_group()
+        return
+
     def box_extras():
         from mimsem_amd.geom import BoxGeom
         from mimsem_amd.mesh import PeriodicBox, box_coords

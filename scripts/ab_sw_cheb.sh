@@ -5,7 +5,7 @@ export MIMSEM_EXPERIMENTS=1      # (the switches below belong to closed experime
 EXP_LIB="$(cd "$(dirname "$0")/.." && pwd)/build_ab/libmimsem_hip_exp.so"; [ -z "$MIMSEM_LIB" ] && [ -f "$EXP_LIB" ] && export MIMSEM_LIB="$EXP_LIB"      # (the variants are compiled in only with -DMIMSEM_WITH_EXPERIMENTS: scripts/build_variant.sh exp "-DMIMSEM_WITH_EXPERIMENTS")
 R=$GRAFT_REPO_ROOT; cd $R
 for e in 0 1 0 1; do
-  MIMSEM_SW_CHEB=$e python3 bench.py --no-families --no-column --no-sweep --cold 0 --no-pmc --no-cpu > /dev/null 2> /dev/null
+  MIMSEM_SW_CHEB=$e python3 bench.py --full --no-families --no-column --no-sweep --cold 0 --no-pmc --no-cpu > /dev/null 2> /dev/null
   python3 - <<PY
 import json
 d = json.load(open("bench_extras.json"))["sw"]

@@ -6,11 +6,11 @@ set -o pipefail
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final3; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-echo "[1] bench default"; python bench.py --steps 300 --warmup 30 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
-echo "[2] bench extras"; python bench.py --no-cpu --no-pmc --no-sweep --horiz --pcie > $O/bench_extras.json 2> $O/bench_extras.err || { tail -5 $O/bench_extras.err; exit 1; }
+echo "[1] bench default"; python bench.py --full --steps 300 --warmup 30 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+echo "[2] bench extras"; python bench.py --full --no-cpu --no-pmc --no-sweep --horiz --pcie > $O/bench_extras.json 2> $O/bench_extras.err || { tail -5 $O/bench_extras.err; exit 1; }
 cd /tmp
 echo "[3] rocprofv3 stats of the bench command"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r03 -- python3 $R/bench.py --no-cpu --no-pmc --no-sw --no-column --no-families --no-sweep --steps 300 --warmup 30 > $O/bench_under_rocprof.json 2> $O/rocprof.err || { tail -5 $O/rocprof.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o r03 -- python3 $R/bench.py --full --no-cpu --no-pmc --no-sw --no-column --no-families --no-sweep --steps 300 --warmup 30 > $O/bench_under_rocprof.json 2> $O/rocprof.err || { tail -5 $O/rocprof.err; exit 1; }
 echo "[4] hot / cold launches separately"
 for w in hot cold; do
   ONLY=$w REPS=40 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$w -o r03 -- python3 $R/scripts/prof_umat.py > $O/stats_$w.log 2>&1 || { tail -5 $O/stats_$w.log; exit 1; }

@@ -3,6 +3,8 @@ must stay below 4 KB whatever the extras hold, and must carry the contract's key
 import json
 import os
 
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,3 +71,33 @@ def test_dump_outputs_writes_float64_npy(tmp_path):
     with pytest.raises(AssertionError):
         bench.dump_outputs(str(tmp_path / "e"), {"big": torch.zeros(bench.DUMP_CAP_BYTES // 8 + 1, dtype=torch.float64)})
     assert not (tmp_path / "e").exists()
+
+
+def test_extras_need_full():
+    """an option that selects an extra is refused without --full (it would otherwise be ignored without a word)"""
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--pcie"], capture_output=True, text=True, timeout=60, cwd=ROOT)
+    assert out.returncode != 0 and "--full" in out.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_only(tmp_path):
+    """`bench.py --gpus 1` without --full: warm-up, the timed steps, --dump-outputs and the line -- no extra, no extras file"""
+    import subprocess
+    import sys
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "element operator-applies/sec" and d["unit"] == "element operator-applies/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and d["steps"] == 20 and d["warmup"] == 5 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert 0 < d["roofline"]["frac"] <= 1
+    assert d["summary"] == {} and d["ms_per_step_median"] is None
+    for k in ("roofline_cold", "cpu_baseline", "extras_file", "extras_with_errors"):
+        assert k not in d, k
+    y = np.load(tmp_path / "umat_y.npy")
+    assert y.dtype == np.float64 and y.shape[0] == 30 and np.isfinite(y).all()
