@@ -644,6 +644,15 @@ int  mimsem_ksp_set_pc_jacobi(mimsem_ksp* ksp, const double* dinv, long long din
  * level geom_lev0 without its thickness factor, D_e = 1 / (number of elements sharing the edge), times 1 / mean(thickInv) of the
  * element per level when the operator carries the thickness flag (exact where a layer's thickness is uniform over an element).     */
 int  mimsem_ksp_set_pc_bjacobi(mimsem_ksp* ksp);
+/* The same blocks in ONE capturable launch, for a preconditioner rebuilt every stage (PCSetUp of ksp1h after M1h->assemble(h),
+ * src/ThermalSW_EEC_2.cpp:253-268): out[e] = D_e (A_e)^-1 D_e, [nEl][2 n1e][2 n1e] row-major (the layout mimsem_ksp_get_pc_blocks returns and
+ * mimsem_elem_blocks_apply(form 1, transposed) reads), A_e the element block of operator `op` at geometry level geom_lev with (scale, flags, f)
+ * as mimsem_op_element_matrices takes them.  One wavefront per element assembles the block at the quadrature points, inverts it (full
+ * pivoting) and scales it in LDS, with the operations of mimsem_ksp_set_pc_bjacobi in the same order: the same bits.  MIMSEM_OP_UMAT and
+ * MIMSEM_OP_UHMAT (f: the 2-form depth row), flags 0, element orders 2..5; anything else MIMSEM_ERR_UNSUPPORTED, a null pointer or a level
+ * outside the context MIMSEM_ERR_ARG.  No allocation, copy or synchronisation once the context holds its edge weights (made by the first
+ * call, which therefore must not be captured: MIMSEM_ERR_STATE).                                                                   */
+int  mimsem_elem_block_pc_build(mimsem_ctx* ctx, int op, int geom_lev, double scale, unsigned flags, const double* f, double* out);
 /* The reference's PCBJACOBI (PCBJacobiSetTotalBlocks(size*nElsX*nElsX), eul/HorizSolve.cpp:77-96, src/SWEqn_Picard.cpp:85-113): PCSetUp builds
  * the exact inverses of the assembled owned blocks (mimsem_owned_blocks_build + mimsem_block_inverse) of the operator of mimsem_ksp_set_operator,
  * one set per level of the operator (one for all levels when the operator has neither the thickness flag nor a field), and applies them with

@@ -1041,7 +1041,7 @@ void mimsem_ctx_destroy(mimsem_ctx* c) {
     orphan_graphs(c);
     void* ptrs[] = {c->d_xn, c->d_E, c->d_w, c->d_U, c->d_V, c->d_W, c->d_P, c->d_J, c->d_det, c->d_th, c->d_tI, c->d_tIp, c->d_tIn,
                     c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_iq, c->d_fperm, c->d_flid, c->d_fslot, c->d_fcnt, c->d_pslot, c->d_ppart, c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin, c->d_woplan, c->d_wgh, c->d_wgx, c->d_wpart, c->d_wsplit, c->d_colstat, c->d_forceflag, c->d_rdcnt, c->d_cheb, c->d_colratio, c->d_g1, c->d_bplan, c->d_g0, c->d_ye, c->d_col, c->d_lu, c->d_kry,
-                    c->d_d0, c->d_d1x, c->d_d1y, c->d_sh0, c->d_sh1, c->d_own[1], c->d_own[2]};
+                    c->d_d0, c->d_d1x, c->d_d1y, c->d_sh0, c->d_sh1, c->d_own[1], c->d_own[2], c->d_pcw};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (void* p : c->retired) (void)hipFree(p);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
@@ -1265,6 +1265,7 @@ static bool is_up_op(int op) {
 int mimsem_ctx_set_halo_slots(mimsem_ctx* c, int form, const int* slots, int n) {
     if (!c || form != 1 || n < 0 || (n && !slots)) return MIMSEM_ERR_ARG;
     if (c->is_capturing() || c->split.pending) return MIMSEM_ERR_STATE;      // (a pending BOUNDARY part belongs to the plan in force)
+    if (c->d_pcw) { c->retired.push_back(c->d_pcw); c->d_pcw = nullptr; }      // (the element-block weights count halo edges twice: remade on next use)
     if (!c->wave1 && c->h_i1x.empty()) {      // two-pass form: nothing to reorder (the split degenerates, see mimsem_op_apply_part); the marks are kept all the same
         c->h_halo1.assign(c->n1, 0);
         for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= c->n1) return MIMSEM_ERR_ARG; c->h_halo1[slots[i]] = 1; }

@@ -141,6 +141,7 @@ struct mimsem_ctx {
     long long ye_doubles = 0;
     // owned-block preconditioner (owned_blocks.hip): per form 1 / 2, [nEl][rows] {slot, owner position, other position, 0}, built on first use
     int4* d_own[3] = {nullptr, nullptr, nullptr}; int own_uncovered[3] = {0, 0, 0};      // slots of the form that no element owns
+    double* d_pcw = nullptr;    // [nEl][2 n1e] 1 / edge multiplicity of the element-local 1-form DoFs (mimsem_elem_block_pc_build), made on first use
     double* d_cheb = nullptr; long long cheb_doubles = 0;      // mimsem_block_chebyshev_solve: the second iterate and two direction vectors, [3][nlev][n1]
     int ensure_cheb(long long doubles);
     int *d_d0 = nullptr, *d_d1x = nullptr, *d_d1y = nullptr;   // direct-write slots (single-contributor DoFs), see ElemArgs

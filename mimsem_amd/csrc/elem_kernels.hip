@@ -2133,3 +2133,5 @@ int launch_halo_unpack(mimsem_ctx* c, const int* idx, int count, int nlev, int m
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
+
+#include "elem_block_pc.inc"

@@ -649,3 +649,21 @@ int mimsem_ksp_get_info(const mimsem_ksp* k, int* its, double* rnorm, int* reaso
 }
 
 }  // extern "C"
+
+// the edge weights of mimsem_elem_block_pc_build on the device: made once per context (the same D_e as above), then only read -- so that
+// the build itself allocates, copies and synchronises nothing and can be recorded.  MIMSEM_ERR_STATE when the first call is captured.
+int mimsem_pc_edge_weights(mimsem_ctx* c, const double** dw) {
+    if (!c->d_pcw) {
+        if (c->is_capturing()) return MIMSEM_ERR_STATE;
+        const int nd = 2*c->es.n1e;
+        std::vector<double> d;
+        int rc = edge_weights(c, nd, d);
+        if (rc) return rc;
+        double* p = nullptr;
+        MIMSEM_HIP_TRY(hipMalloc((void**)&p, std::max<size_t>(d.size(), 1)*8));
+        if (hipMemcpy(p, d.data(), d.size()*8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return MIMSEM_ERR_HIP; }
+        c->d_pcw = p;
+    }
+    *dw = c->d_pcw;
+    return MIMSEM_OK;
+}

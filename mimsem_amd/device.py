@@ -442,6 +442,15 @@ class Engine:
               "mimsem_op_element_matrices(%s)" % op)
         return out
 
+    def elem_block_pc(self, op, f=None, lev=0, scale=1.0, flags=0, out=None):
+        """mimsem_elem_block_pc_build: D_e (A_e)^-1 D_e of a 1-form mass operator (UMAT, UHMAT with f = the depth row) in one launch,
+        [nEl, 2 n1e, 2 n1e] -- the blocks mimsem_ksp_set_pc_bjacobi builds, for blocks_apply(1, ..., transpose=True)"""
+        nd = 2 * self.n1e
+        out = torch.empty(self.nEl, nd, nd, dtype=torch.float64, device=self.device) if out is None else out
+        _need(out.shape == (self.nEl, nd, nd) and out.is_contiguous(), "out: a contiguous [nEl, 2 n1e, 2 n1e] tensor")
+        check(self.L.mimsem_elem_block_pc_build(self.ctx, OPS[op], lev, scale, flags, _ptr(f), _ptr(out)), "mimsem_elem_block_pc_build(%s)" % op)
+        return out
+
     def element_matrices_ray(self, exner, exner_s, dt, lev=0, scale=1.0):
         esz = self.L.mimsem_op_elmat_size(self.ctx, OPS["UMAT_RAY"])
         out = torch.empty(self.nEl, esz, dtype=torch.float64, device=self.device)

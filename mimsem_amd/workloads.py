@@ -45,6 +45,41 @@ def write_arrays(path, arrays):
             a.tofile(f)
 
 
+def read_arrays(path):
+    """the named arrays of write_arrays (also what tests/cpp/test_tsw.cpp writes back): {name: numpy array}"""
+    import struct
+
+    import numpy as np
+    out = {}
+    with open(path, "rb") as f:
+        if f.read(8) != b"MSEMARR1":
+            raise ValueError("%s: not an array file" % path)
+        (count,) = struct.unpack("<i", f.read(4))
+        for _ in range(count):
+            (nl,) = struct.unpack("<i", f.read(4))
+            name = f.read(nl).decode()
+            kind, n = struct.unpack("<iq", f.read(12))
+            out[name] = np.fromfile(f, dtype=np.int32 if kind == 0 else np.float64, count=n)
+    return out
+
+
+def write_tsw_case(path, dm, fg, dt, nsteps, use_graph=True, m1h_its=16, quad=None, state=None):
+    """A thermal shallow-water case for the C++ host (tests/cpp/test_tsw.cpp, mimsem_amd/host/tsw_call.cpp over mimsem_thermalsw.hpp): the
+    tables of a DeviceMesh (nk = 1), the Coriolis 0-form, dt, and either the quadrature-grid fields (uq [nq, 2], hq, sq) that init() projects
+    or a start state (u, h, S) in the mesh's numbering"""
+    import numpy as np
+    a = mesh_arrays(dm)
+    a.update(fg=np.asarray(fg, dtype=np.float64).ravel(), dt=np.array([dt], dtype=np.float64),
+             opts=np.array([nsteps, int(use_graph), m1h_its, 1 if quad is not None else 0], dtype=np.int32))
+    if quad is not None:
+        for k, v in zip(("uq", "hq", "sq"), quad):
+            a[k] = np.asarray(v, dtype=np.float64).ravel()
+    else:
+        for k, v in zip(("u0", "h0", "S0"), state):
+            a[k] = np.asarray(v, dtype=np.float64).ravel()
+    write_arrays(path, a)
+
+
 def mesh_arrays(dm):
     """the tables of a DeviceMesh under their mimsem_mesh_desc names (sw_io.hpp::desc_of)"""
     import numpy as np
