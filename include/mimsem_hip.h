@@ -131,8 +131,17 @@ int  mimsem_op_level_chunk(const mimsem_ctx* ctx, int nlev);
 /* The wave-level fused form of the 1-form -> 1-form operators (Umat, Uhmat, RotMat, Ut_mat; the default for orders <= 4 unless
  * MIMSEM_WAVE=0): out[0] = wave-groups (wavefronts per level chunk), out[1] = vector slots the element kernel writes straight
  * into y, out[2] = partial sums per level it leaves in the workspace, out[3] = slots the perimeter pass finishes,
- * out[4] = levels one wavefront works through at a call over nlev levels (chunks of 8, several per wavefront when the launch has wavefronts to spare).  Returns 0 when the form is off (all five are then 0). */
+ * out[4] = levels the longest work item holds at a call over nlev levels (chunks of 8, several per wavefront when the launch has
+ * wavefronts to spare; the one-launch Umat form walks exactly the levels an item has).  Returns 0 when the form is off (all five are then 0). */
 int  mimsem_op_wave_stats(const mimsem_ctx* ctx, int nlev, int out[5]);
+/* Work items of the one-launch Umat form (p = 3): part_levels > 0 cuts the levels of a call into the fewest parts of at most that many
+ * levels (rounded up to whole level pairs), dealt evenly -- lengths differ by at most one pair; 0 = the library's own rule.  order: bit 0
+ * XCD-contiguous workgroup order, bit 1 the parts of a group as neighbouring work items (default 3), -1 = leave as it is.  Results do not
+ * depend on either (tests/test_gpu_wave_ranges.py).  TUNING AND TESTS ONLY, not part of the stable surface: it is context state, not
+ * per-launch state, and it moves the one-launch form alone -- after a call with part_levels > 0, mimsem_op_wave_stats out[4] reports the
+ * requested parts for that form while the two-launch form of the same context (MIMSEM_WAVE_OWN=0, split applies) keeps its chunks, so the
+ * two can report different numbers until part_levels is set back to 0.  Applies to the launches that follow; not inside a stream capture. */
+int  mimsem_ctx_set_wave_split(mimsem_ctx* ctx, int part_levels, int order);
 /* Interior / boundary split of a 1-form operator apply, so that a halo exchange overlaps the interior work (the
  * reference's MatMult + VecScatterBegin/End, eul/Assembly.cpp:2194-2195): tell the context once which 1-form slots take part in an
  * exchange (ghosts and mirrors of mimsem_halo_create's lists) -- the element groups touching them are moved to the front of the

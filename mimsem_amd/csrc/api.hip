@@ -605,8 +605,9 @@ int level_chunk(const mimsem_ctx* c, int nlev) {
 
 // levels per work item of the wave-level kernel: its compile-time bound WLC = 8 whenever the call has that many levels.  A wavefront's
 // fixed costs (kernel arguments, tables, metric, the dispatch of the wave itself: ~25 cycles per wave and XCD) are what the
-// 103 680-unit launch is made of (scripts/wave_size_sweep.py, s_memtime stamps of scripts/stamp_wave.sh), and the kernel computes
-// all WLC levels of a work item whether the chunk has them or not -- so: as many levels per wave as there are.
+// 103 680-unit launch is made of (scripts/wave_size_sweep.py, s_memtime stamps of scripts/stamp_wave.sh), and the chunk form computes
+// all WLC levels of a work item whether the chunk has them or not -- so: as many levels per wave as there are.  (The owner-computes
+// form walks level ranges instead: wave_level_parts.)
 int wave_level_chunk(const mimsem_ctx* c, int nlev) {
     if (c->wave_lch > 0) return std::max(1, std::min(std::min(c->wave_lch, 8), nlev));
     return std::max(1, std::min(8, nlev));
@@ -624,6 +625,30 @@ int wave_chunks_per_item(const mimsem_ctx* c, int nlev, int lch, int ngroups) {
     // chunks took 17.2 us, 4 parts of 2 take 14.0 us -- round 3)
     for (int np = nparts; np <= nch; np++) if (nch%np == 0) { nparts = np; break; }
     return (nch + nparts - 1)/nparts;
+}
+
+// Level RANGES of the owner-computes form (round 10): every group is cut into `np` parts of whole level pairs, and the kernel walks
+// exactly the batches a part has (elem_wave.inc: the wavefront ends behind its last batch), so no batch is computed for nothing.
+// By default the parts ARE the chunk form's work items -- first level k L, L = wave_level_chunk x wave_chunks_per_item levels, the last
+// one whatever is left (30 levels on 864 groups: 16 + 14; 11 levels: 8 + 3; 30 levels on 6 912 groups: one part of 30) -- so a context
+// reports one number of levels per item (mimsem_op_wave_stats out[4]) whichever of its two forms runs, and the two rules move together
+// or not at all.  Measured on the 864-group sphere x 30 levels (profiles/r10_wave_ranges_ab.txt, us per back-to-back step):
+// 30: 15.5, 16 + 14: 12.8, 10 x 3: 12.5, 8 + 8 + 8 + 6: 14.1, 6 x 5: 14.6.
+// A requested part length (mimsem_ctx_set_wave_split; MIMSEM_WAVE_LCH x MIMSEM_WAVE_CPP in the experiments build) is dealt EVENLY
+// instead: ceil(pairs / pairs of the request) parts whose lengths differ by at most one pair, the longer ones first (an odd nlev leaves
+// the last part one level short) -- 10 + 10 + 10, 8 + 8 + 8 + 6, and 33 levels by 8 as 8 + 8 + 6 + 6 + 5.
+struct WaveParts { int np, pb, pr, longest; };     // parts per group, level pairs of a part, parts that hold one pair more, levels of the longest part
+WaveParts wave_level_parts(const mimsem_ctx* c, int nlev, int ngroups) {
+    const int pairs = (nlev + 1)/2;
+    const int lch = wave_level_chunk(c, nlev);
+    const int asked = c->wave_part > 0 ? c->wave_part : ((c->wave_lch > 0 || c->wave_cpp > 0) ? lch*std::max(c->wave_cpp, 1) : 0);
+    const int tp = ((asked > 0 ? asked : lch*wave_chunks_per_item(c, nlev, lch, ngroups)) + 1)/2;      // pairs of a full part, >= 1
+    WaveParts w;
+    w.np = (pairs + tp - 1)/tp;
+    if (asked > 0) { w.pb = pairs/w.np; w.pr = pairs%w.np; }
+    else           { w.pb = tp; w.pr = 0; }
+    w.longest = std::min(nlev, 2*(w.pb + (w.pr ? 1 : 0)));
+    return w;
 }
 
 int op_spaces(int op, int* in, int* cf, int* out) {
@@ -1134,8 +1159,17 @@ int mimsem_op_wave_stats(const mimsem_ctx* c, int nlev, int out[5]) {
     if (!c->wave1) return 0;
     out[0] = c->w_ngroups; out[1] = c->w_ndirect; out[2] = c->w_npwritten; out[3] = c->w_nps;
     if (c->w_own) { out[1] = c->n1; out[2] = 0; out[3] = 0; }     // the headline operator's form: every slot written once, no partial sums
-    { const int lch = wave_level_chunk(c, nlev); out[4] = lch*wave_chunks_per_item(c, nlev, lch, c->w_ngroups); }
+    if (c->w_own && c->es.n == 3 && c->w_ntiles == 0 && !c->d_tIn) out[4] = wave_level_parts(c, nlev, c->w_ngroups).longest;     // the longest item's levels
+    else { const int lch = wave_level_chunk(c, nlev); out[4] = lch*wave_chunks_per_item(c, nlev, lch, c->w_ngroups); }
     return 1;
+}
+
+int mimsem_ctx_set_wave_split(mimsem_ctx* c, int part_levels, int order) {
+    if (!c || part_levels < 0 || order < -1 || order > 3) return MIMSEM_ERR_ARG;
+    if (c->is_capturing()) return MIMSEM_ERR_STATE;
+    c->wave_part = part_levels;
+    if (order >= 0) c->wave_order = order;
+    return MIMSEM_OK;
 }
 
 int mimsem_ctx_set_levels(mimsem_ctx* c, const double* thick, const double* thickInv) {
@@ -1411,6 +1445,12 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
         if (c->d_tIn) { a.tIp = c->d_tIn; a.tps = (long long)c->n0*2; a.tnode = 1; }     // (MIMSEM_WAVE_TNODE=1: thickInv per node)
         a.lch = wave_level_chunk(c, nlev);
         a.wcpp = wave_chunks_per_item(c, nlev, a.lch, g1 - g0);
+        a.wnp = a.wpb = a.wpr = 0;
+        if (own) {                                                       // level ranges instead of chunks (wave_level_parts)
+            const WaveParts wp = wave_level_parts(c, nlev, g1 - g0);
+            a.wnp = wp.np; a.wpb = wp.pb; a.wpr = wp.pr;
+            a.lch = nlev == 1 ? 1 : 8; a.wcpp = 1;                         // (lch only picks the instantiation: single-level calls have their own)
+        }
         a.swz = c->wave_order;
         a.wtfin = nullptr; a.wtile = 0;
         if (c->w_ntiles > 0) {                                           // tile mode (never together with a halo split: setup_wave)
@@ -1439,7 +1479,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
         for (size_t k = 0; k < 20; k++) a.Etab[k] = k < c->tab.E.size() ? c->tab.E[k] : 0.0;
 #ifdef MIMSEM_STAMPS      // diagnostic build: per-phase s_memtime stamps of every work item of this launch, summarised on stderr
         static long long* d_st = nullptr; static size_t st_items = 0;
-        const size_t items = (size_t)c->w_ngroups*((nlev + a.lch - 1)/a.lch);
+        const size_t items = (size_t)c->w_ngroups*std::max((nlev + a.lch - 1)/a.lch, a.wnp);     // (the kernel stamps item < wgroups x parts: never fewer slots than that)
         if (exp_env("MIMSEM_WAVE_STAMPS")) {
             if (items > st_items) { if (d_st) (void)hipFree(d_st); (void)hipMalloc((void**)&d_st, items*16*8); st_items = items; }
             (void)hipMemsetAsync(d_st, 0, items*16*8, c->stream);

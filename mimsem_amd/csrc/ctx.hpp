@@ -97,6 +97,7 @@ struct mimsem_ctx {
     int wave_lch = 0;                   // MIMSEM_WAVE_LCH override of the levels per chunk
     int wave2_mode = 1;                 // MIMSEM_WAVE2: 2-form-valued operators on k_apply_wave2 (p = 3): 0 none, 1 Whmat / WtQUmat / WtQdUdz, 2 also Wmat
     int wave_cpp = 0;                   // MIMSEM_WAVE_CPP override of the chunks per work item (0: heuristic)
+    int wave_part = 0;                  // mimsem_ctx_set_wave_split: levels of a part of the owner form's level ranges (0: the items of the chunk form)
     int w_ngroups = 0, w_nsing = 0, w_nps = 0, w_npart = 0, w_ndirect = 0;
     int w_npwritten = 0;                // partial sums a level really gets (w_npart is the padded row: w_nsides x 2 x 16)
     // in-kernel completion of the perimeter (round 3, elem_wave.inc "finishing phase"): the partial sums are laid out per SIDE (the
@@ -220,6 +221,10 @@ struct ElemArgs {
     const int4* wfin; const int* wsslot; int* wcnt;      // finishing phase (null: the perimeter pass follows)
     const int4* wtfin; int wtile;                        // tile mode: finishing entries per tile (stride wtile), or null
     const int4* wgh; const int* wgx;                     // owner-computes form: packed ghost lanes, gathered slots (build_wave_own), or null
+    // level ranges (round 10, wave_level_parts): wnp > 0 -- every group is cut into wnp parts of whole level PAIRS, part k = levels
+    // 2 (k wpb + min(k, wpr)) .. + 2 (wpb + (k < wpr)), clipped to nlev; a wavefront leaves at the first batch boundary at or beyond its
+    // last level.  0: the chunk arithmetic (lch, wcpp)
+    int wnp, wpb, wpr;
     int wfence;                      // finishing phase, experiment: partial sums in PLAIN memory, one agent-scope release fence per wavefront before its arrival
     double Etab[20];                 // edge-basis table E[mp1][n] by value (orders <= 4): SGPRs, no load in the kernel
     double Wq[5];                    // GLL weights by value (orders <= 4)

@@ -1664,7 +1664,8 @@ int launch_gather_perim(mimsem_ctx* c, int nlev, const double* yp, long long yps
 template <int N>
 static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     const int nch = (a.nlev + a.lch - 1)/a.lch;
-    const long long items = (long long)a.wgroups*((nch + a.wcpp - 1)/a.wcpp);
+    if (a.wnp > 0 && (a.wtfin || a.wfin || a.wpb < 1 || a.wpr < 0 || a.wpr >= a.wnp || 2*(a.wnp*a.wpb + a.wpr) < a.nlev)) return MIMSEM_ERR_ARG;   // level ranges cover the call; not for the tile / finishing forms
+    const long long items = (long long)a.wgroups*(a.wnp > 0 ? a.wnp : (nch + a.wcpp - 1)/a.wcpp);
     if (items >= (1LL << 31)) return MIMSEM_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)((items + WNW - 1)/WNW);
     if (grid == 0) return MIMSEM_OK;
@@ -1672,7 +1673,7 @@ static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     const bool tile = a.wtfin != nullptr;
     if (tile && (!TILEABLE || a.wgroups%4 != 0 || a.wg0 != 0 || a.lch*a.wcpp > MIMSEM_WTLEV)) return MIMSEM_ERR_STATE;
     const bool own = a.wgh != nullptr;                   // owner-computes form (Umat at p = 3): one launch, no perimeter pass
-    if (own && (N != 3 || op != MIMSEM_OP_UMAT || tile)) return MIMSEM_ERR_STATE;
+    if (own && (N != 3 || op != MIMSEM_OP_UMAT || tile || a.wnp < 1)) return MIMSEM_ERR_STATE;
 #define MIMSEM_WL2(OPV, LCT, ACC, TL, OW) \
         if (c->ev_k1[0]) hipExtLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL, OW>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
         else hipLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL, OW>), dim3(grid), dim3(64*WNW), 0, c->stream, a)

@@ -51,6 +51,18 @@ __device__ __forceinline__ void wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Level ranges: a wavefront whose work item has `left` <= 0 levels left ENDS (wave-uniform: `left` is an SGPR).  The stores of its last
+// batch are issued (program order: the statement is volatile and clobbers memory) and complete on their own; the loads still in flight
+// went to valid addresses and are abandoned: no s_waitcnt is ISSUED for them.  (That is a statement about instructions, not latency:
+// the hardware drains a wave's outstanding memory counters at s_endpgm, so the wave's slot stays held until those loads have returned.)
+// To the compiler this is ONE opaque instruction, so the ring of batches stays one basic block: written as a C++ branch out of the
+// ring, the three exits cost the owner kernel its register allocation (168 VGPRs and 14 spilled, against 150 and none).
+// The compiler does not know that the kernel can end here: whatever the kernel does BEHIND the level loop is skipped by a wavefront
+// that leaves this way.  Only the form with nothing behind the loop may use it (OWN: see the tail of k_apply_wave).
+__device__ __forceinline__ void wave_exit_if_done(int left) {
+    asm volatile("s_cmp_gt_i32 %0, 0\n\ts_cbranch_scc1 .Lwave_goes_on%=\n\ts_endpgm\n.Lwave_goes_on%=:" :: "s"(left) : "scc", "memory");
+}
+
 // 64-bit value of another lane of the same DPP row (16 lanes = one element at p = 3): two v_mov_b32_dpp.  CTRL: quad_perm [j,j,j,j] =
 // j*0x55 (lane j of the caller's quad), row_ror:n = 0x120 + n (lane L reads lane (L - n) mod 16 of its row).  The compiler owns the
 // hazard handling of these builtins (unlike the inline-asm DPP FMAs of the column kernels).
@@ -162,8 +174,12 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
 #endif
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63, el = lane/LPE, q = lane%LPE;
-    // a work item = (wave-group, `wcpp` consecutive chunks of a.lch levels): tables, metric and basis values are loaded once for all of them
-    const unsigned nchunk = ((unsigned)((a.nlev + a.lch - 1)/a.lch) + (unsigned)a.wcpp - 1)/(unsigned)a.wcpp;     // parts per group
+    // a work item = (wave-group, first level, number of levels): tables, metric and basis values are loaded once for all of them.  Level
+    // RANGES (a.wnp > 0; the owner form always): the group's wnp parts of whole level pairs (ElemArgs::wnp); otherwise `wcpp` consecutive
+    // chunks of a.lch levels
+    const bool ranged = OWN || a.wnp > 0;                // wave-uniform (kernel argument)
+    const unsigned nchunk = ranged ? (unsigned)a.wnp
+                                   : ((unsigned)((a.nlev + a.lch - 1)/a.lch) + (unsigned)a.wcpp - 1)/(unsigned)a.wcpp;     // parts per group
     const unsigned nitems = (unsigned)a.wgroups*nchunk;                        // < 2^31: checked by the launcher
     const unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x, a.swz & 1);
     const unsigned item = bid*NW + (unsigned)wv;
@@ -172,7 +188,9 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
     if (!TILE && (a.swz & 2)) { g = item/nchunk; ch = item%nchunk; }            // group-major: the chunks of a group are neighbours
     else           { g = item%(unsigned)a.wgroups; ch = item/(unsigned)a.wgroups; }       // (tile mode: wgroups is a multiple of 4, so a workgroup = one tile, one chunk)
     g += (unsigned)a.wg0;                                // a launch over a sub-range of the groups (interior / boundary split)
-    int lbeg = (int)ch*a.lch*a.wcpp;
+    int lbeg, lend;                                      // the item's levels [lbeg, lend): SGPRs
+    if (ranged) { lbeg = 2*((int)ch*a.wpb + min((int)ch, a.wpr)); lend = min(a.nlev, lbeg + 2*(a.wpb + ((int)ch < a.wpr ? 1 : 0))); }
+    else        { lbeg = (int)ch*a.lch*a.wcpp; lend = min(a.nlev, lbeg + a.lch*a.wcpp); }
 #ifdef MIMSEM_STAMPS
     if (a.wstamps && lane == 0) a.wstamps[(size_t)item*16 + 0] = t_entry;
 #endif
@@ -351,9 +369,9 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
     for (int i = 0; i < LB; i++) s_x[wv][i][ZERO] = 0.0;     // every lane, same value: the second operand of single-contributor sums
     gchar* const dumpp = (gchar*)(a.out + a.wdump + 2*lane);   // tail of the first partial-sum row
     gchar* const dumps = (gchar*)(a.out + a.wdump + lane);
-    for (int cc = 0; cc < a.wcpp; cc++, lbeg += a.lch) {
-    const int nl = min(a.nlev - lbeg, a.lch);
-    if (nl <= 0) break;                                  // wave-uniform
+    // one trip = the ring of LCT levels (a chunk form's item holds whole chunks of LCT levels, or a single shorter one)
+    for (int cc = 0; lbeg < lend; cc++, lbeg += LCT) {   // wave-uniform
+    const int nl = lend - lbeg;                          // levels the item still has: the ring's levels l >= nl store into the dump tail
 #pragma unroll
     for (int b0 = 0; b0 < LCT; b0 += LB) {
         __builtin_amdgcn_sched_barrier(0);
@@ -473,8 +491,22 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(OWN ? 3 
         }
         wave_fence();        // the strips are free again before the next batch lands in them
         WSTAMP(4 + b0/LB);                                // batch done (its stores issued)
+        // level ranges: the item ends with the batch that holds its last level -- a scalar branch on a wave-uniform value, behind the
+        // batch's stores.  The requests still in flight went to valid addresses (load_batch clamps) and are abandoned: no wait is issued
+        // for them (s_endpgm itself lets them drain).  (The ring's last batch leaves through the loop condition.)
+#ifdef MIMSEM_STAMPS
+        if constexpr (OWN) { if (b0 + LB < LCT && b0 + LB >= nl) goto levels_done; }
+#else
+        if constexpr (OWN) { if (b0 + LB < LCT) wave_exit_if_done(nl - (b0 + LB)); }
+#endif
     }
     }
+#ifdef MIMSEM_STAMPS
+levels_done: ;
+#endif
+    // NOTE (OWN): an owner-form wavefront whose item ends inside the ring never gets here -- wave_exit_if_done ends it in the loop (the
+    // MIMSEM_STAMPS build jumps to the label above instead, for its final stamp).  Everything below is `if constexpr (TILE)` or `!OWN`;
+    // code added behind the loop for OWN would run for some wavefronts only: give OWN a real branch out of the ring first.
     // ---- tile mode: the slots the groups of this tile share, from the workgroup's LDS straight into y ----
     if constexpr (TILE) {
         __syncthreads();                                   // every wavefront of the workgroup has stored its pairs (same chunk, same trip counts)
