@@ -195,6 +195,14 @@ int mimsem_op_apply(mimsem_ctx* ctx, int op, int geom_lev0, int nlev, double sca
                     const double* x, long long x_stride,
                     double* y, long long y_stride, double alpha);
 
+/* mimsem_op_apply with the geometry level of row r = geom_lev0 + r geom_lev_step.  Step 1 IS mimsem_op_apply.  Step 0 evaluates every row
+ * at geom_lev0: HorizSolve::diagVertVort (eul/HorizSolve.cpp:842-850) assembles M2 and F at level 0 for every interface, and the mirror
+ * reproduces that.  Step 0: MIMSEM_OP_WMAT and MIMSEM_OP_UHMAT (others MIMSEM_ERR_UNSUPPORTED), in the two-pass form (element pass +
+ * gather) -- row r has the bits of a one-row mimsem_op_apply at geom_lev0 in that form.  Any other step: MIMSEM_ERR_ARG.             */
+int mimsem_op_apply_levels(mimsem_ctx* ctx, int op, int geom_lev0, int geom_lev_step, int nlev, double scale, unsigned flags,
+                           const double* f, long long f_stride, const double* x, long long x_stride,
+                           double* y, long long y_stride, double alpha);
+
 /* Upwinded variants.  PHMAT_UP / ROTMAT_UP: the 0-form (trial function resp. vorticity) is evaluated at the departure
  * points x_q - tau*u_local(x_q) (the reference's tau = 1/(1/(fac*dt)) is formed by the caller).  UMAT_UP / UHMAT_UP /
  * UVEC_HU_UP: the test functions are evaluated at x_q + (op-specific shift).  u: second field (velocity) per level. */
@@ -662,6 +670,14 @@ int  mimsem_ksp_set_pc_bjacobi(mimsem_ksp* ksp);
  * outside the context MIMSEM_ERR_ARG.  No allocation, copy or synchronisation once the context holds its edge weights (made by the first
  * call, which therefore must not be captured: MIMSEM_ERR_STATE).                                                                   */
 int  mimsem_elem_block_pc_build(mimsem_ctx* ctx, int op, int geom_lev, double scale, unsigned flags, const double* f, double* out);
+/* The same for nlev rows in ONE capturable launch (nlev x nEl wavefronts): the PCSetUp per interface of Euler::HorizPotVort
+ * (M1t->assemble_h(i, SCALE, rho_h), eul/Euler_2.cpp:1079-1092) and HorizSolve::diagVertVort (F->assemble(rho_h, 0, false, SCALE),
+ * eul/HorizSolve.cpp:843-855).  Row r: geometry level geom_lev0 + r geom_lev_step (step 0 or 1), field row f + r f_stride; out
+ * [nlev][nEl][2 n1e][2 n1e].  MIMSEM_OP_UMAT, MIMSEM_OP_UHMAT and MIMSEM_OP_UTMAT_H (f: the 2-form density rows); every row has the bits of
+ * the single-level entry, and for UTMAT_H those of mimsem_ksp_set_pc_bjacobi.  Return codes and the first-call rule as above; a step other
+ * than 0 or 1, a negative nlev or f_stride, or a row whose level lies outside the context: MIMSEM_ERR_ARG.                              */
+int  mimsem_elem_block_pc_build_levels(mimsem_ctx* ctx, int op, int geom_lev0, int geom_lev_step, int nlev, double scale, unsigned flags,
+                                       const double* f, long long f_stride, double* out);
 /* The reference's PCBJACOBI (PCBJacobiSetTotalBlocks(size*nElsX*nElsX), eul/HorizSolve.cpp:77-96, src/SWEqn_Picard.cpp:85-113): PCSetUp builds
  * the exact inverses of the assembled owned blocks (mimsem_owned_blocks_build + mimsem_block_inverse) of the operator of mimsem_ksp_set_operator,
  * one set per level of the operator (one for all levels when the operator has neither the thickness flag nor a field), and applies them with

@@ -51,6 +51,8 @@ _SIGS = {
     "mimsem_memset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, c_ll]),
     "mimsem_op_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint,
                                   c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, C.c_double]),
+    "mimsem_op_apply_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint,
+                                         c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, C.c_double]),
     "mimsem_op_apply_up": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_uint,
                                      c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, C.c_double]),
     "mimsem_elem_blocks_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, C.c_double]),
@@ -162,6 +164,7 @@ _SIGS = {
     "mimsem_krylov_chebyshev_update": (C.c_int, [C.c_void_p, C.c_int, c_ll, C.c_double, C.c_double, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll]),
     "mimsem_selftest_rows_half": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "mimsem_elem_block_pc_build": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_uint, c_dp, c_dp]),
+    "mimsem_elem_block_pc_build_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, c_dp, c_ll, c_dp]),
     "mimsem_ksp_get_pc_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "mimsem_ksp_ritz": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mimsem_graph_begin": (C.c_int, [C.c_void_p]),

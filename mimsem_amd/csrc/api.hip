@@ -1282,7 +1282,7 @@ int mimsem_memset(mimsem_ctx* c, void* dev, int byte, long long bytes) {
 static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
                          const double* f, long long fs, const double* f2, long long f2s, double param,
                          const double* x, long long xs, double* y, long long ys, double alpha,
-                         const GatherEpilogue* epi = nullptr, const double* blocks = nullptr, int part = 0);
+                         const GatherEpilogue* epi = nullptr, const double* blocks = nullptr, int part = 0, int lev_step = 1);
 static bool is_up_op(int op);
 
 int mimsem_op_apply(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
@@ -1290,6 +1290,17 @@ int mimsem_op_apply(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale
                     double* y, long long ys, double alpha) {
     if (is_up_op(op)) return MIMSEM_ERR_ARG;   // need mimsem_op_apply_up
     return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, y, ys, alpha);
+}
+
+// HorizSolve::diagVertVort (eul/HorizSolve.cpp:842-850) assembles M2 and F at level 0 for EVERY interface: geom_lev_step 0 evaluates every
+// row at geom_lev0 (the two-pass form: element pass + gather); 1 is mimsem_op_apply
+int mimsem_op_apply_levels(mimsem_ctx* c, int op, int geom_lev0, int geom_lev_step, int nlev, double scale, unsigned flags,
+                           const double* f, long long fs, const double* x, long long xs,
+                           double* y, long long ys, double alpha) {
+    if (geom_lev_step == 1) return mimsem_op_apply(c, op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha);
+    if (geom_lev_step != 0) return MIMSEM_ERR_ARG;
+    if (op != MIMSEM_OP_WMAT && op != MIMSEM_OP_UHMAT) return MIMSEM_ERR_UNSUPPORTED;
+    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, y, ys, alpha, nullptr, nullptr, 0, 0);
 }
 
 static bool is_up_op(int op) {
@@ -1339,7 +1350,7 @@ int mimsem_op_apply_up(mimsem_ctx* c, int op, int geom_lev0, int nlev, double sc
 static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
                          const double* f, long long fs, const double* f2, long long f2s, double param,
                          const double* x, long long xs, double* y, long long ys, double alpha,
-                         const GatherEpilogue* epi, const double* blocks, int part) {
+                         const GatherEpilogue* epi, const double* blocks, int part, int lev_step) {
     if (!c || nlev < 0) return MIMSEM_ERR_ARG;
     // interior / boundary split: only the wave-level form with marked halo slots really splits; everything else runs whole as
     // "the boundary part" and has nothing left for "the interior part", so callers can always issue both
@@ -1352,7 +1363,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
     if (nlev == 0 || c->nEl == 0) return MIMSEM_OK;       // empty batch: nothing to do (pointers of empty arrays may be null)
     if (!x || !y) return MIMSEM_ERR_ARG;
     if (cf >= 0 && !f) return MIMSEM_ERR_ARG;
-    if (geom_lev0 < 0 || geom_lev0 + nlev > c->nk) return MIMSEM_ERR_ARG;
+    if (geom_lev0 < 0 || geom_lev0 + (lev_step ? nlev : 1) > c->nk) return MIMSEM_ERR_ARG;
     if (op == MIMSEM_OP_UTMAT && geom_lev0 + nlev > c->nk - 1) return MIMSEM_ERR_ARG;   // needs thick[lev+1]
     if (nlev == 0 || c->nEl == 0) return MIMSEM_OK;
     if (op == MIMSEM_OP_WMATINV || op == MIMSEM_OP_WHMATINV)
@@ -1368,6 +1379,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
     if (in == 3 && !c->d_iq) return MIMSEM_ERR_STATE;     // projection operators need mimsem_mesh_desc::indsq
     a.f = f; a.fs = fs; a.x = x; a.xs = xs;
     a.f2 = f2; a.f2s = f2s; a.param = param; a.xn = c->d_xn;
+    a.lstep = lev_step;                 // 0 (mimsem_op_apply_levels): the forms below that walk consecutive levels are passed over
     {
         a.lch = level_chunk(c, nlev);
         a.swz = 0;   // pass 1: the natural order already keeps all level-chunks of an element on one XCD (profiles/r01_swizzle_ab.txt)
@@ -1381,7 +1393,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
         // is four DPP stages for 9 values); Whmat +3 %, WtQUmat +14 % (profiles/r02_wave_ab.txt).  MIMSEM_WAVE2=2 includes Wmat, 0 none.
         const bool wave2_op = (op == MIMSEM_OP_WMAT && c->wave2_mode == 2) || op == MIMSEM_OP_WHMAT || op == MIMSEM_OP_WTQUMAT || op == MIMSEM_OP_WTQDUDZ;
         const bool fits = (long long)c->n1 < (1LL << 28) && (long long)c->n2 < (1LL << 28) && (long long)c->nEl*es.mp12 < (1LL << 28);
-        if (c->wave1 && es.n == 3 && wave2_op && fits && part == 0 && c->wave2_mode != 0) {
+        if (c->wave1 && es.n == 3 && wave2_op && fits && part == 0 && c->wave2_mode != 0 && lev_step == 1) {
             // p = 3: the wave-level kernel of the 2-form-valued operators (no scatter: one launch)
             if ((rc = c->ensure_ye(64))) return rc;
             a.wlane = c->d_wlane; a.wplan = nullptr; a.wgroups = c->w_ngroups; a.wg0 = 0; a.wdump = 0; a.wsing = nullptr; a.wnode = nullptr;
@@ -1416,7 +1428,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
         }
         return launch_gather_epilogue(c, outsp, nlev, src, per, *epi, y, ys);
     }
-    if (outsp == 1 && c->fused1 && op < MIMSEM_OP_UMAT_UP && op != MIMSEM_OP_UMAT_RAY) {
+    if (outsp == 1 && c->fused1 && op < MIMSEM_OP_UMAT_UP && op != MIMSEM_OP_UMAT_RAY && lev_step == 1) {
         // fused path: group-local sums in LDS, complete slots written straight to y, perimeter partials to the workspace
         if ((rc = c->ensure_ye((long long)std::max(c->f_npart, 1)*nlev))) return rc;
         a.fperm = c->d_fperm; a.flid = c->d_flid; a.fslot = c->d_fslot; a.fcnt = c->d_fcnt;
@@ -1431,7 +1443,7 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
     // the wave kernel addresses its rows with 32-bit byte offsets: vectors / metric beyond 4 GB per level stay on the two-pass form
     const bool wave_fits = (long long)c->n1 < (1LL << 28) && (long long)c->n0 < (1LL << 28) && (long long)c->n2 < (1LL << 28) &&
                            (long long)c->nEl*es.mp12 < (1LL << 28);
-    if (c->wave1 && wave_fits && wave_op) {
+    if (c->wave1 && wave_fits && wave_op && lev_step == 1) {
         // wave-level fused path: complete slots straight into y, one partial per perimeter slot into the workspace, perimeter pass
         // owner-computes (Umat at p = 3, a whole apply): one launch; the workspace row keeps only its dump tail (a ragged last chunk)
         const bool own = c->w_own && !splits && op == MIMSEM_OP_UMAT && es.n == 3 && !c->d_tIn && c->w_ntiles == 0;

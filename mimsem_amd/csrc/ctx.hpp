@@ -231,6 +231,7 @@ struct ElemArgs {
     long long* wstamps;              // diagnostic build (MIMSEM_STAMPS): 16 s_memtime stamps per work item, else null
     // direct path: DoFs touched by exactly ONE element are written straight into y (no ye round trip, no pass 2 for them)
     const int *d0, *d1x, *d1y;       // [nEl][n0e|n1e]: the slot when the element is its only contributor, else -1 (null = off)
+    int lstep = 1;                   // geometry level of row r: lev0 + r lstep; 0 = every row at lev0 (mimsem_op_apply_levels, k_elem_apply only)
 };
 
 // The vector update a Chebyshev step still owes (mimsem_block_chebyshev_solve: the gather epilogue of step k folded into the element pass of

@@ -398,7 +398,7 @@ __device__ __forceinline__ void body_elem_apply(const ElemArgs& a, const unsigne
             if constexpr (T::cf2 == S1) { if (us1 >= 0) ng1 = uv[us1]; }
         }
         if (qact) {
-            const size_t gl = (size_t)(a.lev0 + lev)*lstride + gq;
+            const size_t gl = (size_t)(a.lev0 + lev*a.lstep)*lstride + gq;
             ntI = a.tI[gl];
             if constexpr (OP == MIMSEM_OP_UTMAT) { nth0 = a.th[gl]; nth1 = a.th[gl + lstride]; }
         }

@@ -204,6 +204,19 @@ class Engine:
                                      _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0), alpha), "mimsem_op_apply(%s)" % op)
         return y if x.dim() == 2 else y2[0]
 
+    def apply_levels(self, op, x, lev_step, f=None, lev0=0, scale=1.0, flags=0, alpha=1.0, out=None):
+        """mimsem_op_apply_levels: apply() with row r at geometry level lev0 + r lev_step; lev_step 0 (WMAT, UHMAT) evaluates every row
+        at lev0, as HorizSolve::diagVertVort assembles M2 and F"""
+        sin, sf, sout = self._SPACES[op]
+        _need(x.dim() == 2 and x.shape[1] == self.sizes[sin], "x: [nlev, n_in]")
+        nlev = x.shape[0]
+        _need(sf is None or (f is not None and f.shape == (nlev, self.sizes[sf])), "f: one row per row of x")
+        y = out if out is not None else torch.empty(nlev, self.sizes[sout], dtype=torch.float64, device=self.device)
+        check(self.L.mimsem_op_apply_levels(self.ctx, OPS[op], lev0, lev_step, nlev, scale, flags,
+                                            _ptr(f) if sf is not None else None, f.stride(0) if sf is not None else 0,
+                                            _ptr(x), x.stride(0), _ptr(y), y.stride(0), alpha), "mimsem_op_apply_levels(%s)" % op)
+        return y
+
     def set_halo_slots(self, form, slots):
         """mark the 1-form slots that take part in a halo exchange: their element groups move to the front of the plan, so that
         apply_part(..., "boundary") completes exactly those slots (mimsem_ctx_set_halo_slots)"""
@@ -449,6 +462,17 @@ class Engine:
         out = torch.empty(self.nEl, nd, nd, dtype=torch.float64, device=self.device) if out is None else out
         _need(out.shape == (self.nEl, nd, nd) and out.is_contiguous(), "out: a contiguous [nEl, 2 n1e, 2 n1e] tensor")
         check(self.L.mimsem_elem_block_pc_build(self.ctx, OPS[op], lev, scale, flags, _ptr(f), _ptr(out)), "mimsem_elem_block_pc_build(%s)" % op)
+        return out
+
+    def elem_block_pc_levels(self, op, nlev, f=None, lev0=0, lev_step=1, scale=1.0, flags=0, out=None):
+        """mimsem_elem_block_pc_build_levels: the blocks of elem_block_pc for nlev rows in one launch, [nlev, nEl, 2 n1e, 2 n1e]; row r at
+        geometry level lev0 + r lev_step with the field row f[r] (UMAT, UHMAT, UTMAT_H)"""
+        nd = 2 * self.n1e
+        out = torch.empty(nlev, self.nEl, nd, nd, dtype=torch.float64, device=self.device) if out is None else out
+        _need(out.shape == (nlev, self.nEl, nd, nd) and out.is_contiguous(), "out: a contiguous [nlev, nEl, 2 n1e, 2 n1e] tensor")
+        _need(f is None or (f.dim() == 2 and f.shape == (nlev, self.sizes[2]) and f.stride(1) == 1), "f: [nlev, n2] with contiguous rows")
+        check(self.L.mimsem_elem_block_pc_build_levels(self.ctx, OPS[op], lev0, lev_step, nlev, scale, flags, _ptr(f),
+                                                       f.stride(0) if f is not None else 0, _ptr(out)), "mimsem_elem_block_pc_build_levels(%s)" % op)
         return out
 
     def element_matrices_ray(self, exner, exner_s, dt, lev=0, scale=1.0):
