@@ -259,6 +259,21 @@ int mimsem_incidence_apply(mimsem_ctx* ctx, int which, int nlev,
 int mimsem_interp_quad(mimsem_ctx* ctx, int form, unsigned flags, int nlev,
                        const double* x, long long x_stride, double* out, long long out_stride);
 
+/* The four horizontal integrals of Euler::diagnostics (eul/Euler_2.cpp:600-744, the line of output/energetics.dat) over levels
+ * 0 .. nlev-1 in one element pass (csrc/energetics.inc) and a fixed-order final pass; out: DEVICE pointer to 4 doubles
+ *   out[0] keh  = 1/2 sum_k velx_k . F(rho_k, k, const_vert = true) velx_k / SCALE    (:630-636, Uhmat::assemble eul/Assembly.cpp:432-448)
+ *   out[1] ie   = CV/CP sum_k rt_k . M2(k, vert_scale) exner_k / SCALE                (:667-673, Wmat::assemble eul/Assembly.cpp:347-353)
+ *   out[2] entr = 1/2 sum_k theta_k . M2(k, vert_scale) rt_k / SCALE                  (:706-711; theta: diagTheta_L2 in the horizontal layout)
+ *   out[3] mass = sum_k int2(rho_k)                                                   (:570-598, :686-690)
+ * with 1/SCALE and the constant factors applied.  velx: local 1-form rows, the others 2-form rows, one row per level at its own
+ * stride (doubles), as mimsem_op_apply takes them.  Element orders 1..7 (every order a context can have).  Deterministic: no
+ * floating-point atomics, two calls on the same input give the same bits.  No host synchronisation; the partial sums live in the
+ * context's reduction workspace, which grows on the first call only (capturable once warmed up: MIMSEM_ERR_STATE if it had to grow
+ * inside a capture).  A null pointer, a negative stride or nlev outside 1..nk: MIMSEM_ERR_ARG, nothing launched, out untouched.   */
+int mimsem_euler_energetics_horiz(mimsem_ctx* ctx, int nlev, const double* velx, long long ldu, const double* rho, long long ldr,
+                                  const double* rt, long long ldt, const double* exner, long long lde,
+                                  const double* theta, long long ldth, double* out);
+
 /* Row N3: the packed [u,h] operator of the shallow-water Picard step, SWEqn::assemble_operator (src/SWEqn_Picard.cpp:622-725),
  * which the reference forms with MatMatMult / MatGetRow / MatSetValues and hands to KSPSolve(kspA):
  *     y_u = (M1 + a R(f)) u + a g E12 M2 h        y_h = M2 (a H E21 u + h)        a = ROS_ALPHA dt, g = grav, H = H_MEAN

@@ -1,0 +1,160 @@
+// energetics.inc -- mimsem_euler_energetics_horiz (include/mimsem_hip.h): the four horizontal integrals of Euler::diagnostics
+// (eul/Euler_2.cpp:600-744) over all levels in ONE element pass plus a small fixed-order final pass.  Included at the end of
+// elem_kernels.hip, whose lane-per-quadrature-point layout (Dims), LDS-staged edge table and interp_point it shares.
+//
+//   keh  = 1/2 sum_k velx_k . F(rho_k, k, vert) velx_k / SCALE      (:630-636; coefficients Uhmat::assemble eul/Assembly.cpp:432-448)
+//   ie   = CV/CP sum_k rt_k . M2(k, vert) exner_k / SCALE           (:667-673; Wmat::assemble eul/Assembly.cpp:347-353)
+//   entr = 1/2 sum_k theta_k . M2(k, vert) rt_k / SCALE             (:706-711)
+//   mass = sum_k int2(rho_k)                                        (:570-598, :686-690)
+//
+// Every term is a sum over elements of a sum over quadrature points: the 1-form term is the quadratic form sum_e x_e^T A_e x_e (no
+// scatter), 2-forms are discontinuous.  With t = thickInv[k][q], w = w_qx w_qy, d = det[e][q], J = [[a, b], [c, e]] and the LOCAL
+// interpolants (u, v) of velx (before the Piola map, as Uhmat has them) and r, T, P, h of rho, rt, exner, theta at the point:
+//   keh_q = u (caa u + cab v) + v (cab u + cbb v),   caa = (r/d t)(a^2 + c^2) w/d t,  cab = (r/d t)(a b + c e) w/d t,  cbb = (r/d t)(b^2 + e^2) w/d t
+//   ie_q  = T P w/d t        entr_q = h T w/d t        mass_q = d w (r/d)
+// (the SCALE of the assembled matrices and the reference's 1/SCALE cancel).
+//
+// Work item = (level, element) as k_interp_quad numbers them; lane q owns quadrature point q.  A unit reads velx once through the 1-form
+// maps (2 n1e doubles), rho, rt, exner, theta once as contiguous 2-form blocks (4 n2e), J, det, thickInv once (6 mp12): at p = 3
+// 24 + 36 + 96 = 156 doubles = 1 248 bytes, at p = 4 40 + 64 + 150 = 254 doubles = 2 032 bytes.
+//
+// Reduction, no atomics: a block walks its units with a fixed stride and every lane accumulates its own points in that order; the 64
+// lanes of a wave are summed by the shuffle tree (offsets 32, 16, .., 1), the four waves as (w0 + w1) + (w2 + w3), and the block leaves ONE
+// partial 4-vector in the context's reduction workspace.  A second launch of four waves sums the partials of one term each (lane l takes
+// partials l, l + 64, .., then the same tree) and applies the constant factor.  The grid depends on (nEl, nlev, order) only: two calls on
+// the same input give the same bits.
+namespace {
+
+constexpr int EN_MAX_BLOCKS = 2048;      // 8 workgroups of 256 on each of the 256 CUs; more units than that: blocks take several
+
+struct EnergeticsArgs {
+    int nEl, nlev;
+    const int *i1x, *i1y, *i2;
+    const double *J, *det, *tI, *E, *w;
+    const double* u; long long us;
+    const double* rho; long long rs;
+    const double* rt; long long ts;
+    const double* ex; long long es;
+    const double* th; long long hs;
+    double* part;                        // [gridDim.x][4]
+};
+
+__device__ __forceinline__ double en_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void k_energetics_horiz(EnergeticsArgs a) {
+    using D = Dims<N>;
+    constexpr int LPE = D::LPE, EPB = D::EPB;
+    __shared__ double sE[D::mp1*N];
+    __shared__ double s_u[EPB][2*LPE];
+    __shared__ double s_r[EPB][LPE], s_t[EPB][LPE], s_p[EPB][LPE], s_h[EPB][LPE];
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x, el = tid/LPE, q = tid%LPE;
+    const int qx = q%D::mp1, qy = q/D::mp1;
+    if (tid < D::mp1*N) sE[tid] = a.E[tid];
+    const double Q = q < D::mp12 ? a.w[qx]*a.w[qy] : 0.0;
+    const long long total = (long long)a.nEl*a.nlev;
+    const size_t lstride = (size_t)a.nEl*D::mp12;
+    double keh = 0.0, ie = 0.0, en = 0.0, ms = 0.0;
+    __syncthreads();                     // sE (the only block-level barrier of the loop: an element's lanes share a wave)
+    for (long long base = (long long)blockIdx.x*EPB; base < total; base += (long long)gridDim.x*EPB) {      // (block-uniform trip count)
+        const long long eg = base + el;
+        const bool act = eg < total;
+        const int lev = act ? (int)(eg/a.nEl) : 0, e = act ? (int)(eg%a.nEl) : 0;
+        if (act) {
+            if (q < D::n1e) {
+                const double* uv = a.u + (size_t)lev*a.us;
+                s_u[el][q] = uv[a.i1x[e*D::n1e + q]]; s_u[el][D::n1e + q] = uv[a.i1y[e*D::n1e + q]];
+            }
+            if (q < D::n2e) {
+                const size_t s = a.i2 ? (size_t)a.i2[e*D::n2e + q] : (size_t)e*D::n2e + q;
+                s_r[el][q] = a.rho[(size_t)lev*a.rs + s]; s_t[el][q] = a.rt[(size_t)lev*a.ts + s];
+                s_p[el][q] = a.ex[(size_t)lev*a.es + s]; s_h[el][q] = a.th[(size_t)lev*a.hs + s];
+            }
+        }
+        wave_lds_sync();
+        if (act && q < D::mp12) {
+            const size_t gq = (size_t)e*D::mp12 + q;
+            const double* Je = a.J + (size_t)e*4*D::mp12;
+            const double J00 = Je[0*D::mp12 + q], J01 = Je[1*D::mp12 + q], J10 = Je[2*D::mp12 + q], J11 = Je[3*D::mp12 + q];
+            const double det = a.det[gq], tI = a.tI[(size_t)lev*lstride + gq];
+            double u, v, r, T, P, h, dmy;
+            interp_point<N, S1>(s_u[el], sE, q, qx, qy, u, v);
+            interp_point<N, S2>(s_r[el], sE, q, qx, qy, r, dmy);
+            interp_point<N, S2>(s_t[el], sE, q, qx, qy, T, dmy);
+            interp_point<N, S2>(s_p[el], sE, q, qx, qy, P, dmy);
+            interp_point<N, S2>(s_h[el], sE, q, qx, qy, h, dmy);
+            const double sd = 1.0/det;
+            const double rq = r/det;                                  // interp2_g
+            const double hi = rq*tI;
+            const double caa = hi*(J00*J00 + J10*J10)*Q*sd*tI;        // Uhmat::assemble, vert_scale
+            const double cab = hi*(J00*J01 + J10*J11)*Q*sd*tI;
+            const double cbb = hi*(J01*J01 + J11*J11)*Q*sd*tI;
+            const double c2 = Q*sd*tI;                                // Wmat::assemble, vert_scale
+            keh += u*(caa*u + cab*v) + v*(cab*u + cbb*v);
+            ie += T*(c2*P);
+            en += h*(c2*T);
+            ms += det*Q*rq;                                           // int2
+        }
+        wave_lds_sync();                 // the unit's rows are read before the next unit's are stored
+    }
+    const int lane = tid & 63, wave = tid >> 6;
+    keh = en_wave_sum(keh); ie = en_wave_sum(ie); en = en_wave_sum(en); ms = en_wave_sum(ms);
+    if (lane == 0) { red[wave][0] = keh; red[wave][1] = ie; red[wave][2] = en; red[wave][3] = ms; }
+    __syncthreads();
+    if (tid < 4) a.part[(size_t)blockIdx.x*4 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// wave t sums term t of the nb partial 4-vectors in a fixed order and applies its constant factor
+__global__ __launch_bounds__(256) void k_energetics_final(int nb, const double* __restrict__ part, double f0, double f1, double f2, double f3,
+                                                          double* __restrict__ out) {
+    const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
+    double s = 0.0;
+    for (int i = lane; i < nb; i += 64) s += part[(size_t)i*4 + t];
+    s = en_wave_sum(s);
+    if (lane == 0) out[t] = s*(t == 0 ? f0 : (t == 1 ? f1 : (t == 2 ? f2 : f3)));
+}
+
+template <int N>
+int energetics_horiz_n(mimsem_ctx* c, EnergeticsArgs& a, double* out) {
+    using D = Dims<N>;
+    const long long total = (long long)a.nEl*a.nlev;
+    const int nb = (int)std::max<long long>(1, std::min<long long>(EN_MAX_BLOCKS, (total + D::EPB - 1)/D::EPB));
+    const int rc = c->ensure_kry((long long)nb*4);                    // (grows outside a capture only: MIMSEM_ERR_STATE inside one)
+    if (rc) return rc;
+    a.part = c->d_kry;
+    hipLaunchKernelGGL((k_energetics_horiz<N>), dim3(nb), dim3(256), 0, c->stream, a);
+    MIMSEM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_energetics_final, dim3(1), dim3(256), 0, c->stream, nb, (const double*)c->d_kry, 0.5, 717.5/1004.5, 0.5, 1.0, out);      // CV/CP eul/Euler_2.cpp:29-30
+    MIMSEM_HIP_TRY(hipGetLastError());
+    return MIMSEM_OK;
+}
+
+}  // namespace
+
+extern "C" int mimsem_euler_energetics_horiz(mimsem_ctx* c, int nlev, const double* velx, long long ldu, const double* rho, long long ldr,
+                                             const double* rt, long long ldt, const double* exner, long long lde,
+                                             const double* theta, long long ldth, double* out) {
+    if (!c || !velx || !rho || !rt || !exner || !theta || !out) return MIMSEM_ERR_ARG;
+    if (nlev < 1 || nlev > c->nk || ldu < 0 || ldr < 0 || ldt < 0 || lde < 0 || ldth < 0) return MIMSEM_ERR_ARG;
+    if (!c->d_J || !c->d_det || !c->d_tI || !c->d_E || !c->d_w || !c->d_i1x || !c->d_i1y) return MIMSEM_ERR_STATE;
+    EnergeticsArgs a{};
+    a.nEl = c->nEl; a.nlev = nlev;
+    a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2;
+    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.E = c->d_E; a.w = c->d_w;
+    a.u = velx; a.us = ldu; a.rho = rho; a.rs = ldr; a.rt = rt; a.ts = ldt; a.ex = exner; a.es = lde; a.th = theta; a.hs = ldth;
+    switch (c->es.n) {
+    case 1: return energetics_horiz_n<1>(c, a, out);
+    case 2: return energetics_horiz_n<2>(c, a, out);
+    case 3: return energetics_horiz_n<3>(c, a, out);
+    case 4: return energetics_horiz_n<4>(c, a, out);
+    case 5: return energetics_horiz_n<5>(c, a, out);
+    case 6: return energetics_horiz_n<6>(c, a, out);
+    case 7: return energetics_horiz_n<7>(c, a, out);
+    default: return MIMSEM_ERR_UNSUPPORTED;
+    }
+}

@@ -566,6 +566,22 @@ class Engine:
         out = out.view(x2.shape[0], self.nEl, self.mp12, 2) if form == 1 else out.view(x2.shape[0], self.nEl, self.mp12)
         return out if x.dim() == 2 else out[0]
 
+    def energetics_horiz(self, velx, rho, rt, exner, theta, out=None):
+        """mimsem_euler_energetics_horiz: [keh, ie, entr, mass] of Euler::diagnostics (eul/Euler_2.cpp:600-744) over the rows' levels
+        0 .. nlev-1 as a device tensor of 4; velx [nlev, n1], the others [nlev, n2] (rows contiguous, any row stride)"""
+        nlev = velx.shape[0] if velx.dim() == 2 else -1
+        _need(velx.dim() == 2 and velx.shape[1] == self.sizes[1] and velx.stride(1) == 1, "velx: [nlev, n1] with contiguous rows")
+        for t, name in ((rho, "rho"), (rt, "rt"), (exner, "exner"), (theta, "theta")):
+            _need(t.dim() == 2 and t.shape == (nlev, self.sizes[2]) and t.stride(1) == 1, "%s: [nlev, n2] with contiguous rows" % name)
+        out = torch.empty(4, dtype=torch.float64, device=self.device) if out is None else out
+        _need(out.numel() == 4 and out.is_contiguous(), "out: 4 contiguous doubles")
+        for t in (velx, rho, rt, exner, theta):             # (rows may lie apart -- a slice of a wider array -- so not _ptr, which wants one block)
+            _need(t.dtype == torch.float64 and t.is_cuda and (nlev == 1 or t.stride(0) >= 0), "float64 device rows")
+        st = lambda t: t.stride(0) if nlev > 1 else 0
+        check(self.L.mimsem_euler_energetics_horiz(self.ctx, nlev, velx.data_ptr(), st(velx), rho.data_ptr(), st(rho), rt.data_ptr(), st(rt),
+                                                   exner.data_ptr(), st(exner), theta.data_ptr(), st(theta), _ptr(out)), "euler_energetics_horiz")
+        return out
+
     def sw_operator(self, a, grav, H, f0, x, out=None):
         """SWEqn::assemble_operator + MatMult (src/SWEqn_Picard.cpp:622-725) in one element pass: x, y packed rows [u | h]"""
         x2 = x if x.dim() == 2 else x.unsqueeze(0)

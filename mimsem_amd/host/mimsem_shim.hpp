@@ -664,6 +664,19 @@ struct VertSolve {
     Mesh* mesh; double dt;
 };
 
+// Euler (eul/Euler_2.h): the horizontal half of Euler::diagnostics (eul/Euler_2.cpp:600-744) for every level in one call
+struct Euler {
+    Euler(Topo* t, Geom* g) : mesh(Mesh::of(t, g)) {}
+    explicit Euler(Mesh* m) : mesh(m) {}
+    // out (device, 4 doubles): keh, ie, entr, mass of levels 0 .. nk-1; velx [nk][n1], the 2-form fields [nk][n2] (rows at the given strides),
+    // theta = diagTheta_L2 in the horizontal layout.  No host synchronisation.
+    void energetics_horiz(int nk, const double* velx, long long ldu, const double* rho, long long ldr, const double* rt, long long ldt,
+                          const double* exner, long long lde, const double* theta, long long ldth, double* out) const {
+        check(mimsem_euler_energetics_horiz(mesh->ctx, nk, velx, ldu, rho, ldr, rt, ldt, exner, lde, theta, ldth, out), "Euler::energetics_horiz");
+    }
+    Mesh* mesh;
+};
+
 // ---- src/ flavour (shallow water, src/Assembly.h:1-278): no lev / scale arguments, no layer thickness ------------------------------
 namespace src {
 struct Umat : OperatorBase {      // src/Assembly.h:1-13
