@@ -154,6 +154,13 @@ public:
         check(mimsem_malloc(&p, (long long)(n*sizeof(double))), "mimsem_malloc");
         return (double*)p;
     }
+    // out = a A (op: 0 nothing, 1 times, 2 divided by) B + b C on `rows` rows of n doubles (rows > 1: n doubles apart); copy; clear
+    void combine(long long n, double a, const double* A, int op, const double* B, double b, const double* C, double* out, int rows = 1) {
+        const long long ld = rows > 1 ? n : 0;
+        check(mimsem_vec_combine(ctx, rows, n, a, A, ld, op, B, ld, b, C, ld, out, ld), "mimsem_vec_combine");
+    }
+    void copy(long long n, const double* a, double* out) { combine(n, 1.0, a, 0, nullptr, 0.0, nullptr, out); }
+    void zero(long long n, double* a) { check(mimsem_memset(ctx, a, 0, n*(long long)sizeof(double)), "mimsem_memset"); }
     // Geom::interp0 / interp1_l / interp1_g / interp2_l / interp2_g (eul/Geom.cpp:328-417) for EVERY quadrature point of the patch:
     // x = device pointer to the local k-form array the reference passes (VecGetArray of the `*l` Vec); out [nEl][mp12] ([..][2] for 1-forms)
     void interp0(const double* x, double* out) const { check(mimsem_interp_quad(ctx, 0, 0, 1, x, 0, out, 0), "interp0"); }

@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
-#include "mimsem_shim.hpp"
+#include "mimsem_mass.hpp"
 
 namespace mimsem_host {
 
@@ -31,19 +31,16 @@ public:
     VertSolveEta(Mesh* m, double dt_) : mesh(m), dt(dt_) {
         nEl = m->nEl_; n2 = m->n2e; nk = m->nk_;
         nl = (size_t)nEl*nk*n2; ni = (size_t)nEl*(nk - 1)*n2; nt = (size_t)nEl*(nk + 1)*n2;
-        try {
-            for (double** p : {&velz_j, &velz_h, &F_w, &d_w, &k2i}) *p = mesh->device_alloc(ni);
-            for (double** p : {&rho_j, &rt_j, &exner_j, &rho_h, &rt_h, &exner_h, &theta_l2_i, &theta_l2_h, &F_rho, &F_eta, &F_exner, &d_rho, &d_eta, &d_exner,
-                               &th_w3, &eta, &add_rho, &add_rt, &ones}) *p = mesh->device_alloc(nl);
-            for (double** p : {&theta_i, &theta_h}) *p = mesh->device_alloc(nt);
-            nrm = mesh->device_alloc(8*nl); sums = mesh->device_alloc((size_t)8*nEl);
-            // a row of ones: the column sums of the update's squares are row dots with it
-            check(mimsem_memset(mesh->ctx, th_w3, 0, (long long)nl*8), "mimsem_memset");
-            std::vector<double> one((size_t)nk*n2, 1.0);
-            check(mimsem_memcpy_h2d(mesh->ctx, ones, one.data(), (long long)one.size()*8), "h2d");
-        } catch (...) { release(); throw; }
+        for (double** p : {&velz_j, &velz_h, &F_w, &d_w, &k2i}) *p = mem.get(ni);
+        for (double** p : {&rho_j, &rt_j, &exner_j, &rho_h, &rt_h, &exner_h, &theta_l2_i, &theta_l2_h, &F_rho, &F_eta, &F_exner, &d_rho, &d_eta, &d_exner,
+                           &th_w3, &eta, &add_rho, &add_rt, &ones}) *p = mem.get(nl);
+        for (double** p : {&theta_i, &theta_h}) *p = mem.get(nt);
+        nrm = mem.get(8*nl); sums = mem.get((size_t)8*nEl);
+        // a row of ones: the column sums of the update's squares are row dots with it
+        mesh->zero((long long)nl, th_w3);
+        std::vector<double> one((size_t)nk*n2, 1.0);
+        check(mimsem_memcpy_h2d(mesh->ctx, ones, one.data(), (long long)one.size()*8), "h2d");
     }
-    ~VertSolveEta() { release(); }
     VertSolveEta(const VertSolveEta&) = delete; VertSolveEta& operator=(const VertSolveEta&) = delete;
 
     // VertSolve::solve_schur_eta: velz / rho / rt / exner at the old time level in, at the new one out (in place); zv from VertSolve::initGZ.
@@ -52,10 +49,10 @@ public:
     int solve_schur_eta(double* velz, double* rho, double* rt, double* exner, const double* zv, int maxit = 20, double tol = 1.0e-12,
                         const double* udwdx = nullptr, const double* hs_lat = nullptr) {
         mimsem_ctx* c = mesh->ctx;
-        copy(velz_j, velz, ni); copy(rho_j, rho, nl); copy(rt_j, rt, nl); copy(exner_j, exner, nl);
+        mesh->copy(ni, velz, velz_j); mesh->copy(nl, rho, rho_j); mesh->copy(nl, rt, rt_j); mesh->copy(nl, exner, exner_j);
         check(mimsem_column_diag_theta_blend(c, rho, rt, theta_i, nullptr, theta_l2_i, nullptr, 1.0, 0.0), "diag_theta_blend");        // diagTheta2 :1766, diagTheta_L2 :1773
-        copy(theta_h, theta_i, nt); copy(theta_l2_h, theta_l2_i, nl);
-        copy(exner_h, exner, nl); copy(velz_h, velz, ni); copy(rho_h, rho, nl); copy(rt_h, rt, nl);
+        mesh->copy(nt, theta_i, theta_h); mesh->copy(nl, theta_l2_i, theta_l2_h);
+        mesh->copy(nl, exner, exner_h); mesh->copy(ni, velz, velz_h); mesh->copy(nl, rho, rho_h); mesh->copy(nl, rt, rt_h);
         history.clear();
         int it = 0;
         for (it = 1; it <= maxit; it++) {
@@ -90,7 +87,7 @@ public:
             if (allreduce_sum) allreduce_sum(&s, 1);
             k2i_z = s/1.0e8;
         }
-        copy(velz, velz_j, ni); copy(rho, rho_j, nl); copy(rt, rt_j, nl); copy(exner, exner_j, nl);
+        mesh->copy(ni, velz_j, velz); mesh->copy(nl, rho_j, rho); mesh->copy(nl, rt_j, rt); mesh->copy(nl, exner_j, exner);
         return std::min(it, maxit);
     }
     const double* theta_half() const { return theta_h; }          // [nEl][(nk+1)*n2e]
@@ -98,26 +95,19 @@ public:
     const double* exner_half() const { return exner_h; }
 
 private:
-    Mesh* mesh; double dt;
+    Mesh* mesh; double dt; DeviceArrays mem;
     int nEl = 0, n2 = 0, nk = 0; size_t nl = 0, ni = 0, nt = 0;
-    double *velz_j = nullptr, *velz_h = nullptr, *F_w = nullptr, *d_w = nullptr, *k2i = nullptr;
-    double *rho_j = nullptr, *rt_j = nullptr, *exner_j = nullptr, *rho_h = nullptr, *rt_h = nullptr, *exner_h = nullptr, *theta_l2_i = nullptr, *theta_l2_h = nullptr,
-           *F_rho = nullptr, *F_eta = nullptr, *F_exner = nullptr, *d_rho = nullptr, *d_eta = nullptr, *d_exner = nullptr, *th_w3 = nullptr, *eta = nullptr,
-           *add_rho = nullptr, *add_rt = nullptr, *ones = nullptr;
-    double *theta_i = nullptr, *theta_h = nullptr, *nrm = nullptr, *sums = nullptr, *ones_i = nullptr;
-    void copy(double* dst, const double* src, size_t n) { check(mimsem_vec_combine(mesh->ctx, 1, (long long)n, 1.0, src, 0, 0, nullptr, 0, 0.0, nullptr, 0, dst, 0), "vec_combine"); }
+    double *velz_j, *velz_h, *F_w, *d_w, *k2i;
+    double *rho_j, *rt_j, *exner_j, *rho_h, *rt_h, *exner_h, *theta_l2_i, *theta_l2_h, *F_rho, *F_eta, *F_exner, *d_rho, *d_eta, *d_exner, *th_w3, *eta, *add_rho, *add_rt, *ones;
+    double *theta_i, *theta_h, *nrm, *sums, *ones_i = nullptr;
     // a vector of ones as long as an interface field (for the sum of k2i): built on first use
     const double* onesi() {
         if (!ones_i) {
-            ones_i = mesh->device_alloc(ni);
+            ones_i = mem.get(ni);
             std::vector<double> one(ni, 1.0);
             check(mimsem_memcpy_h2d(mesh->ctx, ones_i, one.data(), (long long)ni*8), "h2d");
         }
         return ones_i;
-    }
-    void release() {
-        for (double** p : {&velz_j, &velz_h, &F_w, &d_w, &k2i, &rho_j, &rt_j, &exner_j, &rho_h, &rt_h, &exner_h, &theta_l2_i, &theta_l2_h, &F_rho, &F_eta, &F_exner,
-                           &d_rho, &d_eta, &d_exner, &th_w3, &eta, &add_rho, &add_rt, &ones, &theta_i, &theta_h, &nrm, &sums, &ones_i}) { if (*p) mimsem_free(*p); *p = nullptr; }
     }
 };
 

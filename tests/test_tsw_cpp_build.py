@@ -1,5 +1,6 @@
 """CPU checks of the thermal shallow-water C++ host and its preconditioner builder (no GPU needed): mimsem_amd/host/mimsem_thermalsw.hpp with
-tests/cpp/test_tsw.cpp and mimsem_amd/host/tsw_call.cpp compile and link with plain g++ against the built library, the library exports
+tests/cpp/test_tsw.cpp and mimsem_amd/host/tsw_call.cpp -- and every other C++ host on the shared pieces of mimsem_mass.hpp -- compile and link
+with plain g++ against the built library, the library exports
 mimsem_elem_block_pc_build, and the builder's kernel (k_elem_block_pc, csrc/elem_block_pc.inc) uses no scratch at any built order."""
 import os
 import re
@@ -29,6 +30,19 @@ def _build(tmp, src, name):
 def test_host_and_call_sites_compile_and_link(tmp_path, lib_path):
     assert os.path.exists(_build(str(tmp_path), os.path.join(ROOT, "tests", "cpp", "test_tsw.cpp"), "test_tsw"))
     assert os.path.exists(_build(str(tmp_path), os.path.join(ROOT, "mimsem_amd", "host", "tsw_call.cpp"), "tsw_call"))
+
+
+def test_every_host_compiles_on_the_shared_mass_pieces(tmp_path, lib_path):
+    """mimsem_mass.hpp through all four host headers (-Wall -Werror): the call programs of SWEqn, HorizSolve, VertSolveEta and ThermalSW_EEC_2
+    (above) and the driver of the shared pieces on their own; no host keeps a release() list or a constructor try / catch"""
+    host = os.path.join(ROOT, "mimsem_amd", "host")
+    for name in ("mimsem_sweqn.hpp", "mimsem_horizsolve.hpp", "mimsem_thermalsw.hpp", "mimsem_vertsolve.hpp"):
+        text = open(os.path.join(host, name)).read()
+        assert '#include "mimsem_mass.hpp"' in text, name
+        assert "release()" not in text and "catch (...) { release" not in text, name
+    for name in ("sw_call", "horiz_call", "vert_call"):
+        assert os.path.exists(_build(str(tmp_path), os.path.join(host, name + ".cpp"), name))
+    assert os.path.exists(_build(str(tmp_path), os.path.join(ROOT, "tests", "cpp", "test_mass.cpp"), "test_mass"))
 
 
 def test_builder_symbol_exported(lib_path):
