@@ -90,6 +90,11 @@ enum mimsem_op {
     /* Held-Suarez boundary-layer friction (mimsem_op_apply_up: f = exner at the level, u = exner at level 0 with
      * u_stride = 0, tau = dt; both 2-forms in the horizontal layout) */
     MIMSEM_OP_UMAT_RAY = 22,  /* Umat_ray::assemble(lev,scale,dt,exner_k,exner_s) Assembly.cpp:1876-1979    1 -> 1 */
+    /* M1 + M1ray(tau) as ONE operator: the matrix the horizontal momentum update solves with under Held-Suarez forcing
+     * (M1->assemble(kk, SCALE, true); MatAXPY(M1->M, 1.0, M1ray->M), eul/Euler_2.cpp:1431-1451).  Umat_ray::assemble
+     * (Assembly.cpp:1876-1979) is Umat::assemble with each point's weight times dt k_v(q), so the sum is Umat with the weight
+     * thickInv (1 + tau k_v(q)): always thickness-scaled (MIMSEM_FLAG_VERT is implied).  Arguments as MIMSEM_OP_UMAT_RAY. */
+    MIMSEM_OP_UMAT_FRIC = 23, /* Umat::assemble(lev,scale,true) + Umat_ray::assemble(lev,scale,tau,exner_k,exner_s)  1 -> 1 */
     /* projections from the quadrature-point grid (initial conditions, Coriolis): x lives on the quad grid */
     MIMSEM_OP_WTQ = 16,      /* WtQmat::assemble  Assembly.cpp:707-751   quad scalar -> 2-form                        */
     MIMSEM_OP_PTQ = 17,      /* PtQmat::assemble  :766-808               quad scalar -> 0-form                        */
@@ -217,8 +222,8 @@ int mimsem_op_elmat_size(const mimsem_ctx* ctx, int op);
 int mimsem_op_element_matrices(mimsem_ctx* ctx, int op, int geom_lev, double scale, unsigned flags,
                                const double* f, double* out);
 
-/* Element blocks of the operators that take a second field (today: MIMSEM_OP_UMAT_RAY, f = exner_k, u = exner_s,
- * tau = dt) -- what MatAXPY(M1->M, 1.0, M1ray->M) needs (eul/Euler_2.cpp:1448).                  */
+/* Element blocks of the operators that take a second field (MIMSEM_OP_UMAT_RAY and MIMSEM_OP_UMAT_FRIC, f = exner_k,
+ * u = exner_s, tau = dt) -- what MatAXPY(M1->M, 1.0, M1ray->M) needs, resp. its result (eul/Euler_2.cpp:1448). */
 int mimsem_op_element_matrices_ex(mimsem_ctx* ctx, int op, int geom_lev, double scale, double tau, unsigned flags,
                                   const double* f, const double* u, double* out);
 
@@ -338,6 +343,22 @@ int mimsem_block_chebyshev_solve(mimsem_ctx* ctx, int op, int geom_lev0, int nle
                                  const double* elem_scale, long long elem_scale_stride,
                                  const double* b, long long b_stride, int nsteps, const double* coef,
                                  double* x, long long x_stride, double* pb, long long pb_stride, double* upd, long long upd_stride);
+
+/* mimsem_block_chebyshev_solve for  (M1 + M1ray(tau)) x = b  from x = 0: the solve that ends stages 1 and 3 of Euler::Strang_ec under
+ * Held-Suarez forcing (KSPSolve(ksp1, bu, velx[kk]) after MatAXPY(M1->M, 1.0, M1ray->M), eul/Euler_2.cpp:1431-1456, :1477-1492).  The element
+ * pass of each step is MIMSEM_OP_UMAT_FRIC -- one pass, not Umat followed by an accumulated Umat_ray.  exner: 2-form rows of the nlev levels
+ * (exner_stride doubles apart), exner_s: the row of level 0 (Umat_ray's exner_s).  blocks / elem_scale are those of M1 alone: the weights of
+ * the two operators differ pointwise by a factor in [1, 1 + tau K_F], K_F = 1.1574074074074073e-05, so spec(P (M1 + M1ray)) lies in
+ * [lmin, (1 + tau K_F) lmax] when spec(P M1) lies in [lmin, lmax], and the caller's coef come from that interval (mimsem_amd/krylov.py
+ * friction_interval).  First-step rule, pb / upd, order limit (<= 5) and capturability as mimsem_block_chebyshev_solve.  op must be
+ * MIMSEM_OP_UMAT and flags MIMSEM_FLAG_VERT (the reference assembles M1 with vert_scale = true here).  tau == 0 or exner == NULL IS
+ * mimsem_block_chebyshev_solve (the same launches, the same bits); with exner given, exner_s is required. */
+int mimsem_fric_chebyshev_solve(mimsem_ctx* ctx, int op, int geom_lev0, int nlev, double scale, unsigned flags,
+                                const double* f, long long f_stride, const double* blocks,
+                                const double* elem_scale, long long elem_scale_stride,
+                                const double* b, long long b_stride, int nsteps, const double* coef,
+                                double* x, long long x_stride, double* pb, long long pb_stride, double* upd, long long upd_stride,
+                                double tau, const double* exner, long long exner_stride, const double* exner_s);
 
 /* The reference's PCBJACOBI itself: every mass solve runs GMRES + PCBJACOBI with PCBJacobiSetTotalBlocks(size*nElsX*nElsX) (ksp1,
  * eul/HorizSolve.cpp:77-96; ksp, ksp0, ksp0h, src/SWEqn_Picard.cpp:85-113).  PETSc cuts the global numbering into equal contiguous chunks,

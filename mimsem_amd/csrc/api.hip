@@ -668,7 +668,7 @@ int op_spaces(int op, int* in, int* cf, int* out) {
     case MIMSEM_OP_PHMAT_UP:  *in = 0; *cf = 2; *out = 0; return 0;
     case MIMSEM_OP_ROTMAT_UP: *in = 1; *cf = 0; *out = 1; return 0;
     case MIMSEM_OP_UMAT_UP:   *in = 1; *cf = 1; *out = 1; return 0;
-    case MIMSEM_OP_UHMAT_UP: case MIMSEM_OP_UVEC_HU_UP: case MIMSEM_OP_UMAT_RAY: *in = 1; *cf = 2; *out = 1; return 0;
+    case MIMSEM_OP_UHMAT_UP: case MIMSEM_OP_UVEC_HU_UP: case MIMSEM_OP_UMAT_RAY: case MIMSEM_OP_UMAT_FRIC: *in = 1; *cf = 2; *out = 1; return 0;
     }
     return 1;
 }
@@ -1305,7 +1305,7 @@ int mimsem_op_apply_levels(mimsem_ctx* c, int op, int geom_lev0, int geom_lev_st
 
 static bool is_up_op(int op) {
     return op == MIMSEM_OP_PHMAT_UP || op == MIMSEM_OP_ROTMAT_UP || op == MIMSEM_OP_UMAT_UP || op == MIMSEM_OP_UHMAT_UP ||
-           op == MIMSEM_OP_UVEC_HU_UP || op == MIMSEM_OP_UMAT_RAY;
+           op == MIMSEM_OP_UVEC_HU_UP || op == MIMSEM_OP_UMAT_RAY || op == MIMSEM_OP_UMAT_FRIC;
 }
 int mimsem_ctx_set_halo_slots(mimsem_ctx* c, int form, const int* slots, int n) {
     if (!c || form != 1 || n < 0 || (n && !slots)) return MIMSEM_ERR_ARG;
@@ -1546,6 +1546,7 @@ int mimsem_op_elmat_size(const mimsem_ctx* c, int op) {
     const ElemSizes& es = c->es;
     switch (op) {
     case MIMSEM_OP_UMAT: case MIMSEM_OP_UHMAT: case MIMSEM_OP_UTMAT: case MIMSEM_OP_UTMAT_H: case MIMSEM_OP_UMAT_RAY:
+    case MIMSEM_OP_UMAT_FRIC:
         return 4*es.n1e*es.n1e;
     case MIMSEM_OP_ROTMAT: return 2*es.n1e*es.n1e;
     case MIMSEM_OP_WMAT: case MIMSEM_OP_WHMAT: case MIMSEM_OP_WMATINV: case MIMSEM_OP_WHMATINV: return es.n2e*es.n2e;
@@ -1558,7 +1559,7 @@ int mimsem_op_elmat_size(const mimsem_ctx* c, int op) {
 int mimsem_op_element_matrices_ex(mimsem_ctx* c, int op, int geom_lev, double scale, double tau, unsigned flags,
                                   const double* f, const double* u, double* out) {
     if (!c || !out || !f || !u) return MIMSEM_ERR_ARG;
-    if (op != MIMSEM_OP_UMAT_RAY) return MIMSEM_ERR_ARG;
+    if (op != MIMSEM_OP_UMAT_RAY && op != MIMSEM_OP_UMAT_FRIC) return MIMSEM_ERR_ARG;
     if (geom_lev < 0 || geom_lev >= c->nk) return MIMSEM_ERR_ARG;
     return launch_elmats(c, op, geom_lev, scale, flags, f, out, u, tau);
 }
@@ -1701,20 +1702,23 @@ int mimsem_block_chebyshev_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev,
 // EXPERIMENT (experiments build, MIMSEM_CHEB_PEND=1): two launches per step -- the gather epilogue of step k folded into the element pass of
 // step k + 1 (body_elem_apply<..., PEND>), x and p alternating between two buffers.  Bit-equal and SLOWER (8.22 against 7.07 ms per HorizSolve
 // evaluation): the folded update turns the epilogue's coalesced slot-order accesses into 96 gathers per unit on 12 of 32 lanes.
-int mimsem_block_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
-                                 const double* f, long long fs, const double* blocks, const double* elem_scale, long long es_stride,
-                                 const double* b, long long bs, int nsteps, const double* coef,
-                                 double* x, long long xs, double* pb, long long pbs, double* upd, long long upds) {
+}  // extern "C"
+
+// eop: the operator of the element pass -- MIMSEM_OP_UMAT, or MIMSEM_OP_UMAT_FRIC with its two exner fields and tau (mimsem_fric_chebyshev_solve)
+static int block_chebyshev_solve_core(mimsem_ctx* c, int op, int eop, int geom_lev0, int nlev, double scale, unsigned flags,
+                                      const double* ef, long long efs, const double* ef2, double tau,
+                                      const double* blocks, const double* elem_scale, long long es_stride,
+                                      const double* b, long long bs, int nsteps, const double* coef,
+                                      double* x, long long xs, double* pb, long long pbs, double* upd, long long upds) {
     if (!c || nlev < 0 || nsteps < 1 || !coef || (flags & ~MIMSEM_FLAG_VERT)) return MIMSEM_ERR_ARG;
     if (op != MIMSEM_OP_UMAT) return MIMSEM_ERR_UNSUPPORTED;
     if (c->es.n > 5) return MIMSEM_ERR_UNSUPPORTED;
     if (nlev == 0 || c->nEl == 0) return MIMSEM_OK;
     if (!b || !blocks || !x || x == b || geom_lev0 < 0 || geom_lev0 + nlev > c->nk) return MIMSEM_ERR_ARG;
     if (nlev > 1 && (xs < c->n1 || bs < c->n1 || (pb && pbs < c->n1) || (upd && upds < c->n1))) return MIMSEM_ERR_ARG;
-    (void)f; (void)fs;
     const ElemSizes& es = c->es;
     const long long per = (long long)c->nEl*2*es.n1e, n1 = c->n1;
-    const bool pend = kExperiments && c->cheb_pend && nsteps > 1;
+    const bool pend = kExperiments && c->cheb_pend && nsteps > 1 && eop == MIMSEM_OP_UMAT;      // (the owed update rides in Umat's element pass only)
     int rc;
     if ((rc = c->ensure_ye(per*nlev*2))) return rc;
     if ((rc = c->ensure_cheb((pend ? 3 : 1)*n1*nlev))) return rc;
@@ -1725,7 +1729,7 @@ int mimsem_block_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev,
     a.flags = flags; a.scale = scale; a.alpha = 1.0;
     a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;
     a.i0 = c->d_i0; a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2; a.iq = c->d_iq;
-    a.f = nullptr; a.fs = 0; a.f2 = nullptr; a.f2s = 0; a.param = 0.0; a.xn = c->d_xn;
+    a.f = ef; a.fs = efs; a.f2 = ef2; a.f2s = 0; a.param = tau; a.xn = c->d_xn;
     a.lch = level_chunk(c, nlev); a.swz = 0;
     a.fperm = nullptr; a.accum = 0; a.d0 = a.d1x = a.d1y = nullptr; a.y = nullptr; a.ys = 0;
     a.out = ye; a.os = per;
@@ -1739,7 +1743,7 @@ int mimsem_block_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev,
         for (int k = 0; k < nsteps; k++) {
             if (k > 0) {
                 a.x = x; a.xs = xs;
-                if ((rc = launch_elem_apply(c, MIMSEM_OP_UMAT, a))) return rc;
+                if ((rc = launch_elem_apply(c, eop, a))) return rc;
                 if ((rc = launch_blocks_residual(c, nlev, blocks, ye, per, b, bs, ze, per, elem_scale, es_stride))) return rc;
             }
             g.alpha = coef[2*k]; g.beta = coef[2*k + 1]; g.zero = k == 0;
@@ -1771,6 +1775,32 @@ int mimsem_block_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev,
     g.upd = upd; g.us = upds;
     g.alpha = coef[2*(nsteps - 1)]; g.beta = coef[2*(nsteps - 1) + 1]; g.p = P[cur]; g.ps = n1;
     return launch_gather_epilogue(c, 1, nlev, ze, per, g, X[cur], XS[cur]);
+}
+
+extern "C" {
+
+int mimsem_block_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
+                                 const double* f, long long fs, const double* blocks, const double* elem_scale, long long es_stride,
+                                 const double* b, long long bs, int nsteps, const double* coef,
+                                 double* x, long long xs, double* pb, long long pbs, double* upd, long long upds) {
+    (void)f; (void)fs;
+    return block_chebyshev_solve_core(c, op, MIMSEM_OP_UMAT, geom_lev0, nlev, scale, flags, nullptr, 0, nullptr, 0.0, blocks, elem_scale, es_stride,
+                                      b, bs, nsteps, coef, x, xs, pb, pbs, upd, upds);
+}
+
+// (M1 + M1ray(tau)) x = b, Euler_2.cpp:1431-1456: the same sweep with MIMSEM_OP_UMAT_FRIC as its element pass -- x, thickInv and the metric are
+// read once per step, plus the two exner rows.  Without friction (tau == 0 or no exner) it IS the entry above.
+int mimsem_fric_chebyshev_solve(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
+                                const double* f, long long fs, const double* blocks, const double* elem_scale, long long es_stride,
+                                const double* b, long long bs, int nsteps, const double* coef,
+                                double* x, long long xs, double* pb, long long pbs, double* upd, long long upds,
+                                double tau, const double* exner, long long exner_stride, const double* exner_s) {
+    if (tau == 0.0 || !exner)
+        return mimsem_block_chebyshev_solve(c, op, geom_lev0, nlev, scale, flags, f, fs, blocks, elem_scale, es_stride, b, bs, nsteps, coef,
+                                            x, xs, pb, pbs, upd, upds);
+    if (!c || flags != MIMSEM_FLAG_VERT || !exner_s || !(tau > 0.0) || (nlev > 1 && exner_stride < c->n2)) return MIMSEM_ERR_ARG;
+    return block_chebyshev_solve_core(c, op, MIMSEM_OP_UMAT_FRIC, geom_lev0, nlev, scale, flags, exner, exner_stride, exner_s, tau, blocks, elem_scale,
+                                      es_stride, b, bs, nsteps, coef, x, xs, pb, pbs, upd, upds);
 }
 
 int mimsem_sw_operator_precond_apply(mimsem_ctx* c, int nlev, double a, double grav, double H, const double* f0, long long f0s,

@@ -37,7 +37,9 @@ template <int OP> struct OpTraits;
         static constexpr int tup = (op == MIMSEM_OP_UMAT_UP) ? 1 : (op == MIMSEM_OP_UVEC_HU_UP ? 2 : (op == MIMSEM_OP_UHMAT_UP ? 3 : 0)); \
         static constexpr bool up = (op == MIMSEM_OP_PHMAT_UP || op == MIMSEM_OP_ROTMAT_UP) || tup != 0; \
         /* second coefficient field: the velocity of the upwinded operators, the surface Exner pressure of Umat_ray */ \
-        static constexpr Space cf2 = up ? S1 : (op == MIMSEM_OP_UMAT_RAY ? S2 : SN); }
+        /* Held-Suarez friction: the coefficient needs exner at the level (f) and at level 0 (second field), and thickInv of level 0 */ \
+        static constexpr bool hs = (op == MIMSEM_OP_UMAT_RAY || op == MIMSEM_OP_UMAT_FRIC); \
+        static constexpr Space cf2 = up ? S1 : (hs ? S2 : SN); }
 MIMSEM_TRAIT(MIMSEM_OP_UMAT,    S1, SN, S1);
 MIMSEM_TRAIT(MIMSEM_OP_WMAT,    S2, SN, S2);
 MIMSEM_TRAIT(MIMSEM_OP_UHMAT,   S1, S2, S1);
@@ -59,13 +61,14 @@ MIMSEM_TRAIT(MIMSEM_OP_UVEC_HU_UP, S1, S2, S1);   // f = rho, second field vel2
 MIMSEM_TRAIT(MIMSEM_OP_PHMAT_UP,  S0, S2, S0);   // + velocity (1-form) as second field
 MIMSEM_TRAIT(MIMSEM_OP_ROTMAT_UP, S1, S0, S1);   // + velocity (1-form) as second field
 MIMSEM_TRAIT(MIMSEM_OP_UMAT_RAY,  S1, S2, S1);   // f = exner at the level, second field = exner at level 0 (both 2-forms)
+MIMSEM_TRAIT(MIMSEM_OP_UMAT_FRIC, S1, S2, S1);   // Umat (vertical flag) + Umat_ray in one pass: the same two fields
 
 // ---- per-quadrature-point coefficient: the fused restatement of each assemble()'s Q?? loop --------
 // in : interpolated input (u,v for a 1-form, h for a 0/2-form in .u)
 // out: a,b = the two flux components to project (1-form out) or a = scalar to project (0/2-form out)
 struct QPoint {
     double J00, J01, J10, J11, det, Q, tI, th0, th1;
-    double tI0, param;          // Umat_ray: thickInv of level 0, dt
+    double tI0, param;          // Umat_ray, Umat_fric: thickInv of level 0, dt
 };
 
 // Held-Suarez boundary-layer friction rate, compute_k_v eul/Assembly.cpp:1845-1856
@@ -87,8 +90,19 @@ __device__ __forceinline__ void qpoint_op(const QPoint& g, double scale, unsigne
     const double sd = scale/g.det;
     const bool vert = (flags & MIMSEM_FLAG_VERT) != 0;
     if constexpr (OP == MIMSEM_OP_UMAT || OP == MIMSEM_OP_UHMAT || OP == MIMSEM_OP_UTMAT || OP == MIMSEM_OP_UTMAT_H ||
-                  OP == MIMSEM_OP_UMAT_UP || OP == MIMSEM_OP_UHMAT_UP || OP == MIMSEM_OP_UVEC_HU_UP || OP == MIMSEM_OP_UMAT_RAY) {
+                  OP == MIMSEM_OP_UMAT_UP || OP == MIMSEM_OP_UHMAT_UP || OP == MIMSEM_OP_UVEC_HU_UP || OP == MIMSEM_OP_UMAT_RAY ||
+                  OP == MIMSEM_OP_UMAT_FRIC) {
         double caa, cab, cbb;
+        if constexpr (OP == MIMSEM_OP_UMAT_FRIC) {                   // M1 + M1ray, Euler_2.cpp:1431-1451: Umat (:99-113, vert_scale) whose point
+            caa = (g.J00*g.J00 + g.J10*g.J10)*g.Q*sd;                //  weight carries 1 + dt k_v (Umat_ray :1913-1933); k_v = 0 leaves Umat's bits
+            cab = (g.J00*g.J01 + g.J10*g.J11)*g.Q*sd;
+            cbb = (g.J01*g.J01 + g.J11*g.J11)*g.Q*sd;
+            caa *= g.tI; cab *= g.tI; cbb *= g.tI;
+            double ek = fu/g.det, es = fv/g.det;
+            ek *= g.tI; es *= g.tI0;
+            const double wf = 1.0 + g.param*hs_k_v(ek, es);
+            caa *= wf; cab *= wf; cbb *= wf;
+        } else
         if constexpr (OP == MIMSEM_OP_UMAT_RAY) {                    // Umat_ray::assemble Assembly.cpp:1913-1933 (fu = exner_k, fv = exner_s)
             caa = (g.J00*g.J00 + g.J10*g.J10)*g.Q*sd;
             cab = (g.J00*g.J01 + g.J10*g.J11)*g.Q*sd;
@@ -333,7 +347,7 @@ __device__ __forceinline__ void body_elem_apply(const ElemArgs& a, const unsigne
     g.J00 = g.J01 = g.J10 = g.J11 = 0.0; g.det = 1.0; g.Q = 0.0; g.tI = 1.0; g.th0 = g.th1 = 1.0;
     g.tI0 = 1.0; g.param = a.param;
     if (qact) {
-        if constexpr (OP == MIMSEM_OP_UMAT_RAY) g.tI0 = a.tI[(size_t)e*D::mp12 + q];
+        if constexpr (T::hs) g.tI0 = a.tI[(size_t)e*D::mp12 + q];
         const double* Je = a.J + (size_t)e*4*D::mp12;
         g.J00 = Je[0*D::mp12 + q]; g.J01 = Je[1*D::mp12 + q];
         g.J10 = Je[2*D::mp12 + q]; g.J11 = Je[3*D::mp12 + q];
@@ -419,7 +433,7 @@ __device__ __forceinline__ void body_elem_apply(const ElemArgs& a, const unsigne
             double u, v, fu = 0.0, fv = 0.0;
             interp_point<N, T::in>(s_x[el], sE, q, qx, qy, u, v);
             if constexpr (T::cf != SN) interp_point<N, T::cf>(s_f[el], sE, q, qx, qy, fu, fv);
-            if constexpr (OP == MIMSEM_OP_UMAT_RAY) { double dmy; interp_point<N, S2>(s_g[el], sE, q, qx, qy, fv, dmy); }
+            if constexpr (T::hs) { double dmy; interp_point<N, S2>(s_g[el], sE, q, qx, qy, fv, dmy); }
             if constexpr (TUP != 0) {
                 // test functions of this point evaluated at its departure point (rows B2 / B4 / B17)
                 double gu, gv, px, py;
@@ -891,7 +905,7 @@ __global__ __launch_bounds__(256) void k_elmats(ElmatArgs a) {
     if constexpr (T::cf != SN) {
         ElemArgs ea{}; ea.i0 = a.i0; ea.i1x = a.i1x; ea.i1y = a.i1y; ea.i2 = a.i2;
         if (tid < 64) stage_dofs<N, T::cf>(ea, a.f, e, tid, s_f);
-        if constexpr (OP == MIMSEM_OP_UMAT_RAY) { if (tid < 64) stage_dofs<N, S2>(ea, a.f2, e, tid, s_g); }
+        if constexpr (T::hs) { if (tid < 64) stage_dofs<N, S2>(ea, a.f2, e, tid, s_g); }
     }
     __syncthreads();
     if (q < D::mp12) {
@@ -906,7 +920,7 @@ __global__ __launch_bounds__(256) void k_elmats(ElmatArgs a) {
         g.tI0 = a.tI[(size_t)e*D::mp12 + q]; g.param = a.param;
         double fu = 0.0, fv = 0.0;
         if constexpr (T::cf != SN) interp_point<N, T::cf>(s_f, sE, q, qx, qy, fu, fv);
-        if constexpr (OP == MIMSEM_OP_UMAT_RAY) { double dmy; interp_point<N, S2>(s_g, sE, q, qx, qy, fv, dmy); }
+        if constexpr (T::hs) { double dmy; interp_point<N, S2>(s_g, sE, q, qx, qy, fv, dmy); }
         // probe the coefficient functor with unit inputs to read the coefficients out
         double a10, b10, a01, b01;
         qpoint_op<OP>(g, a.scale, a.flags, 1.0, 0.0, fu, fv, a10, b10);
@@ -1479,6 +1493,7 @@ int dispatch_apply(mimsem_ctx* c, int op, const ElemArgs& a) {
         MIMSEM_CASE(MIMSEM_OP_ROTMAT) MIMSEM_CASE(MIMSEM_OP_WHMAT) MIMSEM_CASE(MIMSEM_OP_UTMAT)
         MIMSEM_CASE(MIMSEM_OP_UTMAT_H) MIMSEM_CASE(MIMSEM_OP_UTQWMAT) MIMSEM_CASE(MIMSEM_OP_WTQDUDZ)
         MIMSEM_CASE(MIMSEM_OP_PHMAT_UP) MIMSEM_CASE(MIMSEM_OP_ROTMAT_UP) MIMSEM_CASE(MIMSEM_OP_UMAT_RAY)
+        MIMSEM_CASE(MIMSEM_OP_UMAT_FRIC)
         MIMSEM_CASE(MIMSEM_OP_WTQ) MIMSEM_CASE(MIMSEM_OP_PTQ) MIMSEM_CASE(MIMSEM_OP_UTQ)
         case MIMSEM_OP_UMAT_UP: case MIMSEM_OP_UHMAT_UP: case MIMSEM_OP_UVEC_HU_UP:
             if constexpr (N <= 6) { switch (op) { MIMSEM_CASE(MIMSEM_OP_UMAT_UP) MIMSEM_CASE(MIMSEM_OP_UHMAT_UP) MIMSEM_CASE(MIMSEM_OP_UVEC_HU_UP) } break; }
@@ -1508,7 +1523,7 @@ int dispatch_elmats(mimsem_ctx* c, int op, const ElmatArgs& a) {
         MIMSEM_CASE(MIMSEM_OP_PMAT) MIMSEM_CASE(MIMSEM_OP_PHMAT) MIMSEM_CASE(MIMSEM_OP_WTQUMAT)
         MIMSEM_CASE(MIMSEM_OP_ROTMAT) MIMSEM_CASE(MIMSEM_OP_WHMAT) MIMSEM_CASE(MIMSEM_OP_UTMAT)
         MIMSEM_CASE(MIMSEM_OP_UTMAT_H) MIMSEM_CASE(MIMSEM_OP_UTQWMAT) MIMSEM_CASE(MIMSEM_OP_WTQDUDZ)
-        MIMSEM_CASE(MIMSEM_OP_UMAT_RAY)
+        MIMSEM_CASE(MIMSEM_OP_UMAT_RAY) MIMSEM_CASE(MIMSEM_OP_UMAT_FRIC)
     default: return MIMSEM_ERR_ARG;
     }
 #undef MIMSEM_CASE

@@ -330,6 +330,27 @@ class Engine:
                                                   _ptr(upd), upd.stride(0) if upd is not None else 0), "block_chebyshev_solve(%s)" % op)
         return x
 
+    def fric_chebyshev_solve(self, blocks, b, coef, tau, exner, exner_s, x=None, elem_scale=None, lev0=0, scale=1.0, flags=1, pb=None, upd=None):
+        """block_chebyshev_solve for (M1 + M1ray(tau)) x = b (mimsem_fric_chebyshev_solve): the element pass of every step is UMAT_FRIC.  exner
+        [nlev, n2]: the levels lev0.., exner_s [n2]: level 0; tau = 0 or exner = None: block_chebyshev_solve("UMAT", ...) itself."""
+        import ctypes
+        nd = 2 * self.n1e
+        assert b.dim() == 2 and b.shape[1] == self.sizes[1] and blocks.shape == (self.nEl, nd, nd)
+        x = torch.empty_like(b) if x is None else x
+        assert x.shape == b.shape and (pb is None or pb.shape == b.shape) and (upd is None or upd.shape == b.shape)
+        assert elem_scale is None or elem_scale.shape == (b.shape[0], self.nEl)
+        assert exner is None or (exner.shape == (b.shape[0], self.sizes[2]) and exner.stride(1) == 1 and
+                                 exner_s is not None and exner_s.shape == (self.sizes[2],) and exner_s.is_contiguous())
+        flat = (ctypes.c_double * (2 * len(coef)))(*[v for ab in coef for v in ab])
+        check(self.L.mimsem_fric_chebyshev_solve(self.ctx, OPS["UMAT"], lev0, b.shape[0], scale, flags, None, 0, _ptr(blocks),
+                                                 _ptr(elem_scale), elem_scale.stride(0) if elem_scale is not None else 0,
+                                                 _ptr(b), b.stride(0), len(coef), flat, _ptr(x), x.stride(0),
+                                                 _ptr(pb), pb.stride(0) if pb is not None else 0,
+                                                 _ptr(upd), upd.stride(0) if upd is not None else 0,
+                                                 float(tau), _ptr(exner), exner.stride(0) if exner is not None else 0, _ptr(exner_s)),
+              "fric_chebyshev_solve")
+        return x
+
     _OWNED_FORM = {"UMAT": 1, "UHMAT": 1, "UTMAT": 1, "UTMAT_H": 1, "WMAT": 2, "WHMAT": 2}
 
     def owned_rows(self, form):
@@ -422,6 +443,19 @@ class Engine:
               "mimsem_op_apply_up(UMAT_RAY)")
         return y if x.dim() == 2 else y2[0]
 
+    def apply_fric(self, x, exner, exner_s, tau, lev0=0, scale=1.0, alpha=1.0, flags=0, out=None):
+        """M1 + M1ray(tau) in one element pass (MIMSEM_OP_UMAT_FRIC; eul/Euler_2.cpp:1431-1451): Umat with the vertical flag whose point weights
+        carry 1 + tau k_v.  Arguments as apply_ray; flags: FLAG_ACCUM or 0."""
+        x2 = x if x.dim() == 2 else x.unsqueeze(0); f2 = exner if exner.dim() == 2 else exner.unsqueeze(0)
+        nlev = x2.shape[0]
+        assert x2.shape[1] == self.sizes[1] and f2.shape == (nlev, self.sizes[2]) and exner_s.shape == (self.sizes[2],)
+        y = out if out is not None else torch.empty(nlev, self.sizes[1], dtype=torch.float64, device=self.device)
+        y2 = y if y.dim() == 2 else y.unsqueeze(0)
+        check(self.L.mimsem_op_apply_up(self.ctx, OPS["UMAT_FRIC"], lev0, nlev, scale, tau, flags, _ptr(f2), f2.stride(0),
+                                        _ptr(exner_s), 0, _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0), alpha),
+              "mimsem_op_apply_up(UMAT_FRIC)")
+        return y if x.dim() == 2 else y2[0]
+
     def prepare_apply(self, op, x, f=None, lev0=0, scale=1.0, flags=0, alpha=1.0, out=None):
         """Validate once, return (call, y): `call()` re-issues the same mimsem_op_apply with pre-marshalled
         arguments (the buffers are fixed) -- the host-side fast path for time-step loops and bench.py."""
@@ -480,6 +514,14 @@ class Engine:
         out = torch.empty(self.nEl, esz, dtype=torch.float64, device=self.device)
         check(self.L.mimsem_op_element_matrices_ex(self.ctx, OPS["UMAT_RAY"], lev, scale, dt, 0, _ptr(exner), _ptr(exner_s), _ptr(out)),
               "mimsem_op_element_matrices_ex(UMAT_RAY)")
+        return out
+
+    def element_matrices_fric(self, exner, exner_s, tau, lev=0, scale=1.0):
+        """the element blocks of M1 + M1ray(tau) at one level (what MatAXPY(M1->M, 1.0, M1ray->M) leaves in M1, eul/Euler_2.cpp:1448)"""
+        esz = self.L.mimsem_op_elmat_size(self.ctx, OPS["UMAT_FRIC"])
+        out = torch.empty(self.nEl, esz, dtype=torch.float64, device=self.device)
+        check(self.L.mimsem_op_element_matrices_ex(self.ctx, OPS["UMAT_FRIC"], lev, scale, tau, 0, _ptr(exner), _ptr(exner_s), _ptr(out)),
+              "mimsem_op_element_matrices_ex(UMAT_FRIC)")
         return out
 
     def blocks_apply(self, form, blocks, x, transpose=False, alpha=1.0, accum=False, out=None, elem_scale=None):

@@ -216,6 +216,18 @@ def _pcg_general(apply_A, b, precond, x0, rtol, maxit, check_every, allreduce):
     return x, its
 
 
+K_F = 1.1574074074074073e-05       # the largest Held-Suarez friction rate k_v can take (1/day; compute_k_v, eul/Assembly.cpp:1846-1856)
+
+
+def friction_interval(lmin, lmax, tau):
+    """spectral interval of P (M1 + M1ray(tau)) from that of P M1, P any symmetric positive definite preconditioner.  Umat_ray::assemble
+    (eul/Assembly.cpp:1876-1979) is Umat::assemble with each quadrature point's weight times tau k_v(q), 0 <= k_v <= K_F, so element by element
+    M1 <= M1 + M1ray(tau) <= (1 + tau K_F) M1 in the Loewner order (non-negative weights that differ pointwise by a factor in
+    [1, 1 + tau K_F]); the order survives the assembly and the congruence with P^(1/2), and with it the Rayleigh quotients: the lower end
+    stays, the upper end widens by 1 + tau K_F.  The only place this bound lives (MassSolver.solve_fric)."""
+    return lmin, lmax * (1.0 + tau * K_F)
+
+
 class MassSolver:
     """M1 u = b on all levels (the ksp1 solves, eul/HorizSolve.cpp:77-96: GMRES + PCBJACOBI with one block per element).
     Preconditioner: element blocks P^-1 = sum_e R_e^T D_e (M1_e)^-1 D_e R_e (D_e = 1/multiplicity of the edge), applied by
@@ -233,6 +245,7 @@ class MassSolver:
         self.kind = precond
         self.fixed_its = 0          # > 0: run exactly that many PCG iterations (hipGraph capture)
         self._cheb = None
+        self._cheb_fric = {}        # tau -> the fixed-length solver of M1 + M1ray(tau) (solve_fric)
         self._cheb_checked = False
         # every fixed-length solve logs {|P r_last|^2, |P b|^2} per level into a slot of this device log (round 6: round 5 verified the first
         # solve only; a later, rougher right-hand side could lose accuracy unseen): verify() reads it once per evaluation / step
@@ -310,6 +323,7 @@ class MassSolver:
                 b = torch.randn(eng.nk, eng.sizes[1], generator=g, dtype=torch.float64).to(eng.device)
                 lmin, lmax, elo, ehi = lanczos_bounds(lambda v: self.apply(v, 0), lambda r: self.precond(r, 0), b, its=40, errors=True)
             self.ritz_errors = (elo / lmin, ehi / lmax)
+            self.ritz = (lmin, lmax)
             # safety margins around the Ritz interval (round 6): as wide as the Ritz values are uncertain -- twice their residual bounds, at
             # least 1 %, at most the 10 % / 5 % of rounds 3-5.  On a smooth thickness field the extreme Ritz values of 40 steps are exact to
             # 1e-4 and the old margins cost 2 of 15 steps (profiles/r06_cheb_margin_probe.txt); every solve is still checked (verify()).
@@ -451,6 +465,38 @@ class MassSolver:
         if self.kind == "jacobi":
             return pcg(lambda v: self.apply(v, lev0), b, minv=self.minv[lev0:lev0 + nlev], rtol=rtol, maxit=maxit)
         return pcg(lambda v: self.apply(v, lev0), b, precond=lambda r: self.precond(r, lev0), rtol=rtol, maxit=maxit, check_every=2)
+
+    def apply_fric(self, x, tau, exner, exner_s, lev0=0):
+        """(M1 + M1ray(tau)) x in one element pass; exner: the rows of levels lev0.., exner_s: the row of level 0"""
+        return self.eng.apply_fric(x, exner, exner_s, tau, lev0=lev0, scale=self.scale)
+
+    def solve_fric(self, b, tau, exner, exner_s, lev0=0, rtol=1e-14, maxit=300, out=None):
+        """(M1 + M1ray(tau)) x = b on the levels lev0..: the solve that ends stages 1 and 3 of Euler::Strang_ec under Held-Suarez forcing
+        (eul/Euler_2.cpp:1431-1456, :1477-1492).  The fixed-length Chebyshev solve keeps this object's blocks, escale, Ritz bounds and margins:
+        friction_interval widens the upper end and the step count follows from ChebyshevMass' rule; its check norms go to the same device log,
+        so verify() covers it.  Chebyshev mode off or another preconditioner: PCG on apply_fric.  Returns (x, steps or iterations);
+        tau = 0 or exner = None: solve(b).  out (fixed-length mode only): where x goes -- with it a recorded solve allocates nothing."""
+        if self.dist:
+            raise NotImplementedError("MassSolver.solve_fric: sharded engines are not supported")
+        if tau == 0.0 or exner is None:
+            return self.solve(b, lev0, rtol, maxit)
+        if not self.flags:
+            raise ValueError("MassSolver.solve_fric: M1 + M1ray carries the layer thickness (vert_scale=True)")
+        nlev = b.shape[0]
+        if self.kind == "blocks" and self.chebyshev:
+            self._chebyshev()
+            ch = self._cheb_fric.get(float(tau))
+            if ch is None:
+                lo, hi = friction_interval(self.ritz[0], self.ritz[1], tau)
+                ch = self._cheb_fric[float(tau)] = ChebyshevMass(self.eng, None, lo, hi, rtol=1e-15, margin=self.margin)
+            es = self.escale[lev0:lev0 + nlev]
+            ch.whole = lambda rhs, coef, pb, upd: self.eng.fric_chebyshev_solve(
+                self._blocks_cm, rhs, coef, tau, exner, exner_s, x=out, elem_scale=es, lev0=lev0, scale=self.scale, flags=self.flags, pb=pb, upd=upd)
+            return self._logged_solve(ch, b), ch.steps
+        A = lambda v: self.apply_fric(v, tau, exner, exner_s, lev0)
+        if self.kind == "jacobi":
+            return pcg(A, b, minv=self.minv[lev0:lev0 + nlev], rtol=rtol, maxit=maxit)
+        return pcg(A, b, precond=lambda r: self.precond(r, lev0), rtol=rtol, maxit=maxit, check_every=2)
 
 
 def gmres(apply_A, b, precond=None, x0=None, rtol=1e-14, atol=1e-50, restart=30, maxit=1000, dot=None, eng=None):
