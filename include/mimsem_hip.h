@@ -279,6 +279,22 @@ int mimsem_euler_energetics_horiz(mimsem_ctx* ctx, int nlev, const double* velx,
                                   const double* rt, long long ldt, const double* exner, long long lde,
                                   const double* theta, long long ldth, double* out);
 
+/* The four column sums of Euler::diagnostics in ONE pass over velz, rho and zv (k_energetics_column, csrc/energetics.inc) and the same
+ * fixed-order final pass; it replaces the per-column AssembleConLinWithW / AssembleLinearWithRT / AssembleLinearInv + MatMult + VecDot
+ * loops of eul/Euler_2.cpp:638-664 and :675-684.  out: DEVICE pointer to 4 doubles
+ *   out[0] kev = 1/2 sum_e rho_e . CONLIN_W(velz_e) velz_e / SCALE     (:638-648)
+ *   out[1] k2p = sum_e gi_e . (V01 zv_e) / SCALE                       (:650-655; gi = LINEAR_INV LINEAR_RT(rho, vert) velz, V01 zv = initGZ's GRAD gz)
+ *   out[2] p2k = sum_e (V10 gi_e) . zv_e / SCALE                       (:657-664)
+ *   out[3] pe  = sum_e zv_e . rho_e / SCALE                            (:675-684)
+ * velz: [nEl][(nk-1) n2e], rho and zv: [nEl][nk n2e], contiguous, in the vertical layout (mimsem_l2_transpose); linear_inv: the blocks
+ * [nEl][nk-1][n2e][n2e] that mimsem_colop_blocks(MIMSEM_V_LINEAR_INV) returns (geometry only: made once per mesh).  Element orders 1..4,
+ * the range of the fused Newton entries (MIMSEM_ERR_UNSUPPORTED above).  Deterministic: no floating-point atomics, the grid depends on
+ * (nEl, order) only, two calls on the same input give the same bits.  No host synchronisation; capturable once warmed up (the reduction
+ * workspace grows on the first call only: MIMSEM_ERR_STATE if it had to grow inside a capture).  A null pointer or a context with
+ * nk < 2: MIMSEM_ERR_ARG; every argument is checked before anything is launched, out untouched on error.                             */
+int mimsem_euler_energetics_column(mimsem_ctx* ctx, const double* velz, const double* rho, const double* zv, const double* linear_inv,
+                                   double* out);
+
 /* Row N3: the packed [u,h] operator of the shallow-water Picard step, SWEqn::assemble_operator (src/SWEqn_Picard.cpp:622-725),
  * which the reference forms with MatMatMult / MatGetRow / MatSetValues and hands to KSPSolve(kspA):
  *     y_u = (M1 + a R(f)) u + a g E12 M2 h        y_h = M2 (a H E21 u + h)        a = ROS_ALPHA dt, g = grav, H = H_MEAN

@@ -134,7 +134,146 @@ int energetics_horiz_n(mimsem_ctx* c, EnergeticsArgs& a, double* out) {
     return MIMSEM_OK;
 }
 
+// ---- the column half: kev, k2p, p2k, pe (eul/Euler_2.cpp:638-664, :675-684) in one pass over velz, rho and zv ------------------------
+//
+//   kev = 1/2 sum_e rho_e . CONLIN_W(velz_e) velz_e / SCALE       k2p = sum_e gi_e . (V01 zv_e) / SCALE
+//   p2k = sum_e (V10 gi_e) . zv_e / SCALE                         pe  = sum_e zv_e . rho_e / SCALE
+//   gi_e = LINEAR_INV LINEAR_RT(rho_e, vert) velz_e               (AssembleLinearInv / AssembleLinearWithRT eul/VertOps.cpp:422-430, :621-662)
+//
+// all in the vertical layout (velz [nEl][(nk-1) n2e], rho and zv [nEl][nk n2e]).  The W^T diag(c) W blocks of CONLIN_W and LINEAR_RT are
+// never formed: with R_k, V_i the interpolants of rho_k, velz_i at quadrature point q (wint of column_kernels.hip) and q0 = SCALE w_q / det_q
+//   rho_k . (CONLIN_W(velz) velz)_k = sum_q R_k q0 (1/2 V_{k-1}/det) V_{k-1} + R_k q0 (1/2 V_k/det) V_k          (VertOps.cpp:551-600)
+//   (LINEAR_RT(rho) velz)_i[j]      = sum_q W[q][j] (q0 (1/2 R_i/det) + q0 (1/2 R_{i+1}/det)) V_i                (do_internal: no thickness)
+// LINEAR_INV is the one factor that is not a quadrature sum: its blocks [nEl][nk-1][n2e][n2e] are READ (the ones mimsem_colop_blocks made
+// once per mesh, VertSolve keeps the same), not recomputed -- a fully pivoted Gauss-Jordan of an n2e x n2e block per interface and call
+// would cost n2e^3 dependent flops where the read costs n2e^2 doubles, and the cached blocks keep gi equal to the composed route's.
+//
+// Work item = column (element), lanes and groups as k_energetics_horiz: lane q of a group of LPE owns quadrature point q and, for q < n2e,
+// DoF q.  Levels are walked in order; at level k the lane holds R_{k-1}, V_{k-1} in registers, so interface k-1 is finished there:
+// t_q -> LDS, b = W^T t (lane j, mp12 terms), gi_{k-1}[j] = LINEAR_INV[k-1][j][:] . b; gi of the previous interface and zv of the previous
+// level stay in registers, so (V10 gi)_{k-1} = gi_{k-1} - gi_{k-2} and (V01 zv)_{k-1} = zv_k - zv_{k-1} need no global intermediate.  Every
+// input is read once.  Blocks are ONE wave (64 threads, 64/LPE columns): a column is a serial walk of nk levels, so many small blocks
+// spread the columns over the CUs (3 456 columns at the bench mesh are 864 blocks; 256-thread blocks would leave 40 CUs idle).
+// Reduction as above: fixed-stride walk over the columns, shuffle tree 32..1, one partial 4-vector per block, k_energetics_final.
+constexpr double EN_SCALE = 1.0e+8;      // eul/VertOps.cpp:21
+
+struct EnColumnArgs {
+    int nEl, nk;
+    const double *det, *E, *w;
+    const double *velz, *rho, *zv, *Ainv;
+    double* part;                        // [gridDim.x][4]
+};
+
+template <int N>
+__global__ __launch_bounds__(64) void k_energetics_column(EnColumnArgs a) {
+    using D = Dims<N>;
+    constexpr int LPE = D::LPE, EPB = 64/LPE, n2 = D::n2e, nn = n2*n2;
+    __shared__ double sE[D::mp1*N];
+    __shared__ double s_r[EPB][LPE], s_v[EPB][LPE], s_t[EPB][LPE], s_b[EPB][LPE];
+    const int tid = threadIdx.x, el = tid/LPE, q = tid%LPE;
+    const int qx = q%D::mp1, qy = q/D::mp1;
+    const int jx = q%N, jy = q/N;                                     // (as a DoF lane, q < n2e)
+    if (tid < D::mp1*N) sE[tid] = a.E[tid];
+    const double Q = q < D::mp12 ? a.w[qx]*a.w[qy] : 0.0;
+    const int nk = a.nk, ni = a.nk - 1;
+    double kev = 0.0, k2p = 0.0, p2k = 0.0, pe = 0.0;
+    wave_lds_sync();                     // sE (a block is one wave)
+    for (int base = blockIdx.x*EPB; base < a.nEl; base += gridDim.x*EPB) {        // (block-uniform trip count)
+        const int e = base + el;
+        const bool act = e < a.nEl, pt = act && q < D::mp12, dof = act && q < n2;
+        const double det = pt ? a.det[(size_t)e*D::mp12 + q] : 1.0;
+        const double q0 = Q*(EN_SCALE/det);
+        const double* ve = a.velz + (size_t)e*ni*n2;
+        const double* re = a.rho + (size_t)e*nk*n2;
+        const double* ze = a.zv + (size_t)e*nk*n2;
+        const double* Ae = a.Ainv + (size_t)e*ni*nn + (size_t)q*n2;  // row q of the column's first block
+        double Rp = 0.0, Vp = 0.0, zp = 0.0, gp = 0.0;                // level / interface k - 1: R, V at the point; zv, gi at the DoF
+        for (int k = 0; k < nk; k++) {
+            double zk = 0.0;
+            if (dof) {
+                const double rk = re[k*n2 + q];
+                zk = ze[k*n2 + q];
+                s_r[el][q] = rk; s_v[el][q] = k < ni ? ve[k*n2 + q] : 0.0;
+                pe += zk*rk;
+            }
+            wave_lds_sync();
+            double R = 0.0, V = 0.0, dmy;
+            if (pt) {
+                interp_point<N, S2>(s_r[el], sE, q, qx, qy, R, dmy);
+                interp_point<N, S2>(s_v[el], sE, q, qx, qy, V, dmy);
+                kev += R*((q0*(0.5*Vp/det))*Vp + (q0*(0.5*V/det))*V);             // rho_k . (CONLIN_W(velz) velz)_k
+                if (k > 0) s_t[el][q] = (q0*(0.5*Rp/det) + q0*(0.5*R/det))*Vp;    // LINEAR_RT(rho, vert) of interface k - 1 times V_{k-1}
+            }
+            wave_lds_sync();             // s_r, s_v read; s_t stored
+            if (k > 0) {
+                if (dof) {
+                    double b = 0.0;
+#pragma unroll
+                    for (int py = 0; py < D::mp1; py++)
+#pragma unroll
+                        for (int px = 0; px < D::mp1; px++) b += (sE[px*N + jx]*sE[py*N + jy])*s_t[el][py*D::mp1 + px];
+                    s_b[el][q] = b;
+                }
+                wave_lds_sync();
+                if (dof) {
+                    const double* Ar = Ae + (size_t)(k - 1)*nn;
+                    double g = 0.0;
+#pragma unroll
+                    for (int m = 0; m < n2; m++) g += Ar[m]*s_b[el][m];
+                    k2p += g*(zk - zp);                               // gi_{k-1} . (V01 zv)_{k-1}
+                    p2k += (g - gp)*zp;                               // (V10 gi)_{k-1} . zv_{k-1}
+                    gp = g;
+                }
+            }
+            Rp = R; Vp = V; zp = zk;
+        }
+        p2k += (0.0 - gp)*zp;                                         // (V10 gi)_{nk-1} = -gi_{nk-2}
+        wave_lds_sync();                 // the column's last s_b reads are done before the next column's stores
+    }
+    kev = en_wave_sum(kev); k2p = en_wave_sum(k2p); p2k = en_wave_sum(p2k); pe = en_wave_sum(pe);
+    if (tid == 0) {
+        double* o = a.part + (size_t)blockIdx.x*4;
+        o[0] = kev; o[1] = k2p; o[2] = p2k; o[3] = pe;
+    }
+}
+
+template <int N>
+int energetics_column_n(mimsem_ctx* c, EnColumnArgs& a, double* out) {
+    constexpr int EPB = 64/Dims<N>::LPE;
+    const int nb = std::max(1, std::min(EN_MAX_BLOCKS, (a.nEl + EPB - 1)/EPB));
+    const int rc = c->ensure_kry((long long)nb*4);                    // (grows outside a capture only: MIMSEM_ERR_STATE inside one)
+    if (rc) return rc;
+    a.part = c->d_kry;
+    hipLaunchKernelGGL((k_energetics_column<N>), dim3(nb), dim3(64), 0, c->stream, a);
+    MIMSEM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_energetics_final, dim3(1), dim3(256), 0, c->stream, nb, (const double*)c->d_kry, 0.5/EN_SCALE, 1.0/EN_SCALE, 1.0/EN_SCALE,
+                       1.0/EN_SCALE, out);
+    MIMSEM_HIP_TRY(hipGetLastError());
+    return MIMSEM_OK;
+}
+
 }  // namespace
+
+// Euler::diagnostics' column sums (eul/Euler_2.cpp:638-664 kev, k2p, p2k; :675-684 pe), which the reference forms column by column with
+// AssembleConLinWithW / AssembleLinearWithRT / AssembleLinearInv + MatMult + VecDot
+extern "C" int mimsem_euler_energetics_column(mimsem_ctx* c, const double* velz, const double* rho, const double* zv, const double* linear_inv,
+                                              double* out) {
+    if (!c || !velz || !rho || !zv || !linear_inv || !out) return MIMSEM_ERR_ARG;
+    if (c->nk < 2) return MIMSEM_ERR_ARG;
+    if (c->es.n > 4) return MIMSEM_ERR_UNSUPPORTED;
+    if (!c->d_det || !c->d_E || !c->d_w) return MIMSEM_ERR_STATE;
+    EnColumnArgs a{};
+    a.nEl = c->nEl; a.nk = c->nk;
+    a.det = c->d_det; a.E = c->d_E; a.w = c->d_w;
+    a.velz = velz; a.rho = rho; a.zv = zv; a.Ainv = linear_inv;
+    switch (c->es.n) {
+    case 1: return energetics_column_n<1>(c, a, out);
+    case 2: return energetics_column_n<2>(c, a, out);
+    case 3: return energetics_column_n<3>(c, a, out);
+    case 4: return energetics_column_n<4>(c, a, out);
+    default: return MIMSEM_ERR_UNSUPPORTED;
+    }
+}
 
 extern "C" int mimsem_euler_energetics_horiz(mimsem_ctx* c, int nlev, const double* velx, long long ldu, const double* rho, long long ldr,
                                              const double* rt, long long ldt, const double* exner, long long lde,

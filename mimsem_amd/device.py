@@ -117,6 +117,7 @@ class Engine:
         self.n0e, self.n1e, self.n2e, self.mp12 = (n + 1) ** 2, (n + 1) * n, n * n, (n + 1) ** 2
         self.nEl, self.nk = dmesh.nEl, dmesh.nk
         self.sizes = {0: dmesh.n0, 1: dmesh.n1, 2: dmesh.n2, "q": dmesh.nq, "q2": 2 * dmesh.nq}
+        self._linear_inv = None              # the LINEAR_INV column blocks energetics_column reads (made on its first call)
 
     def __del__(self):
         try:
@@ -622,6 +623,21 @@ class Engine:
         st = lambda t: t.stride(0) if nlev > 1 else 0
         check(self.L.mimsem_euler_energetics_horiz(self.ctx, nlev, velx.data_ptr(), st(velx), rho.data_ptr(), st(rho), rt.data_ptr(), st(rt),
                                                    exner.data_ptr(), st(exner), theta.data_ptr(), st(theta), _ptr(out)), "euler_energetics_horiz")
+        return out
+
+    def energetics_column(self, velz, rho, zv, out=None):
+        """mimsem_euler_energetics_column: [kev, k2p, p2k, pe] of Euler::diagnostics (eul/Euler_2.cpp:638-664, :675-684) as a device tensor
+        of 4; velz [nEl, (nk-1) n2e], rho and zv [nEl, nk n2e] in the vertical layout.  Orders 1..4.  The LINEAR_INV blocks the kernel reads
+        are made on the first call and kept: they depend on the geometry only, and a context's geometry (its levels included) is fixed when
+        the DeviceMesh is made"""
+        _need(self.nk >= 2, "energetics_column needs at least one interface (nk >= 2)")
+        self._col(velz, self.nk - 1, "velz"); self._col(rho, self.nk, "rho"); self._col(zv, self.nk, "zv")
+        out = torch.empty(4, dtype=torch.float64, device=self.device) if out is None else out
+        _need(out.numel() == 4 and out.is_contiguous(), "out: 4 contiguous doubles")
+        if self._linear_inv is None:                        # (first call: one allocation and the launches of colop_blocks -- warm up before recording)
+            self._linear_inv = self.colop_blocks("LINEAR_INV")
+        check(self.L.mimsem_euler_energetics_column(self.ctx, _ptr(velz), _ptr(rho), _ptr(zv), _ptr(self._linear_inv), _ptr(out)),
+              "euler_energetics_column")
         return out
 
     def sw_operator(self, a, grav, H, f0, x, out=None):

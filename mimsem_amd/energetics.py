@@ -5,7 +5,9 @@ after every step -- its only verification of the Euler stack.  Twelve numbers in
 
   horizontal()   keh, ie, entr, mass: the four element-local quadrature sums over all levels in one element pass plus a fixed-order final
                  pass (mimsem_euler_energetics_horiz, csrc/energetics.inc)
-  column()       kev, k2p, p2k, pe (:638-664, :675-684): composed from the column operators that exist,
+  column()       kev, k2p, p2k, pe (:638-664, :675-684): at orders <= 4 one pass over velz, rho, zv (mimsem_euler_energetics_column,
+                 csrc/energetics.inc: the LINEAR_INV blocks are read, every other factor is a quadrature sum formed in registers) and the
+                 final pass of horizontal(); at higher orders, and as column_composed() at every order, composed from the column operators,
                    kev = 1/2 sum_e rho_e . CONLIN_W(velz_e) velz_e / SCALE         k2p = sum_e gi_e . gv_e / SCALE
                    p2k = sum_e (V10 gi_e) . zv_e / SCALE                           pe  = sum_e zv_e . rho_e / SCALE
                  with gi = LINEAR_INV LINEAR_RT(rho, vert) velz and gv = V01 zv (initGZ's GRAD gz, eul/VertSolve.cpp:148-162; computed once per
@@ -24,6 +26,8 @@ FIELDS = ("keh", "kev", "pe", "ie", "k2p", "p2k", "k2i", "i2k", "k2i_z", "i2k_z"
 
 
 class Energetics:
+    FUSED_MAX_ORDER = 4                      # the orders mimsem_euler_energetics_column is instantiated for (those of the fused Newton entries)
+
     def __init__(self, eng, vert, horiz=None):
         """eng: Engine with nk >= 2 levels; vert: its VertSolve (column operators, k2i_z); horiz: the HorizSolve whose momentum_rhs_ec left k2i
         (None: k2i = 0)"""
@@ -34,6 +38,8 @@ class Energetics:
         self.eng, self.vert, self.horiz = eng, vert, horiz
         self.nk = eng.nk
         self.zv = None                       # the geopotential diagnostics() uses: set_geopotential
+        self.fused = True                    # column(): the one-pass kernel where it exists, 2.9x the composed route's speed at the bench mesh
+                                             # (profiles/energetics_column.txt); False: column_composed everywhere
         self._gv_of, self._gv = None, None
         n = eng.nEl * eng.nk * eng.n2e
         # rows of the one rowdot: kev, k2p, p2k, pe.  The interface arrays of k2p are shorter than a level array: their tails stay zero
@@ -60,7 +66,18 @@ class Energetics:
         return self.eng.energetics_horiz(velx, rho, rt, exner, theta, out=out)
 
     def column(self, velz, rho, zv=None):
-        """[kev, k2p, p2k, pe] (device) from velz [nEl, (nk-1) n2e], rho and zv [nEl, nk n2e] in the vertical layout"""
+        """[kev, k2p, p2k, pe] (device) from velz [nEl, (nk-1) n2e], rho and zv [nEl, nk n2e] in the vertical layout: ONE pass over the three
+        inputs (Engine.energetics_column, k_energetics_column) at orders <= 4 when self.fused, the composed route otherwise"""
+        if not self.fused or self.eng.mesh.n > self.FUSED_MAX_ORDER:
+            return self.column_composed(velz, rho, zv)
+        zv = self.zv if zv is None else zv
+        if zv is None:
+            raise ValueError("Energetics.column: no geopotential (pass zv or call set_geopotential)")
+        return self.eng.energetics_column(velz, rho, zv)
+
+    def column_composed(self, velz, rho, zv=None):
+        """column() composed from the single column operators (five operator launches, one V10, seven copies into padded rows, one rowdot):
+        every order; kept beside the fused kernel for comparison -- the two differ in summation order only"""
         eng, vert, nk = self.eng, self.vert, self.nk
         zv = self.zv if zv is None else zv
         if zv is None:

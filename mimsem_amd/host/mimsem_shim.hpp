@@ -671,7 +671,7 @@ struct VertSolve {
     Mesh* mesh; double dt;
 };
 
-// Euler (eul/Euler_2.h): the horizontal half of Euler::diagnostics (eul/Euler_2.cpp:600-744) for every level in one call
+// Euler (eul/Euler_2.h): the two halves of Euler::diagnostics (eul/Euler_2.cpp:600-744), each for every level in one call
 struct Euler {
     Euler(Topo* t, Geom* g) : mesh(Mesh::of(t, g)) {}
     explicit Euler(Mesh* m) : mesh(m) {}
@@ -680,6 +680,11 @@ struct Euler {
     void energetics_horiz(int nk, const double* velx, long long ldu, const double* rho, long long ldr, const double* rt, long long ldt,
                           const double* exner, long long lde, const double* theta, long long ldth, double* out) const {
         check(mimsem_euler_energetics_horiz(mesh->ctx, nk, velx, ldu, rho, ldr, rt, ldt, exner, lde, theta, ldth, out), "Euler::energetics_horiz");
+    }
+    // out (device, 4 doubles): kev, k2p, p2k, pe (eul/Euler_2.cpp:638-664, :675-684); velz [nEl][(nk-1) n2e], rho, zv [nEl][nk n2e] in the vertical
+    // layout, linear_inv the LINEAR_INV blocks of mimsem_colop_blocks.  Orders 1..4.  No host synchronisation.
+    void energetics_column(const double* velz, const double* rho, const double* zv, const double* linear_inv, double* out) const {
+        check(mimsem_euler_energetics_column(mesh->ctx, velz, rho, zv, linear_inv, out), "Euler::energetics_column");
     }
     Mesh* mesh;
 };
