@@ -295,6 +295,21 @@ int mimsem_euler_energetics_horiz(mimsem_ctx* ctx, int nlev, const double* velx,
 int mimsem_euler_energetics_column(mimsem_ctx* ctx, const double* velz, const double* rho, const double* zv, const double* linear_inv,
                                    double* out);
 
+/* HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470), the horizontal Bernoulli function of momentum_rhs_ec, for levels 0 .. nk-1 in ONE
+ * launch (k_horiz_bernoulli, csrc/bernoulli.inc) instead of three accumulating WtQUmat applies, two interface averages and three
+ * accumulating Whmat applies:
+ *   out_k = 1/3 (K(velx1_k) velx1_k + K(velx1_k) velx2_k + K(velx2_k) velx2_k)                 (:428-439, WtQUmat::assemble eul/Assembly.cpp:951-966)
+ *         + 1/6 (M2h(z1_k) z1_k + M2h(z1_k) z2_k + M2h(z2_k) z2_k)                             (:461-468, Whmat::assemble :1268-1281, no vertical scaling)
+ *   za_k  = 1/2 velza_{k-1} (k > 0) + 1/2 velza_k (k < nk-1)                                   (:451-459)
+ * velx1, velx2: local 1-form rows [nk][n1] at the row stride ldu; velz1, velz2: 2-form rows of the nk - 1 interfaces in the horizontal
+ * layout at the row stride ldz; out: 2-form rows [nk][n2] at the row stride ldo (strides in doubles); scale: the SCALE of the assembled
+ * matrices.  velx1 == velx2 and velz1 == velz2 are allowed (the first stage of Euler::Strang_ec calls it so); out must not overlap an
+ * input.  Element orders 1..7.  The result is element-local (2-forms are discontinuous): no atomics, no workspace, a fixed summation
+ * order -- two calls on the same input give the same bits; no host synchronisation, capturable.  A null pointer, a negative stride or
+ * nk outside 2..ctx nk: MIMSEM_ERR_ARG; an order outside 1..7: MIMSEM_ERR_UNSUPPORTED; nothing launched, out untouched.            */
+int mimsem_horiz_bernoulli(mimsem_ctx* ctx, int nk, const double* velx1, const double* velx2, long long ldu,
+                           const double* velz1, const double* velz2, long long ldz, double scale, double* out, long long ldo);
+
 /* Row N3: the packed [u,h] operator of the shallow-water Picard step, SWEqn::assemble_operator (src/SWEqn_Picard.cpp:622-725),
  * which the reference forms with MatMatMult / MatGetRow / MatSetValues and hands to KSPSolve(kspA):
  *     y_u = (M1 + a R(f)) u + a g E12 M2 h        y_h = M2 (a H E21 u + h)        a = ROS_ALPHA dt, g = grav, H = H_MEAN

@@ -640,6 +640,25 @@ class Engine:
               "euler_energetics_column")
         return out
 
+    def bernoulli(self, velx1, velx2, velz1, velz2, scale=1.0, out=None):
+        """mimsem_horiz_bernoulli: HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470) of every level in one launch; velx1, velx2 [nk, n1],
+        velz1, velz2 [nk-1, n2] (horizontal layout) -> Phi [nk, n2].  Rows contiguous, any row stride (the two of a pair share it); velx1 is
+        velx2 and velz1 is velz2 are allowed"""
+        nk = velx1.shape[0] if velx1.dim() == 2 else -1
+        _need(nk >= 2, "bernoulli needs at least one interface (nk >= 2)")
+        for t, rows, n, name in ((velx1, nk, 1, "velx1"), (velx2, nk, 1, "velx2"), (velz1, nk - 1, 2, "velz1"), (velz2, nk - 1, 2, "velz2")):
+            _need(t.dim() == 2 and t.shape == (rows, self.sizes[n]) and t.stride(1) == 1 and t.stride(0) >= 0,
+                  "%s: [%d, n%d] with contiguous rows" % (name, rows, n))
+            _need(t.dtype == torch.float64 and t.is_cuda, "float64 device rows")
+        _need(velx1.stride(0) == velx2.stride(0), "velx1, velx2: one row stride")
+        _need(nk == 2 or velz1.stride(0) == velz2.stride(0), "velz1, velz2: one row stride")
+        out = torch.empty(nk, self.sizes[2], dtype=torch.float64, device=self.device) if out is None else out
+        _need(out.dim() == 2 and out.shape == (nk, self.sizes[2]) and out.stride(1) == 1 and out.stride(0) >= self.sizes[2]
+              and out.dtype == torch.float64 and out.is_cuda, "out: [nk, n2] float64 device rows")
+        check(self.L.mimsem_horiz_bernoulli(self.ctx, nk, velx1.data_ptr(), velx2.data_ptr(), velx1.stride(0), velz1.data_ptr(), velz2.data_ptr(),
+                                            velz1.stride(0) if nk > 2 else 0, scale, out.data_ptr(), out.stride(0)), "horiz_bernoulli")
+        return out
+
     def sw_operator(self, a, grav, H, f0, x, out=None):
         """SWEqn::assemble_operator + MatMult (src/SWEqn_Picard.cpp:622-725) in one element pass: x, y packed rows [u | h]"""
         x2 = x if x.dim() == 2 else x.unsqueeze(0)

@@ -30,6 +30,7 @@ class HorizSolve:
         self.m0 = eng.pvec(0, eng.nk, SCALE)                  # M0 is diagonal for the collocated 0-forms (Pvec)
         self.fg = None
         self.k2i_dev = None
+        self.fused_phi = False                                  # diagnose_Phi: True = the one-launch kernel (Engine.bernoulli), False = the eight composed launches
         if quad_coords is not None:
             self.coriolis(quad_coords)
 
@@ -106,6 +107,8 @@ class HorizSolve:
 
     def diagnose_Phi(self, u1, u2, velz1, velz2):
         """:419-470"""
+        if self.fused_phi:
+            return self.eng.bernoulli(u1, u2, velz1, velz2, scale=SCALE)
         Phi = self._ap("WTQUMAT", u1, f=u1, alpha=1.0 / 3.0)
         self._ap("WTQUMAT", u2, f=u1, flags=ACCUM, alpha=1.0 / 3.0, out=Phi)
         self._ap("WTQUMAT", u2, f=u2, flags=ACCUM, alpha=1.0 / 3.0, out=Phi)

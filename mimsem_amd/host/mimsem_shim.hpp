@@ -686,6 +686,11 @@ struct Euler {
     void energetics_column(const double* velz, const double* rho, const double* zv, const double* linear_inv, double* out) const {
         check(mimsem_euler_energetics_column(mesh->ctx, velz, rho, zv, linear_inv, out), "Euler::energetics_column");
     }
+    // HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470) of levels 0 .. nk-1 in one launch: Phi [nk][n2] from velx1, velx2 [nk][n1] and velz1, velz2 [nk-1][n2]
+    void diagnose_Phi(int nk, const double* velx1, const double* velx2, long long ldu, const double* velz1, const double* velz2, long long ldz,
+                      double scale, double* Phi, long long ldp) const {
+        check(mimsem_horiz_bernoulli(mesh->ctx, nk, velx1, velx2, ldu, velz1, velz2, ldz, scale, Phi, ldp), "HorizSolve::diagnose_Phi");
+    }
     Mesh* mesh;
 };
 
