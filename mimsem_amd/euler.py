@@ -21,12 +21,36 @@ saw (ThermalSW treats a missed step the same way).
 
 One difference from the reference, kept out on purpose: at :1475 the reference pairs the global vectors (velx_0, velx) with the LOCAL copies
 in the other order (ul, ul_prev).  HorizSolve.momentum_rhs_ec has one vector per argument (local == global on one context), so each velocity
-is paired with itself.  Single context, global numbering; sharded engines are not supported."""
+is paired with itself.  Single context, global numbering; sharded engines are not supported.
+
+The baroclinic-wave driver around the step (eul/UMJS14.cpp:291-353) is host-side composition of the same device calls: init1 / init2
+(eul/Euler_2.cpp:429-529) project fields given on the quadrature grid, initial_state applies them to mimsem_amd/umjs14.py, run loops
+strang_ec with the reference's dump numbering, dump is the `save` branch (:1503-1534) and load the restart branch (UMJS14.cpp:334-344)."""
+import os
+
+import numpy as np
+import torch
+
+from . import io, umjs14
 from .energetics import Energetics
 from .hmomentum import HorizMomentum
-from .horizsolve import HorizSolve
+from .horizsolve import SCALE, VERT, HorizSolve
 from .vertsolve import VertSolve
 from .vortdiag import VortDiag
+
+
+def last_writer_table(indsq, nq):
+    """for every global quadrature point the flat index e mp12 + i of the element-local point whose value Geom::write0 / write1 / write2
+    leave there.  They store with INSERT_VALUES in the element loop ey, ex ascending (eul/Geom.cpp:441-452), so of the elements that share a
+    point the one visited last wins; patches count in the order of their ranks (between ranks PETSc leaves the order of INSERT_VALUES open).
+    indsq [nEl, mp12]: DeviceMesh.indsq, elements patch by patch in that loop order.  numpy's indexed assignment keeps the last of repeated
+    indices, which is the rule"""
+    iq = np.asarray(indsq).reshape(-1)
+    last = np.full(nq, -1, dtype=np.int64)
+    last[iq] = np.arange(iq.size)
+    if (last < 0).any():
+        raise ValueError("last_writer_table: a quadrature point that no element holds")
+    return last
 
 
 class Euler:
@@ -56,6 +80,10 @@ class Euler:
         self.u_prev = self.u_curr = self.uz = self.uz_prev = None
         self.steps = 0
         self.redone = 0                  # steps that missed a check and were run again
+        self.xq = np.asarray(quad_coords, dtype=np.float64)
+        self.step = 0                    # the dump counter (Euler::step, set to startStep by the driver: eul/UMJS14.cpp:297)
+        self.init1_redone = 0            # init1 solves run again after a missed check
+        self._m2inv = self._last = self._thick = None
 
     def _step(self, velx, velz, rho, rt, exner, carried):
         """one evaluation of the step from `carried` = (first_step, u_curr, uz); changes nothing of self.first_step / u_* / uz*.
@@ -119,3 +147,123 @@ class Euler:
         self.steps += 1
         values = self.energetics.diagnostics(*new) if diagnostics else None            # :1501
         return (*new, values)
+
+    # ---- the initial state (eul/Euler_2.cpp:429-529, eul/UMJS14.cpp:318-322) -----------------------------------------------------------
+    def _m2_inverse(self):
+        """the exact inverses of the nk x nEl element blocks of M2(k, SCALE, vert_scale = true) -- M2 is element-block diagonal, and the levels
+        do not change: built once"""
+        if self._m2inv is None:
+            eng, n2e = self.eng, self.eng.n2e
+            B = torch.stack([eng.element_matrices("WMAT", lev=k, scale=SCALE, flags=VERT).view(eng.nEl, n2e, n2e) for k in range(self.nk)])
+            self._m2inv = eng.block_inverse(B.view(self.nk * eng.nEl, n2e, n2e)).view(self.nk, eng.nEl, n2e, n2e)
+        return self._m2inv
+
+    def _quad_rows(self, fq, cols, what):
+        fq = torch.as_tensor(fq, dtype=torch.float64).to(self.eng.device).reshape(-1, cols).contiguous()
+        if fq.shape[0] != self.nk:
+            raise ValueError("Euler.%s: one row of the quadrature grid per level expected" % what)
+        return fq
+
+    def init2(self, fq):
+        """:489-529: fq [nk, nq] on the quadrature grid -> the 2-form [nk, n2], h_k = M2(k, SCALE, true)^-1 SCALE WtQ f_k"""
+        b = self.eng.apply("WTQ", self._quad_rows(fq, self.eng.sizes["q"], "init2"))
+        return self.eng.blocks_apply(2, self._m2_inverse(), b.mul_(SCALE))
+
+    def init1(self, uq):
+        """:429-487: uq [nk, nq, 2] (func_x, func_y interleaved per quadrature point, :454-455) -> the 1-form [nk, n1],
+        u_k = M1(k, SCALE, true)^-1 SCALE UtQ uq_k, every level in one batched solve of HorizSolve's mass solver.  eul/'s UtQmat
+        (eul/Assembly.cpp:824-902) is src/'s (src/Assembly.cpp:1052-1139) entry for entry -- J[0][0], J[1][0] on the x edges, J[0][1], J[1][1] on
+        the y edges, columns 2 q + {0, 1}, no thickness factor -- so Engine.apply("UTQ") is the operator.  The solve is checked through
+        verify(); after a miss the solver has switched to its adaptive form and the solve is run again"""
+        b = self.eng.apply("UTQ", self._quad_rows(uq, self.eng.sizes["q2"], "init1")).mul_(SCALE)
+        for attempt in range(2):
+            u, _ = self.horiz.m1.solve(b)
+            if self.horiz.verify():
+                return u
+            self.init1_redone += 1
+        raise RuntimeError("Euler.init1: the solve missed its check again after the switch to the adaptive solver")
+
+    def initial_state(self, vp=umjs14.VP):
+        """(velx, velz, rho, rt, exner) of the baroclinic-wave case in strang_ec's layouts (eul/UMJS14.cpp:313-322): the analytic fields of
+        mimsem_amd/umjs14.py at this object's quadrature points and level count, projected by init1 / init2; velz = 0.  The levels this
+        object was built with are expected to be umjs14.levels(nk, quad_coords); vp = 0 gives the steady state"""
+        uq, rho, rt, exner = umjs14.layer_fields(self.nk, self.xq, vp)
+        velz = self.eng.zeros(self.eng.nEl, (self.nk - 1) * self.eng.n2e)
+        return self.init1(uq), velz, self.init2(rho), self.init2(rt), self.init2(exner)
+
+    # ---- the loop, the `save` branch and the restart (eul/UMJS14.cpp:334-353, eul/Euler_2.cpp:1503-1534) -------------------------------------
+    def run(self, state, nsteps, dump_every=0, outdir="output", start_step=0, on_step=None):
+        """the driver's loop (eul/UMJS14.cpp:347-353): step = start_step dump_every + 1 .. nsteps, each one strang_ec whose twelve numbers go to
+        outdir/energetics.dat (Energetics.write_line); on a step with step % dump_every == 0 the dump counter self.step (which starts at
+        start_step) goes up by one and dump() writes under it.  on_step(step, values), when given, is called after every step.  Returns the
+        final state"""
+        self.step = start_step
+        os.makedirs(outdir, exist_ok=True)
+        path = os.path.join(outdir, "energetics.dat")
+        state = tuple(state)
+        for step in range(start_step * dump_every + 1, nsteps + 1):
+            out = self.strang_ec(*state)
+            state = out[:5]
+            Energetics.write_line(path, out[5])
+            if dump_every and step % dump_every == 0:
+                self.step += 1                                                          # :1505
+                self.dump(state, self.step, outdir)
+            if on_step is not None:
+                on_step(step, out[5])
+        return state
+
+    def last_writer(self):
+        """last_writer_table of this mesh as a device tensor, made once"""
+        if self._last is None:
+            self._last = torch.as_tensor(last_writer_table(self.eng.mesh.indsq, self.eng.sizes["q"]), device=self.eng.device)
+            self._thick = torch.as_tensor(np.ascontiguousarray(self.eng.mesh.thick), device=self.eng.device)
+        return self._last
+
+    def quad_fields(self, state):
+        """the physical fields of the `save` branch on the quadrature grid, {name: [nlev, nq] device tensor} in the global quadrature numbering:
+        Geom::write0 of the vorticity (HorizSolve::curl per level), write1 of velocity_h (two components), write2 with vert_scale = true of
+        density, rhoTheta, exner -- each divided by the level's thickness -- and write2 with vert_scale = false of theta (nk+1 levels) and
+        velocity_z (nk-1 levels).  A point shared by several elements takes the value of last_writer()'s element, by a gather.  Returns that
+        dict and the two fields diagnosed on the way, theta [nk+1, n2] and velz in the horizontal layout [nk-1, n2]"""
+        eng, nk = self.eng, self.nk
+        velx, velz, rho, rt, exner = state
+        last = self.last_writer()
+        pick = lambda a, thick: (a / self._thick if thick else a).reshape(a.shape[0], -1)[:, last].contiguous()
+        theta = eng.l2_vert_to_horiz(eng.diag_theta(1, eng.l2_horiz_to_vert(rho), eng.l2_horiz_to_vert(rt)), nk + 1)
+        velz_h = eng.l2_vert_to_horiz(velz.contiguous(), nk - 1)
+        uq = eng.interp_quad(1, velx)
+        out = {"vorticity": pick(eng.interp_quad(0, self.horiz.curl(velx)), True),
+               "velocity_h_x": pick(uq[..., 0], True), "velocity_h_y": pick(uq[..., 1], True)}
+        for name, a in (("density", rho), ("rhoTheta", rt), ("exner", exner)):
+            out[name] = pick(eng.interp_quad(2, a), True)
+        out["theta"] = pick(eng.interp_quad(2, theta), False)
+        out["velocity_z"] = pick(eng.interp_quad(2, velz_h), False)
+        return out, theta, velz_h
+
+    def dump(self, state, step, outdir="output"):
+        """the `save` branch of Strang_ec (eul/Euler_2.cpp:1503-1534) for `state` under the dump index `step`:
+          - the raw degree-of-freedom vectors, the .vec files of Geom::write1 / write2 (eul/Geom.cpp:553, :627) that LoadVecs / LoadVecsVert
+            read back, in the reference's names <field>_<level %.3u>_<step %.4u>.vec: velocity_h, density, rhoTheta, exner (nk levels),
+            velocity_z (nk-1 levels in the horizontal layout, Geom::writeVertToHoriz) and theta (nk+1 levels, diagTheta2 of the state);
+          - quad_fields() as one [nlev, nq] array per field, <field>_<step %.4u>.npy.
+        The reference writes the quadrature-grid fields through PETSc's ASCII viewer (.dat); that format is third-party and unpinned in the
+        reference and is not reproduced"""
+        velx, velz, rho, rt, exner = state
+        quad, theta, velz_h = self.quad_fields(state)
+        host = lambda a: a.detach().cpu().numpy()
+        for name, a in (("velocity_h", velx), ("density", rho), ("rhoTheta", rt), ("exner", exner), ("velocity_z", velz_h), ("theta", theta)):
+            io.save_levels(name, step, host(a), outdir)
+        for name, a in quad.items():
+            np.save(os.path.join(outdir, "%s_%.4u.npy" % (name, step)), host(a))
+
+    def load(self, step, outdir="output"):
+        """the restart branch (eul/UMJS14.cpp:334-344): (velx, velz, rho, rt, exner) from the .vec files of dump index `step`.  As in the
+        reference a restarted Euler begins with first_step = True: u_prev / uz_prev are not in the dumps, the first step after a restart
+        takes the forward predictor and uz_prev = uz, so a restarted run is not the continued run"""
+        eng, nk = self.eng, self.nk
+        rows = lambda name, n: eng.tensor(io.load_levels(name, step, n, outdir))
+        rho, velx, exner, rt = rows("density", nk), rows("velocity_h", nk), rows("exner", nk), rows("rhoTheta", nk)
+        velz = eng.l2_horiz_to_vert(rows("velocity_z", nk - 1))                       # LoadVecsVert :251-267
+        self.first_step = True
+        self.u_prev = self.u_curr = self.uz = self.uz_prev = None
+        return velx, velz, rho, rt, exner

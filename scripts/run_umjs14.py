@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""The baroclinic-wave run of eul/UMJS14.cpp:269-353 on one GPU: the cubed sphere and the stretched levels, Euler.initial_state (or Euler.load
+of dump index --start-step, the restart branch) and Euler.run.
+
+  python scripts/run_umjs14.py --pn 3 --ne 24 --nk 30 --dt 75 --nsteps 20 --dump-every 10 --start-step 0 --outdir output
+
+Prints per step the Newton iterations of the vertical solve with their last norms, the steps redone so far and the energetics line; at the end
+steps per second (host clock between device synchronisations around every step, the first step left out as warm-up: it finds the solvers' fixed
+lengths), the time of a dump, the fixed lengths the solvers settled on and the relative drift of mass and of total energy
+(keh + kev + pe + ie) from the first line to the last.  --profile PATH writes that summary to a file as well.
+
+The work runs in a child process under a time limit of its own (--time-limit seconds, default 1200; exit status 124 when it runs out): this
+process never opens the GPU."""
+import argparse
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse(argv):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--pn", type=int, default=3)
+    ap.add_argument("--ne", type=int, default=24)
+    ap.add_argument("--nk", type=int, default=30)
+    ap.add_argument("--dt", type=float, default=75.0)
+    ap.add_argument("--nsteps", type=int, default=20)
+    ap.add_argument("--dump-every", type=int, default=0)
+    ap.add_argument("--start-step", type=int, default=0)
+    ap.add_argument("--outdir", default="output")
+    ap.add_argument("--vp", type=float, default=None, help="amplitude of the wind perturbation (default: umjs14.VP; 0: the steady state)")
+    ap.add_argument("--newton-maxit", type=int, default=20)
+    ap.add_argument("--patches", type=int, default=0, help="patches of the mesh (default: 24 for an even ne >= 8, else 6)")
+    ap.add_argument("--profile", default=None, help="write the summary to this file as well")
+    ap.add_argument("--time-limit", type=float, default=1200.0)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    return ap.parse_args(argv)
+
+
+def work(a):
+    import numpy as np
+    import torch
+    from mimsem_amd import umjs14 as um
+    from mimsem_amd.device import DeviceMesh, Engine
+    from mimsem_amd.energetics import FIELDS
+    from mimsem_amd.euler import Euler
+    from mimsem_amd.geom import Geom
+    from mimsem_amd.mesh import CubedSphere, sphere_coords
+    from mimsem_amd.topo import Topo
+    if not torch.cuda.is_available():
+        raise SystemExit("run_umjs14: no GPU (the step has no CPU path)")
+    if a.start_step and not a.dump_every:
+        raise SystemExit("run_umjs14: --start-step counts dumps and needs --dump-every")
+    npatch = a.patches or (24 if a.ne >= 8 and a.ne % 2 == 0 else 6)
+    t0 = time.perf_counter()
+    cs = CubedSphere(a.pn, a.ne, npatch); coords = sphere_coords(a.pn, a.ne)
+    topos = [Topo(cs, p, a.nk) for p in range(npatch)]
+    geoms = [Geom(t, cs, coords, a.nk) for t in topos]
+    for g in geoms:
+        g.set_levels(um.levels(a.nk, coords[g.loc0]))
+    eng = Engine(DeviceMesh(topos, geoms, nk=a.nk, numbering="global"))
+    xq = coords[eng.mesh.gidq]
+    eu = Euler(eng, a.dt, um.levels(a.nk, xq), xq, newton_maxit=a.newton_maxit)
+    head = "UMJS14 baroclinic wave, p = %d, %d x %d x 6 sphere (%d elements), %d levels, dt = %g s; %s" \
+        % (a.pn, a.ne, a.ne, eng.nEl, a.nk, a.dt, torch.cuda.get_device_name(0))
+    print(head, flush=True)
+    state = eu.load(a.start_step, a.outdir) if a.start_step else eu.initial_state(um.VP if a.vp is None else a.vp)
+    torch.cuda.synchronize()
+    t_init = time.perf_counter() - t0
+    print("mesh, engine and %s: %.1f s (init1 solves redone: %d)" % ("restart" if a.start_step else "initial state", t_init, eu.init1_redone), flush=True)
+
+    ms, dump_ms, newton, lines = [], [], [], []
+
+    def timed(name, sink):
+        inner = getattr(eu, name)
+
+        def wrapped(*args, **kw):
+            torch.cuda.synchronize(); t = time.perf_counter()
+            out = inner(*args, **kw)
+            torch.cuda.synchronize(); sink.append((time.perf_counter() - t) * 1e3)
+            return out
+        setattr(eu, name, wrapped)
+    timed("strang_ec", ms); timed("dump", dump_ms)
+
+    def on_step(step, values):
+        h = eu.vert.history
+        newton.append(len(h)); lines.append(values)
+        print("step %d (day %.4f): Newton iterations %d, last |d_exner|/|exner| %.3e |d_rho|/|rho| %.3e, steps redone %d, %.1f ms"
+              % (step, step * a.dt / 86400.0, len(h), h[-1]["exner"], h[-1]["rho"], eu.redone, ms[-1]))
+        if len(h) >= a.newton_maxit:
+            print("  no convergence in %d iterations; norms per iteration:" % len(h))
+            for i, n in enumerate(h):
+                print("    %2d  exner %.3e  w %.3e  rho %.3e  eta %.3e" % (i + 1, n["exner"], n["w"], n["rho"], n["eta"]))
+        print("  " + "\t".join("%s %.16g" % kv for kv in zip(FIELDS, values)), flush=True)
+    state = eu.run(state, a.nsteps, dump_every=a.dump_every, outdir=a.outdir, start_step=a.start_step, on_step=on_step)
+    finite = all(bool(torch.isfinite(x).all()) for x in state)
+
+    out = [head, ""]
+    if len(ms) > 1:
+        rest = np.array(ms[1:])
+        out.append("steps per second: %.2f  (%.1f ms per step: mean of %d steps after one warm-up step of %.1f ms; median %.1f, min %.1f, max %.1f)"
+                   % (1e3 / rest.mean(), rest.mean(), rest.size, ms[0], np.median(rest), rest.min(), rest.max()))
+    if newton:
+        out.append("Newton iterations per step (maxit %d, tol %.0e): %s" % (a.newton_maxit, eu.newton_tol, " ".join(str(n) for n in newton)))
+    out.append("steps redone after a missed check: %d of %d; init1 solves redone: %d; state finite: %s" % (eu.redone, eu.steps, eu.init1_redone, finite))
+    m1, vd = eu.horiz.m1, eu.vort
+    cal = getattr(m1, "cheb_calibration", None)
+    out.append("1-form mass solver: %s; solves checked %d, missed %d, worst check %.2e"
+               % ("fixed-length Chebyshev, %d steps (bound %d)" % (cal["steps"], cal["bound_steps"]) if m1.chebyshev and cal else "adaptive PCG",
+                  m1.solves_checked, m1.solves_missed, m1.worst_check))
+    out.append("density-weighted solves (HorizPotVort, diagVertVort): fixed PCG lengths %s (0: adaptive), checks missed %d" % (dict(vd._its), vd.missed))
+    if dump_ms:
+        out.append("one dump (.vec of six fields, .npy of eight on the quadrature grid): %s ms" % " ".join("%.0f" % v for v in dump_ms))
+    if len(lines) > 1:
+        tot = lambda v: sum(v[FIELDS.index(n)] for n in ("keh", "kev", "pe", "ie"))
+        im = FIELDS.index("mass")
+        out.append("relative drift over %d steps (line 1 to line %d): mass %.3e, total energy %.3e"
+                   % (len(lines) - 1, len(lines), (lines[-1][im] - lines[0][im]) / lines[0][im], (tot(lines[-1]) - tot(lines[0])) / tot(lines[0])))
+        out.append("max |velz| of the final state: %.3e" % float(state[1].abs().max()))
+    text = "\n".join(out) + "\n"
+    print("\n" + text, end="", flush=True)
+    if a.profile:
+        os.makedirs(os.path.dirname(os.path.abspath(a.profile)), exist_ok=True)
+        with open(a.profile, "w") as f:
+            f.write(text)
+    return 0 if finite else 1
+
+
+def main(argv):
+    a = parse(argv)
+    if a.child:
+        return work(a)
+    try:
+        return subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + list(argv), timeout=a.time_limit).returncode
+    except subprocess.TimeoutExpired:
+        print("run_umjs14: the run did not end within %g s and was stopped" % a.time_limit, file=sys.stderr)
+        return 124
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))
