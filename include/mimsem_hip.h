@@ -595,6 +595,29 @@ int mimsem_column_max_norms(mimsem_ctx* ctx, const double* norm_squares, double*
 int mimsem_column_diag_theta_blend(mimsem_ctx* ctx, const double* rho, const double* rt, double* theta2, const double* blend2,
                                    double* thetaL, const double* blendL, double wa, double wb);
 
+/* ---- the Newton loop of solve_schur_column_3: VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246) ------------------------------- */
+/* The residual assembly and the update around mimsem_column_solve_schur_3, for EVERY column, orders 1..4 (MIMSEM_ERR_UNSUPPORTED above;
+ * nk < 4 is MIMSEM_ERR_ARG, as for the solve).  Capturable: no atomics, no host synchronisation.
+ *
+ * mimsem_column_newton2_residual (two launches): assemble_residual (:386-430) with diagnose_F_z / diagnose_Phi_z (:237-286) and the
+ *   right-hand sides of :1134-1154.  theta_h on the nk+1 INTERFACES (AssembleLinearWithTheta), Pi = exner_h.  The nullable additions each
+ *   enter times dt: add_w to F_w (u dw/dx, :1134); add_rho_pre / add_rt_pre to dF_z / dG_z BEFORE the VB product (the horizontal forcing of
+ *   advection_rhs, :1145-1146); add_rt_post to F_rt after it (AssembleTempForcing_HS, :1151-1154).
+ *   Out: F_w [nEl][(nk-1)*n2e], F_rho / F_rt / F_exner [nEl][nk*n2e], k2i [nEl][(nk-1)*n2e] = F_z . (VA(theta) grad Pi) entry by entry
+ *   (:415; its sum / SCALE is VertSolve::k2i_z). */
+int mimsem_column_newton2_residual(mimsem_ctx* ctx, double dt, double rayleigh,
+        const double* theta_h, const double* Pi, const double* velz_i, const double* velz_j, const double* rho_i, const double* rho_j,
+        const double* zv, const double* rt_i, const double* rt_j, const double* exner_j,
+        const double* add_w, const double* add_rho_pre, const double* add_rt_pre, const double* add_rt_post,
+        double* F_w, double* F_rho, double* F_rt, double* F_exner, double* k2i);
+/* after the solve (:1159-1183, one launch): x_j += d_x for (w, rho, rt, exner), x_h = 0.5 x_i + 0.5 x_j; norm_squares [8][nEl][nk*n2e] =
+ * squares of (d_exner, exner_j, d_w, velz_j, d_rho, rho_j, d_rt, rt_j) in the order mimsem_column_max_norms reads (the w rows end in n2e
+ * zeros). */
+int mimsem_column_newton2_update(mimsem_ctx* ctx, const double* d_w, const double* d_rho, const double* d_rt, const double* d_exner,
+        const double* velz_i, const double* rho_i, const double* rt_i, const double* exner_i,
+        double* velz_j, double* rho_j, double* rt_j, double* exner_j,
+        double* velz_h, double* rho_h, double* rt_h, double* exner_h, double* norm_squares);
+
 /* ---- Strang / Held-Suarez column rows --------------------------------------------------------- */
 /* mimsem_colop_blocks / mimsem_colop_apply with the extra arguments of the *_ex operators: param (dt_fric or dt)
  * and uh = the horizontal velocity as local 1-forms, one row per level ([nk][uh_stride], the reference's Vec* uhl). */

@@ -908,6 +908,40 @@ class Engine:
                                                  _ptr(velz_h), _ptr(rho_h), _ptr(rt_h), _ptr(exner_h), _ptr(nrm)), "newton_update")
         return velz_h, rho_h, rt_h, exner_h, nrm
 
+    def newton2_residual(self, dt, rayleigh, theta_h, Pi, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, exner_j,
+                         add_w=None, add_rho_pre=None, add_rt_pre=None, add_rt_post=None):
+        """mimsem_column_newton2_residual: (F_w, F_rho, F_rt, F_exner, k2i) of VertSolve::solve_schur_2 for every column
+        (VertSolve.cpp:1131-1154); theta_h on the nk+1 interfaces; the additions each enter times dt"""
+        nk = self.nk
+        for a, sl, nm in ((theta_h, nk + 1, "theta_h"), (Pi, nk, "Pi"), (velz_i, nk - 1, "velz_i"), (velz_j, nk - 1, "velz_j"), (rho_i, nk, "rho_i"),
+                          (rho_j, nk, "rho_j"), (zv, nk, "zv"), (rt_i, nk, "rt_i"), (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j")):
+            self._col(a, sl, nm)
+        self._col(add_w, nk - 1, "add_w", optional=True); self._col(add_rho_pre, nk, "add_rho_pre", optional=True)
+        self._col(add_rt_pre, nk, "add_rt_pre", optional=True); self._col(add_rt_post, nk, "add_rt_post", optional=True)
+        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
+        F_w, F_rho, F_rt, F_ex, k2i = mk(nk - 1), mk(nk), mk(nk), mk(nk), mk(nk - 1)
+        check(self.L.mimsem_column_newton2_residual(self.ctx, dt, rayleigh, _ptr(theta_h), _ptr(Pi), _ptr(velz_i), _ptr(velz_j), _ptr(rho_i), _ptr(rho_j),
+                                                    _ptr(zv), _ptr(rt_i), _ptr(rt_j), _ptr(exner_j),
+                                                    _ptr(add_w), _ptr(add_rho_pre), _ptr(add_rt_pre), _ptr(add_rt_post),
+                                                    _ptr(F_w), _ptr(F_rho), _ptr(F_rt), _ptr(F_ex), _ptr(k2i)), "newton2_residual")
+        return F_w, F_rho, F_rt, F_ex, k2i
+
+    def newton2_update(self, d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i, velz_j, rho_j, rt_j, exner_j):
+        """mimsem_column_newton2_update: velz_j / rho_j / rt_j / exner_j are updated IN PLACE; returns (velz_h, rho_h, rt_h, exner_h, norm_squares
+        [8, nEl, nk n2e]) (VertSolve.cpp:1159-1183)"""
+        nk = self.nk
+        for a, sl, nm in ((d_w, nk - 1, "d_w"), (d_rho, nk, "d_rho"), (d_rt, nk, "d_rt"), (d_exner, nk, "d_exner"), (velz_i, nk - 1, "velz_i"),
+                          (rho_i, nk, "rho_i"), (rt_i, nk, "rt_i"), (exner_i, nk, "exner_i"), (velz_j, nk - 1, "velz_j"), (rho_j, nk, "rho_j"),
+                          (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j")):
+            self._col(a, sl, nm)
+        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
+        velz_h, rho_h, rt_h, exner_h = mk(nk - 1), mk(nk), mk(nk), mk(nk)
+        nrm = torch.empty(8, self.nEl, nk * self.n2e, dtype=torch.float64, device=self.device)
+        check(self.L.mimsem_column_newton2_update(self.ctx, _ptr(d_w), _ptr(d_rho), _ptr(d_rt), _ptr(d_exner), _ptr(velz_i), _ptr(rho_i), _ptr(rt_i),
+                                                  _ptr(exner_i), _ptr(velz_j), _ptr(rho_j), _ptr(rt_j), _ptr(exner_j),
+                                                  _ptr(velz_h), _ptr(rho_h), _ptr(rt_h), _ptr(exner_h), _ptr(nrm)), "newton2_update")
+        return velz_h, rho_h, rt_h, exner_h, nrm
+
     def max_norms(self, nrm):
         """mimsem_column_max_norms: VertSolve::MaxNorm for the four pairs of newton_update's norm squares -> device tensor [4] (exner, w, rho, eta)"""
         assert nrm.shape == (8, self.nEl, self.nk * self.n2e) and nrm.is_contiguous()

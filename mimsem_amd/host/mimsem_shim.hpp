@@ -656,6 +656,23 @@ struct VertSolve {
         check(mimsem_column_solve_schur_3(mesh->ctx, dt, box_twin ? MIMSEM_SCHUR3_BOX : 0u, theta, velz, rho, rt, pi,
                                           F_u, F_rho, F_rt, F_pi, d_u, d_rho, d_rt, d_pi, nullptr), "solve_schur_column_3");
     }
+    // the residual assembly and the update of VertSolve::solve_schur_2 around solve_schur_column_3 (eul/VertSolve.cpp:1131-1183), every column in
+    // two + one launches (mimsem_amd/host/mimsem_vertsolve.hpp: VertSolve2 is the whole loop).  theta_h on the nk+1 interfaces; the four additions
+    // are nullable and enter times dt: udwdx -> F_w, dFx / dGx before the VB product, hs (AssembleTempForcing_HS) after it
+    void newton2_residual(double rayleigh, const double* theta_h, const double* exner_h, const double* velz_i, const double* velz_j, const double* rho_i,
+                          const double* rho_j, const double* zv, const double* rt_i, const double* rt_j, const double* exner_j,
+                          const double* udwdx, const double* dFx, const double* dGx, const double* hs,
+                          double* F_w, double* F_rho, double* F_rt, double* F_exner, double* k2i) {
+        check(mimsem_column_newton2_residual(mesh->ctx, dt, rayleigh, theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, exner_j,
+                                             udwdx, dFx, dGx, hs, F_w, F_rho, F_rt, F_exner, k2i), "newton2_residual");
+    }
+    void newton2_update(const double* d_w, const double* d_rho, const double* d_rt, const double* d_exner,
+                        const double* velz_i, const double* rho_i, const double* rt_i, const double* exner_i,
+                        double* velz_j, double* rho_j, double* rt_j, double* exner_j,
+                        double* velz_h, double* rho_h, double* rt_h, double* exner_h, double* norm_squares) {
+        check(mimsem_column_newton2_update(mesh->ctx, d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i, velz_j, rho_j, rt_j, exner_j,
+                                           velz_h, rho_h, rt_h, exner_h, norm_squares), "newton2_update");
+    }
     // what PCLU's band-wide pivoting would have guaranteed (eul/VertSolve.cpp:645-653), asked instead: the number of columns of the last
     // solve_schur_column_eta whose refinement did not reach 1e-10 of their solution (-1: the path in use keeps no status), per-column
     // status (0 / 1 / 2) and achieved |correction| / |solution| on request (host arrays of nEl entries, or nullptr)

@@ -5,6 +5,7 @@
 // mimsem_column_diag_theta_blend (diagTheta2 / diagTheta_L2 :289-352 with the half-time blend) -- and the max-norms of VertSolve::MaxNorm
 // (:228: mimsem_column_max_norms) with the reference's stopping test.  All state in the "vertical" layout of L2Vecs::vz: [nEl][slots*n2e], velz on the nk-1
 // interfaces, theta on nk+1, the rest on the nk levels.  Orders 1..4 (the fused entries' range).  Header-only, C++17, no HIP toolchain.
+// VertSolve2 below is the same for VertSolve::solve_schur_2 (:1059-1246), the loop around solve_schur_column_3.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -109,6 +110,86 @@ private:
         }
         return ones_i;
     }
+};
+
+// The other vertical Newton loop: VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246), the caller of solve_schur_column_3 and the vertical
+// half of Euler::Strang.  Per iteration mimsem_column_newton2_residual (assemble_residual :386-430 and the right-hand sides of :1134-1154),
+// mimsem_column_solve_schur_3 (:504-675), mimsem_column_newton2_update (:1159-1183), mimsem_column_max_norms and mimsem_column_diag_theta_blend
+// (diagTheta2 with the half-time blend, :1186-1191).  theta lives on the nk+1 interfaces; the loop stops on THREE norms (:1202).  Orders 1..4.
+class VertSolve2 {
+public:
+    struct Norms { double exner, w, rho, rt; };
+    std::vector<Norms> history;                       // |d x| / |x| (max over the columns) of the iterations of the last solve
+    double k2i_z = 0.0;                               // VertSolve::k2i_z of the last iteration (:415-416)
+    double rayleigh = 4.0/120.0;                      // RAYLEIGH, eul/VertSolve.cpp:32 (0: the box twin has none)
+    unsigned schur3_flags = 0;                        // passed to mimsem_column_solve_schur_3 (MIMSEM_SCHUR3_BOX: box/VertSolve.cpp)
+    // HorizSolve::advection_rhs (:1124): forcing(rho_i, rho_j, theta_h on the nk+1 interfaces, dFx, dGx) fills the two output arrays
+    // ([nEl][nk*n2e]); they join dF_z / dG_z BEFORE the VB product (:1145-1146).  Empty = no horizontal wind
+    std::function<void(const double*, const double*, const double*, double*, double*)> horiz_forcing;
+    // several ranks: MPI_Allreduce(MAX) of the four norms (:1195-1198) and the sum of k2i_z; unset = one rank (columns need no exchange)
+    std::function<void(double*, int)> allreduce_max, allreduce_sum;
+
+    VertSolve2(Mesh* m, double dt_) : mesh(m), dt(dt_) {
+        nEl = m->nEl_; n2 = m->n2e; nk = m->nk_;
+        nl = (size_t)nEl*nk*n2; ni = (size_t)nEl*(nk - 1)*n2; nt = (size_t)nEl*(nk + 1)*n2;
+        for (double** p : {&velz_j, &velz_h, &F_w, &d_w, &k2i, &ones_i}) *p = mem.get(ni);
+        for (double** p : {&rho_j, &rt_j, &exner_j, &rho_h, &rt_h, &exner_h, &F_rho, &F_rt, &F_exner, &d_rho, &d_rt, &d_exner, &dFx, &dGx, &hs}) *p = mem.get(nl);
+        for (double** p : {&theta_i, &theta_h}) *p = mem.get(nt);
+        nrm = mem.get(8*nl); sums = mem.get((size_t)4*nEl + 4);
+        std::vector<double> one(ni, 1.0);
+        check(mimsem_memcpy_h2d(mesh->ctx, ones_i, one.data(), (long long)ni*8), "h2d");
+    }
+    VertSolve2(const VertSolve2&) = delete; VertSolve2& operator=(const VertSolve2&) = delete;
+
+    // velz / rho / rt / exner at the old time level in, at the new one out (in place); zv from VertSolve::initGZ.  udwdx (nullable,
+    // [nEl][(nk-1)*n2e]): :1134; hs_lat (nullable, [nEl][mp12]): the Held-Suarez temperature forcing (:1151-1154).  Returns the number of
+    // iterations run; theta_h / exner_h (what Euler::Strang reads afterwards) stay in the accessors below.
+    int solve_schur_2(double* velz, double* rho, double* rt, double* exner, const double* zv, int maxit = 20, double tol = 1.0e-12,
+                      const double* udwdx = nullptr, const double* hs_lat = nullptr) {
+        mimsem_ctx* c = mesh->ctx;
+        mesh->copy(ni, velz, velz_j); mesh->copy(nl, rho, rho_j); mesh->copy(nl, rt, rt_j); mesh->copy(nl, exner, exner_j);      // :1099-1102
+        check(mimsem_column_diag_theta_blend(c, rho, rt, theta_i, nullptr, nullptr, nullptr, 1.0, 0.0), "diag_theta_blend");      // diagTheta2 :1105
+        mesh->copy(nt, theta_i, theta_h);
+        mesh->copy(nl, exner, exner_h); mesh->copy(ni, velz, velz_h); mesh->copy(nl, rho, rho_h); mesh->copy(nl, rt, rt_h);       // :1112-1117
+        history.clear();
+        int it = 0;
+        for (it = 1; it <= maxit; it++) {
+            const double *a_rho = nullptr, *a_rt = nullptr, *a_hs = nullptr;
+            if (horiz_forcing) { horiz_forcing(rho, rho_j, theta_h, dFx, dGx); a_rho = dFx; a_rt = dGx; }                         // :1124
+            if (hs_lat) { check(mimsem_column_temp_forcing_hs(c, hs_lat, exner_h, theta_h, rho_h, hs), "temp_forcing_hs"); a_hs = hs; }
+            check(mimsem_column_newton2_residual(c, dt, rayleigh, theta_h, exner_h, velz, velz_j, rho, rho_j, zv, rt, rt_j, exner_j,
+                                                 udwdx, a_rho, a_rt, a_hs, F_w, F_rho, F_rt, F_exner, k2i), "newton2_residual");
+            check(mimsem_column_solve_schur_3(c, dt, schur3_flags, theta_h, velz_h, rho_h, rt_h, exner_h, F_w, F_rho, F_rt, F_exner,
+                                              d_w, d_rho, d_rt, d_exner, nullptr), "solve_schur_3");                              // :1156
+            check(mimsem_column_newton2_update(c, d_w, d_rho, d_rt, d_exner, velz, rho, rt, exner, velz_j, rho_j, rt_j, exner_j,
+                                               velz_h, rho_h, rt_h, exner_h, nrm), "newton2_update");                             // :1159-1183
+            check(mimsem_column_max_norms(c, nrm, sums, sums + 4*(size_t)nEl), "column_max_norms");                               // MaxNorm :228
+            check(mimsem_column_diag_theta_blend(c, rho_j, rt_j, theta_h, theta_i, nullptr, nullptr, 0.5, 0.5), "diag_theta_blend");   // :1186-1191
+            double mx[4];
+            mesh->to_host(mx, sums + 4*(size_t)nEl, 4);
+            if (allreduce_max) allreduce_max(mx, 4);                                                                              // :1195-1198
+            history.push_back({mx[0], mx[1], mx[2], mx[3]});
+            if (mx[0] < tol && mx[2] < tol && mx[3] < tol) break;                                                                 // :1202
+        }
+        {
+            double s = 0.0;
+            check(mimsem_krylov_rowdot(c, 1, (long long)ni, k2i, (long long)ni, ones_i, 0, sums), "krylov_rowdot");
+            mesh->to_host(&s, sums, 1);
+            if (allreduce_sum) allreduce_sum(&s, 1);
+            k2i_z = s/1.0e8;
+        }
+        mesh->copy(ni, velz_j, velz); mesh->copy(nl, rho_j, rho); mesh->copy(nl, rt_j, rt); mesh->copy(nl, exner_j, exner);       // :1209-1212
+        return std::min(it, maxit);
+    }
+    const double* theta_half() const { return theta_h; }          // [nEl][(nk+1)*n2e]
+    const double* exner_half() const { return exner_h; }
+
+private:
+    Mesh* mesh; double dt; DeviceArrays mem;
+    int nEl = 0, n2 = 0, nk = 0; size_t nl = 0, ni = 0, nt = 0;
+    double *velz_j, *velz_h, *F_w, *d_w, *k2i, *ones_i;
+    double *rho_j, *rt_j, *exner_j, *rho_h, *rt_h, *exner_h, *F_rho, *F_rt, *F_exner, *d_rho, *d_rt, *d_exner, *dFx, *dGx, *hs;
+    double *theta_i, *theta_h, *nrm, *sums;
 };
 
 }  // namespace mimsem_host

@@ -11,6 +11,10 @@ FLAG_VERT = 1
 
 
 class VertSolve:
+    # solve_schur_2's default route: fused where its median iteration measured lower than the composed one's (profiles/schur2_newton.txt:
+    # 0.627 / 1.093 ms at order 2, 1.170 / 2.088 ms at order 3, 2.060 / 4.348 ms at order 4); order 1 is not measured and stays composed
+    FUSED2_ORDERS = (2, 3, 4)
+
     def __init__(self, eng, dt, rayleigh=RAYLEIGH):
         self.eng, self.dt, self.rayleigh = eng, dt, rayleigh
         self.nk, self.n2e = eng.nk, eng.n2e
@@ -19,6 +23,9 @@ class VertSolve:
         # orders 1..4: residual assembly / update of the Newton loop through the fused entry points (mimsem_column_newton_*: four
         # launches per iteration instead of ~150 single-operator calls); MIMSEM_NEWTON_FUSED=0 keeps the composed form below
         self.fused = os.environ.get("MIMSEM_NEWTON_FUSED", "1") != "0"
+        # solve_schur_2: the fused route (mimsem_column_newton2_*) at the orders where it measured faster than the composed one
+        # (profiles/schur2_newton.txt); MIMSEM_NEWTON_FUSED=0 keeps the composed form of both loops
+        self.fused2 = self.fused and eng.mesh.n in self.FUSED2_ORDERS
 
     # thin wrappers: vo->AssembleX(ex,ey,...,M); MatMult(M, x, y) for every column
     _GEOMETRY_ONLY = ("CONST", "CONST_INV", "LINEAR", "LINEAR_INV", "RAYLEIGH")
@@ -212,4 +219,95 @@ class VertSolve:
                 break
         self.k2i_z = float(self._k2i.sum()) / SCALE if self._k2i is not None else 0.0
         self.theta_h, self.theta_l2_h, self.exner_h = theta_h, theta_l2_h, exner_h
+        return velz_j, rho_j, rt_j, exner_j
+
+    # ---- the other vertical implicit solve: the caller of solve_schur_column_3, the vertical half of Euler::Strang -----------------------
+    def assemble_residual(self, theta, Pi, velz1, velz2, rho1, rho2, zv):
+        """eul/VertSolve.cpp:386-430 -> (fw, F, G); theta on the nk+1 INTERFACES (AssembleLinearWithTheta), Pi / rho on levels, velz on the
+        nk-1 interfaces.  Leaves F * tA1 (the integrand of k2i_z, :415) in self._k2i"""
+        nk, nm, dt = self.nk, self.nk - 1, self.dt
+        F = self.diagnose_F_z(velz1, velz2, rho1, rho2)
+        Phi = self.diagnose_Phi_z(velz1, velz2, zv)
+        fw = self._mv("LINEAR", velz2, rows=nm) - self._mv("LINEAR", velz1, rows=nm)
+        fw += dt * self.V01(Phi)                                            # bernoulli function term
+        tA2 = self._mv("LINEAR_INV", self.V01(self._mv("CONST", Pi, rows=nk)), rows=nm)     # pressure gradient
+        tA1 = self._mv("LINEAR_THETA", tA2, f1=theta, rows=nm)
+        fw += dt * tA1
+        self._k2i = F * tA1                                                 # kinetic to internal energy power, entry by entry
+        G = self._mv("LINEAR_INV", self._mv("LINEAR_THETA", F, f1=theta, rows=nm), rows=nm)
+        if self.rayleigh:
+            fw += 0.5 * dt * self.rayleigh * (self._mv("RAYLEIGH", velz2, rows=nm) + self._mv("RAYLEIGH", velz1, rows=nm))
+        return fw, F, G
+
+    def solve_schur_2(self, velz_i, rho_i, rt_i, exner_i, zv, horiz_forcing=None, udwdx=None, hs_lat=None, maxit=20, tol=1.0e-12,
+                      schur3_flags=0, verbose=False, fused=None):
+        """VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246) for EVERY column at once: Newton iterations on (w, rho, rt, Pi) with
+        solve_schur_column_3 as the linear solve, all state in the "vertical" layout [nEl][slots*n2e] (L2Vecs::vz).
+
+        horiz_forcing(rho_i, rho_j, theta_h) -> (dFx, dGx): HorizSolve::advection_rhs (:1124) in the vertical layout ([nEl][nk*n2e]);
+        theta_h is on the nk+1 interfaces; the two join dF_z / dG_z BEFORE the VB product.  udwdx: optional [nEl][(nk-1)*n2e] (:1134).
+        hs_lat: latitude of the quadrature points [nEl][mp12] switches the Held-Suarez temperature forcing on (:1151-1154).
+        schur3_flags: passed to solve_schur_3 (3 with rayleigh = 0: the box twin's solve).  fused: None = the default route of this order.
+        Stops when the exner, rho AND rt norms are below tol (:1202).  Returns (velz, rho, rt, exner) at the new time level and leaves
+        theta_h / exner_h (what Euler::Strang reads), the per-iteration max-norms (history: exner, w, rho, rt) and k2i_z in self.*"""
+        eng, nk, dt = self.eng, self.nk, self.dt
+        fused = self.fused2 if fused is None else (fused and eng.mesh.n <= 4)       # (above order 4 the entries are unsupported: composed)
+        velz_j, rho_j, rt_j, exner_j = velz_i.clone(), rho_i.clone(), rt_i.clone(), exner_i.clone()      # :1099-1102
+        if fused:
+            theta_i, _ = eng.diag_theta_blend(rho_i, rt_i, wantL=False)                                 # diagTheta2 :1105
+        else:
+            theta_i = eng.diag_theta(1, rho_i, rt_i)
+        theta_h = theta_i
+        exner_h, velz_h, rho_h, rt_h = exner_i, velz_i, rho_i, rt_i                                     # :1112-1117 (never written in place)
+        self.history = []
+        self._k2i = None
+        for itt in range(1, maxit + 1):
+            dFx, dGx = horiz_forcing(rho_i, rho_j, theta_h) if horiz_forcing is not None else (None, None)      # :1124
+            hs = eng.temp_forcing_hs(hs_lat, exner_h, theta_h, rho_h) if hs_lat is not None else None          # :1152
+            if fused:
+                F_w, F_rho, F_rt, F_exner, self._k2i = eng.newton2_residual(
+                    dt, self.rayleigh or 0.0, theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, exner_j,
+                    add_w=udwdx, add_rho_pre=dFx, add_rt_pre=dGx, add_rt_post=hs)
+            else:
+                F_w, F_z, G_z = self.assemble_residual(theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv)     # :1131
+                if udwdx is not None:
+                    F_w = F_w + dt * udwdx                                                                 # :1134
+                F_exner = eng.column_eos(0, rt_j, exner_j)                                                 # Assemble_EOS_Residual :1135
+                dF_z = rho_j + dt * self.V10(F_z) - rho_i                                                  # :1137-1142
+                dG_z = rt_j + dt * self.V10(G_z) - rt_i
+                if dFx is not None:
+                    dF_z = dF_z + dt * dFx                                                                 # :1145-1146
+                    dG_z = dG_z + dt * dGx
+                F_rho = self._mv("CONST", dF_z, rows=nk)                                                   # :1148-1149
+                F_rt = self._mv("CONST", dG_z, rows=nk)
+                if hs is not None:
+                    F_rt = F_rt + dt * hs                                                                  # :1153
+            d_w, d_rho, d_rt, d_exner = eng.solve_schur_3(dt, theta_h, velz_h, rho_h, rt_h, exner_h, F_w, F_rho, F_rt, F_exner,
+                                                          flags=schur3_flags)                              # :1156
+            if fused:
+                velz_h, rho_h, rt_h, exner_h, nrm = eng.newton2_update(d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i,
+                                                                       velz_j, rho_j, rt_j, exner_j)     # :1159-1183
+                nv = eng.max_norms(nrm)                                                                    # MaxNorm :228 (two launches)
+            else:
+                velz_j = velz_j + d_w; rho_j = rho_j + d_rho; rt_j = rt_j + d_rt; exner_j = exner_j + d_exner
+                col = lambda dx, x: (torch.linalg.vector_norm(dx, dim=1) / torch.linalg.vector_norm(x, dim=1)).max()
+                nv = torch.stack([col(d_exner, exner_j), col(d_w, velz_j), col(d_rho, rho_j), col(d_rt, rt_j)])
+                exner_h = 0.5 * exner_i + 0.5 * exner_j; velz_h = 0.5 * velz_i + 0.5 * velz_j
+                rho_h = 0.5 * rho_i + 0.5 * rho_j; rt_h = 0.5 * rt_i + 0.5 * rt_j
+            nv = eng.allreduce(nv, op="max")                                                               # MPI_Allreduce(MAX) :1195-1198
+            # (the theta diagnosis does not depend on the norms: launched BEFORE the host waits for them)
+            if fused:
+                theta_h, _ = eng.diag_theta_blend(rho_j, rt_j, blend2=theta_i, wa=0.5, wb=0.5, wantL=False)   # :1186-1191
+            else:
+                theta_h = 0.5 * eng.diag_theta(1, rho_j, rt_j) + 0.5 * theta_i
+            nv = nv.tolist()
+            norms = dict(exner=nv[0], w=nv[1], rho=nv[2], rt=nv[3])
+            self.history.append(norms)
+            if verbose:
+                print("\t%d:\t|d_exner|/|exner|: %.6e\t|d_w|/|w|: %.6e\t|d_rho|/|rho|: %.6e\t|d_rt|/|rt|: %.6e"
+                      % (itt, norms["exner"], norms["w"], norms["rho"], norms["rt"]))
+            if norms["exner"] < tol and norms["rho"] < tol and norms["rt"] < tol:                          # :1202
+                break
+        self.k2i_z = float(self._k2i.sum()) / SCALE if self._k2i is not None else 0.0                      # :415-416, last iteration
+        self.theta_h, self.exner_h = theta_h, exner_h
         return velz_j, rho_j, rt_j, exner_j
