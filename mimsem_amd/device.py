@@ -1,12 +1,16 @@
 """Device-resident mesh + operator engine: thin Python layer over the C ABI (include/mimsem_hip.h).
 PyTorch supplies device memory, streams and torch.distributed -- plumbing, not the product."""
+import contextlib
 import ctypes as C
+import gc
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import COLOPS, FLAG_ACCUM, FLAG_VERT, OPS, MeshDesc, check
+
+_F64, _I32 = torch.float64, torch.int32
 
 
 def _ptr(t):
@@ -24,18 +28,32 @@ def _need(cond, what):
         raise _lib.MimsemError("invalid argument: " + what)
 
 
+def _ps(t2):
+    """(address, row stride) of a 2-D view that Engine._rows has checked; (None, 0) for an absent optional operand"""
+    return (None, 0) if t2 is None else (t2.data_ptr(), t2.stride(0))
+
+
+def _host(a, dtype):
+    """a host numpy array as the ABI reads it: (the contiguous array -- the caller keeps it alive over the call --, its address)"""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, a.ctypes.data
+
+
+def _coef(coef):
+    """[(alpha, beta)] of a fixed-length Chebyshev solve as the flat array of doubles the ABI takes"""
+    return (C.c_double * (2 * len(coef)))(*[v for ab in coef for v in ab])
+
+
 class no_gc:
     """Python's cyclic garbage collector must not run inside a stream capture: a collected device tensor is freed by the caching
     allocator with calls that are illegal on a capturing stream, the error is raised inside a destructor and the process aborts
     (seen as 'Fatal Python error: Aborted ... Garbage-collecting' in the middle of a GraphedGMRES capture)."""
 
     def __enter__(self):
-        import gc
         self.was = gc.isenabled()
         gc.disable()                     # (torch.cuda.graph collects once on entry by itself)
 
     def __exit__(self, *exc):
-        import gc
         if self.was:
             gc.enable()
         return False
@@ -55,7 +73,7 @@ class DeviceMesh:
         self.topos, self.geoms = topos, geoms
         n2e = self.n * self.n
         if numbering == "local":
-            assert len(topos) == 1
+            _need(len(topos) == 1, "numbering=\"local\" takes exactly one patch")
             self.inds0, self.inds1x, self.inds1y = t0.all_inds0_l(), t0.all_inds1x_l(), t0.all_inds1y_l()
             self.n0, self.n1, self.n2 = t0.n0, t0.n1, t0.n2
             self.gid0 = self.gid1 = self.gid2 = self.gidq = None
@@ -90,11 +108,11 @@ class DeviceMesh:
         keep = []
         d.nq = self.nq
         for name in ("inds0", "inds1x", "inds1y", "inds2", "indsq"):
-            a = np.ascontiguousarray(getattr(self, name), dtype=np.int32); keep.append(a)
-            setattr(d, name, a.ctypes.data)
+            a, p = _host(getattr(self, name), np.int32); keep.append(a)
+            setattr(d, name, p)
         for name in ("det", "J", "thick", "thickInv"):
-            a = np.ascontiguousarray(getattr(self, name), dtype=np.float64); keep.append(a)
-            setattr(d, name, a.ctypes.data)
+            a, p = _host(getattr(self, name), np.float64); keep.append(a)
+            setattr(d, name, p)
         d._keep = keep
         return d
 
@@ -182,47 +200,108 @@ class Engine:
     def zeros(self, *shape):
         return torch.zeros(*shape, dtype=torch.float64, device=self.device)
 
+    # ---- argument checks ----------------------------------------------------------------------
+    # The C ABI takes raw addresses and cannot check a length, so every wrapper below takes its addresses from _rows / _like / _out
+    # (with _ps), _vec, _word, _blocks or _col (with _ptr) -- nowhere else -- and every failure is a MimsemError through _need.
+    def _rows(self, t, n, name, rows=None, min_rows=0, optional=False, strided=False, dtype=_F64):
+        """the 2-D view of a row array [nrows, n] (a [n] tensor: one row), checked for what keeps the library in bounds: float64 (int32
+        where the ABI wants indices) on this engine's device, rows of length n (None: as they come), `rows` rows or at least min_rows.
+        strided=False: one contiguous block, as _ptr demands; "r" / "w": rows with unit inner stride that lie at least n apart (slices of
+        a wider array; "r", read only: also the same row for every level, as expand() makes)"""
+        if t is None:
+            _need(optional, name + " is required")
+            return None
+        d = t.dim()
+        t2 = t if d == 2 else t.unsqueeze(0)
+        if (d == 2 or d == 1) and t2.dtype is dtype and t2.device == self.device:
+            r, w = t2.shape
+            if (n is None or w == n) and (rows is None or r == rows) and r >= min_rows:
+                if t2.is_contiguous() if not strided else (t2.stride(1) == 1 and (r <= 1 or t2.stride(0) >= w or (strided == "r" and t2.stride(0) == 0))):
+                    return t2
+        _need(False, "%s: %s %s rows of length %s on %s required (%s), got %s %s on %s with strides %s" % (
+            name, dtype, rows if rows is not None else ">= %d" % min_rows, n, self.device, "one contiguous block" if not strided else "contiguous rows",
+            t.dtype, tuple(t.shape), t.device, t.stride()))
+
+    def _like(self, n, rows, strided=False, **named):
+        """_rows for several operands of one shape [rows, n], in the order given; None stays None (the library refuses a missing operand)"""
+        return [self._rows(t, n, name, rows=rows, optional=True, strided=strided) for name, t in named.items()]
+
+    def _out(self, out, rows, n, exact=False, strided=False, zero=False):
+        """(result, its 2-D view) of a row wrapper: `out` when given -- rows of length n, at least `rows` of them (exact: just `rows`) --,
+        else a new [rows, n] tensor"""
+        if out is None:
+            out = (torch.zeros if zero else torch.empty)(rows, n, dtype=_F64, device=self.device)
+            return out, out
+        return out, self._rows(out, n, "out", rows if exact else None, rows, False, strided)
+
+    def _vec(self, t, n, name, atleast=False, optional=False, dtype=_F64, pinned=False):
+        """address of a flat array: one contiguous block of n entries (atleast: n or more; n None: as it comes) of any shape, float64 or
+        int32, on this engine's device (pinned: see _word)"""
+        if t is None:
+            _need(optional, name + " is required")
+            return None
+        if t.dtype == dtype and t.is_contiguous() and (n is None or (t.numel() >= n if atleast else t.numel() == n)) \
+                and (t.device == self.device or (pinned and t.is_pinned())):
+            return t.data_ptr()
+        _need(False, "%s: a contiguous %s array of %s%s entries on %s required, got %s %s on %s" % (
+            name, dtype, "at least " if atleast else "", n, self.device, t.dtype, tuple(t.shape), t.device))
+
+    def _word(self, t, n, name, dtype=_F64):
+        """the col / flag words of cgs2, reorthonormalize and normalize, the one exception to "on this engine's device": they may lie in
+        PINNED host memory, which the kernels write directly; dtype, contiguity and length (at least n) are checked as everywhere"""
+        return self._vec(t, n, name, atleast=True, optional=True, dtype=dtype, pinned=True)
+
+    def _blocks(self, t, nd, name, nlev=None):
+        """(address, level stride) of element blocks: one contiguous float64 [nEl, nd, nd] set (stride 0) or, where nlev is given, also
+        [nlev, nEl, nd, nd]"""
+        if not (t is not None and t.dtype == _F64 and t.device == self.device and t.is_contiguous() and t.shape[-3:] == (self.nEl, nd, nd)
+                and (t.dim() == 3 or (nlev is not None and t.dim() == 4 and t.shape[0] == nlev))):
+            _need(False, "%s: contiguous float64 blocks [%snEl=%d, %d, %d] on %s required, got %s" % (
+                name, "" if nlev is None else "(nlev=%d, ) " % nlev, self.nEl, nd, nd, self.device,
+                None if t is None else (t.dtype, tuple(t.shape), t.device, t.stride())))
+        return t.data_ptr(), t.stride(0) if t.dim() == 4 else 0
+
+    def _new(self, *shape):
+        return torch.empty(*shape, dtype=_F64, device=self.device)
+
     # ---- horizontal operators ---------------------------------------------------------------
     _SPACES = dict(UMAT=(1, None, 1), UTMAT=(1, None, 1), UHMAT=(1, 2, 1), UTMAT_H=(1, 2, 1), ROTMAT=(1, 0, 1),
                    WMAT=(2, None, 2), WMATINV=(2, None, 2), WHMAT=(2, 2, 2), WHMATINV=(2, 2, 2), PMAT=(0, None, 0),
                    PHMAT=(0, 2, 0), WTQUMAT=(1, 1, 2), WTQDUDZ=(1, 1, 2), UTQWMAT=(2, 1, 1),
                    PHMAT_UP=(0, 2, 0), ROTMAT_UP=(1, 0, 1), UMAT_UP=(1, 1, 1), UHMAT_UP=(1, 2, 1), UVEC_HU_UP=(1, 2, 1), WTQ=("q", None, 2), PTQ=("q", None, 0), UTQ=("q2", None, 1))
 
+    def _op_args(self, op, x, f, out, exact=False):
+        """the _SPACES-driven check shared by apply, apply_part, apply_levels, apply_up and prepare_apply: the 2-D views of x and of the
+        operator's field (None for an operator that takes none), the result (given or new) and its 2-D view"""
+        sin, sf, sout = self._SPACES[op]
+        x2 = self._rows(x, self.sizes[sin], "x")
+        f2 = None if sf is None else self._rows(f, self.sizes[sf], "f", x2.shape[0])
+        return (x2, f2) + self._out(out, x2.shape[0], self.sizes[sout], exact)
+
+    def _fsize(self, op):
+        """length of the operator's field rows; None (not checked) for an operator that takes none"""
+        sf = self._SPACES.get(op, (None, None, None))[1]
+        return None if sf is None else self.sizes[sf]
+
     def apply(self, op, x, f=None, lev0=0, scale=1.0, flags=0, alpha=1.0, out=None):
         """y_k = A_op(level lev0+k, f_k) x_k ; x: [nlev, n_in] (or [n_in]) device tensor"""
-        sin, sf, sout = self._SPACES[op]
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        nlev = x2.shape[0]
-        assert x2.shape[1] == self.sizes[sin], (x2.shape, self.sizes[sin])
-        f2 = None
-        if sf is not None:
-            f2 = f if f.dim() == 2 else f.unsqueeze(0)
-            assert f2.shape == (nlev, self.sizes[sf])
-        y = out if out is not None else torch.empty(nlev, self.sizes[sout], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        check(self.L.mimsem_op_apply(self.ctx, OPS[op], lev0, nlev, scale, flags,
-                                     _ptr(f2), f2.stride(0) if f2 is not None else 0,
-                                     _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0), alpha), "mimsem_op_apply(%s)" % op)
+        x2, f2, y, y2 = self._op_args(op, x, f, out)
+        check(self.L.mimsem_op_apply(self.ctx, OPS[op], lev0, x2.shape[0], scale, flags, *_ps(f2), *_ps(x2), *_ps(y2), alpha), "mimsem_op_apply(%s)" % op)
         return y if x.dim() == 2 else y2[0]
 
     def apply_levels(self, op, x, lev_step, f=None, lev0=0, scale=1.0, flags=0, alpha=1.0, out=None):
         """mimsem_op_apply_levels: apply() with row r at geometry level lev0 + r lev_step; lev_step 0 (WMAT, UHMAT) evaluates every row
         at lev0, as HorizSolve::diagVertVort assembles M2 and F"""
-        sin, sf, sout = self._SPACES[op]
-        _need(x.dim() == 2 and x.shape[1] == self.sizes[sin], "x: [nlev, n_in]")
-        nlev = x.shape[0]
-        _need(sf is None or (f is not None and f.shape == (nlev, self.sizes[sf])), "f: one row per row of x")
-        y = out if out is not None else torch.empty(nlev, self.sizes[sout], dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_op_apply_levels(self.ctx, OPS[op], lev0, lev_step, nlev, scale, flags,
-                                            _ptr(f) if sf is not None else None, f.stride(0) if sf is not None else 0,
-                                            _ptr(x), x.stride(0), _ptr(y), y.stride(0), alpha), "mimsem_op_apply_levels(%s)" % op)
+        x2, f2, y, y2 = self._op_args(op, x, f, out)
+        check(self.L.mimsem_op_apply_levels(self.ctx, OPS[op], lev0, lev_step, x2.shape[0], scale, flags, *_ps(f2), *_ps(x2), *_ps(y2), alpha),
+              "mimsem_op_apply_levels(%s)" % op)
         return y
 
     def set_halo_slots(self, form, slots):
         """mark the 1-form slots that take part in a halo exchange: their element groups move to the front of the plan, so that
         apply_part(..., "boundary") completes exactly those slots (mimsem_ctx_set_halo_slots)"""
-        sl = np.ascontiguousarray(slots, dtype=np.int32)
-        check(self.L.mimsem_ctx_set_halo_slots(self.ctx, form, sl.ctypes.data, sl.size), "ctx_set_halo_slots")
+        sl, p = _host(slots, np.int32)
+        check(self.L.mimsem_ctx_set_halo_slots(self.ctx, form, p, sl.size), "ctx_set_halo_slots")
 
     def reset_parts(self):
         """forget a BOUNDARY part whose INTERIOR part will not come (error path of a split apply; mimsem_op_apply_part_reset)"""
@@ -232,19 +311,10 @@ class Engine:
         """the boundary or the interior part of apply(): part "boundary" first (all marked slots of `out` complete afterwards), then
         "interior" into the SAME out with the same arguments.  The pending boundary part keeps its partial sums in a buffer of its own:
         other calls may run in between, but a second boundary part or a non-matching interior part is refused (MIMSEM_ERR_STATE)"""
-        sin, sf, sout = self._SPACES[op]
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        nlev = x2.shape[0]
-        if x2.shape[1] != self.sizes[sin] or out is None or out.shape != (nlev, self.sizes[sout]):
-            raise _lib.MimsemError("apply_part: x [nlev, n_in] and out [nlev, n_out] required")
-        f2 = None
-        if sf is not None:
-            f2 = f if f.dim() == 2 else f.unsqueeze(0)
-            if f2.shape != (nlev, self.sizes[sf]):
-                raise _lib.MimsemError("apply_part: coefficient field of the wrong shape")
-        check(self.L.mimsem_op_apply_part(self.ctx, OPS[op], lev0, nlev, scale, flags, _ptr(f2), f2.stride(0) if f2 is not None else 0,
-                                          _ptr(x2), x2.stride(0), _ptr(out), out.stride(0), alpha, {"all": 0, "boundary": 1, "interior": 2}[part]),
-              "mimsem_op_apply_part(%s)" % op)
+        _need(out is not None, "apply_part: out [nlev, n_out] is required")
+        x2, f2, y, y2 = self._op_args(op, x, f, out, exact=True)
+        check(self.L.mimsem_op_apply_part(self.ctx, OPS[op], lev0, x2.shape[0], scale, flags, *_ps(f2), *_ps(x2), *_ps(y2), alpha,
+                                          {"all": 0, "boundary": 1, "interior": 2}[part]), "mimsem_op_apply_part(%s)" % op)
         return out
 
     def apply_up(self, op, x, f, u, fac=None, dt=None, lev0=0, alpha=1.0, flags=0, out=None, scale=1.0, tau=None):
@@ -252,103 +322,83 @@ class Engine:
         (tau = 1/(1/(fac*dt)), src/Assembly.cpp:541); the eul ops (UMAT_UP / UHMAT_UP / UVEC_HU_UP) pass scale and tau."""
         if tau is None:
             tau = 1.0 / (1.0 / (fac * dt))
-        sin, sf, sout = self._SPACES[op]
-        x2 = x if x.dim() == 2 else x.unsqueeze(0); f2 = f if f.dim() == 2 else f.unsqueeze(0); u2 = u if u.dim() == 2 else u.unsqueeze(0)
-        nlev = x2.shape[0]
-        assert x2.shape[1] == self.sizes[sin] and f2.shape == (nlev, self.sizes[sf]) and u2.shape == (nlev, self.sizes[1])
-        y = out if out is not None else torch.empty(nlev, self.sizes[sout], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        check(self.L.mimsem_op_apply_up(self.ctx, OPS[op], lev0, nlev, scale, tau, flags, _ptr(f2), f2.stride(0), _ptr(u2), u2.stride(0),
-                                        _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0), alpha), "mimsem_op_apply_up(%s)" % op)
+        x2, f2, y, y2 = self._op_args(op, x, f, out)
+        u2 = self._rows(u, self.sizes[1], "u", rows=x2.shape[0])
+        check(self.L.mimsem_op_apply_up(self.ctx, OPS[op], lev0, x2.shape[0], scale, tau, flags, *_ps(f2), *_ps(u2), *_ps(x2), *_ps(y2), alpha),
+              "mimsem_op_apply_up(%s)" % op)
         return y if x.dim() == 2 else y2[0]
+
+    def _sweep_rows(self, op, x, f, u, form=None, **like):
+        """operands of an in-place sweep: the views of x [nlev, n], the operator's field rows, the velocity rows and x's like-shaped
+        companions (None stays None).  form None: n from the operator, which must be square"""
+        sin, sf, sout = self._SPACES[op]
+        _need(form is not None or sin == sout, "%s is not a square operator" % op)
+        n = self.sizes[sin if form is None else form]
+        x2 = self._rows(x, n, "x")
+        nlev = x2.shape[0]
+        return (x2, self._rows(f, self._fsize(op), "f", rows=nlev, optional=True), self._rows(u, self.sizes[1], "u", rows=nlev, optional=True),
+                self._like(n, nlev, **like))
 
     def richardson_sweep(self, op, x, b, dinv, f=None, u=None, tau=0.0, lev0=0, scale=1.0, flags=0, upd=None):
         """x += dinv * (b - Op x) in place (mimsem_op_richardson_sweep: element pass + gather with the update epilogue);
         upd (optional, same shape) receives the update.  [nlev, n] tensors."""
-        sin, sf, sout = self._SPACES[op]
-        nlev = x.shape[0]
-        assert sin == sout and x.dim() == 2 and x.shape == b.shape == dinv.shape and x.shape[1] == self.sizes[sin]
-        assert upd is None or upd.shape == x.shape
-        check(self.L.mimsem_op_richardson_sweep(self.ctx, OPS[op], lev0, nlev, scale, tau, flags,
-                                                _ptr(f), f.stride(0) if f is not None else 0, _ptr(u), u.stride(0) if u is not None else 0,
-                                                _ptr(b), b.stride(0), _ptr(dinv), dinv.stride(0), _ptr(x), x.stride(0),
-                                                _ptr(upd), upd.stride(0) if upd is not None else 0), "richardson_sweep(%s)" % op)
+        x2, f2, u2, (b2, d2, upd2) = self._sweep_rows(op, x, f, u, b=b, dinv=dinv, upd=upd)
+        check(self.L.mimsem_op_richardson_sweep(self.ctx, OPS[op], lev0, x2.shape[0], scale, tau, flags, *_ps(f2), *_ps(u2), *_ps(b2), *_ps(d2),
+                                                *_ps(x2), *_ps(upd2)), "richardson_sweep(%s)" % op)
         return x
 
     def chebyshev_sweep(self, op, x, b, dinv, p, alpha, beta, f=None, u=None, tau=0.0, lev0=0, scale=1.0, flags=0, upd=None):
         """z = dinv * (b - Op x); p = z + beta p; x += alpha p in place (mimsem_op_chebyshev_sweep: two launches); upd receives z"""
-        sin, sf, sout = self._SPACES[op]
-        nlev = x.shape[0]
-        assert sin == sout and x.dim() == 2 and x.shape == b.shape == dinv.shape == p.shape and x.shape[1] == self.sizes[sin]
-        assert upd is None or upd.shape == x.shape
-        check(self.L.mimsem_op_chebyshev_sweep(self.ctx, OPS[op], lev0, nlev, scale, tau, flags,
-                                               _ptr(f), f.stride(0) if f is not None else 0, _ptr(u), u.stride(0) if u is not None else 0,
-                                               _ptr(b), b.stride(0), _ptr(dinv), dinv.stride(0), float(alpha), float(beta), _ptr(p), p.stride(0),
-                                               _ptr(x), x.stride(0), _ptr(upd), upd.stride(0) if upd is not None else 0), "chebyshev_sweep(%s)" % op)
+        x2, f2, u2, (b2, d2, p2, upd2) = self._sweep_rows(op, x, f, u, b=b, dinv=dinv, p=p, upd=upd)
+        check(self.L.mimsem_op_chebyshev_sweep(self.ctx, OPS[op], lev0, x2.shape[0], scale, tau, flags, *_ps(f2), *_ps(u2), *_ps(b2), *_ps(d2),
+                                               float(alpha), float(beta), *_ps(p2), *_ps(x2), *_ps(upd2)), "chebyshev_sweep(%s)" % op)
         return x
 
     def block_richardson_sweep(self, op, blocks, x, b, f=None, lev0=0, scale=1.0, flags=0, upd=None):
         """x += sum_e R_e^T B_e R_e (b - Op x) in place on 1-forms; blocks [nEl, 2 n1e, 2 n1e] column-major per element
         (mimsem_block_richardson_sweep: element pass, block pass with on-the-fly gathered residual, gather with update)"""
-        nd = 2 * self.n1e
-        assert x.dim() == 2 and x.shape == b.shape and x.shape[1] == self.sizes[1] and blocks.shape == (self.nEl, nd, nd)
-        assert upd is None or upd.shape == x.shape
-        check(self.L.mimsem_block_richardson_sweep(self.ctx, OPS[op], lev0, x.shape[0], scale, flags,
-                                                   _ptr(f), f.stride(0) if f is not None else 0, _ptr(blocks),
-                                                   _ptr(b), b.stride(0), _ptr(x), x.stride(0),
-                                                   _ptr(upd), upd.stride(0) if upd is not None else 0), "block_richardson_sweep(%s)" % op)
+        x2, f2, _, (b2, upd2) = self._sweep_rows(op, x, f, None, form=1, b=b, upd=upd)
+        check(self.L.mimsem_block_richardson_sweep(self.ctx, OPS[op], lev0, x2.shape[0], scale, flags, *_ps(f2),
+                                                   self._blocks(blocks, 2 * self.n1e, "blocks")[0], *_ps(b2), *_ps(x2), *_ps(upd2)),
+              "block_richardson_sweep(%s)" % op)
         return x
+
+    def _elem_scale(self, elem_scale, nlev):
+        return self._rows(elem_scale, self.nEl, "elem_scale", rows=nlev, optional=True)
 
     def block_chebyshev_sweep(self, op, blocks, x, b, p, alpha, beta, f=None, elem_scale=None, lev0=0, scale=1.0, flags=0, upd=None):
         """z = P (b - Op x) with P = sum_e R_e^T (elem_scale[lev, e] B_e) R_e; p = z + beta p; x += alpha p -- in place, three
         launches (mimsem_block_chebyshev_sweep).  blocks [nEl, 2 n1e, 2 n1e] column-major per element."""
-        nd = 2 * self.n1e
-        assert x.dim() == 2 and x.shape == b.shape == p.shape and x.shape[1] == self.sizes[1] and blocks.shape == (self.nEl, nd, nd)
-        assert upd is None or upd.shape == x.shape
-        assert elem_scale is None or elem_scale.shape == (x.shape[0], self.nEl)
-        check(self.L.mimsem_block_chebyshev_sweep(self.ctx, OPS[op], lev0, x.shape[0], scale, flags,
-                                                  _ptr(f), f.stride(0) if f is not None else 0, _ptr(blocks),
-                                                  _ptr(elem_scale), elem_scale.stride(0) if elem_scale is not None else 0,
-                                                  _ptr(b), b.stride(0), alpha, beta, _ptr(p), p.stride(0), _ptr(x), x.stride(0),
-                                                  _ptr(upd), upd.stride(0) if upd is not None else 0), "block_chebyshev_sweep(%s)" % op)
+        x2, f2, _, (b2, p2, upd2) = self._sweep_rows(op, x, f, None, form=1, b=b, p=p, upd=upd)
+        check(self.L.mimsem_block_chebyshev_sweep(self.ctx, OPS[op], lev0, x2.shape[0], scale, flags, *_ps(f2),
+                                                  self._blocks(blocks, 2 * self.n1e, "blocks")[0], *_ps(self._elem_scale(elem_scale, x2.shape[0])),
+                                                  *_ps(b2), alpha, beta, *_ps(p2), *_ps(x2), *_ps(upd2)), "block_chebyshev_sweep(%s)" % op)
         return x
+
+    def _solve_rows(self, b, x, pb, upd):
+        """operands of a fixed-length 1-form solve from x = 0: (x -- new when not given --, nlev, the (address, stride) pairs of b, x, pb, upd)"""
+        b2 = self._rows(b, self.sizes[1], "b")
+        x = torch.empty_like(b) if x is None else x
+        return (x, b2.shape[0], _ps(b2)) + tuple(_ps(t2) for t2 in self._like(self.sizes[1], b2.shape[0], x=x, pb=pb, upd=upd))
 
     def block_chebyshev_solve(self, op, blocks, b, coef, x=None, elem_scale=None, lev0=0, scale=1.0, flags=0, pb=None, upd=None):
         """the whole fixed-length solve from x = 0 as ONE call: len(coef) steps of block_chebyshev_sweep, the first without its operator pass
         and without cleared x / p (mimsem_block_chebyshev_solve; the same bits).  coef: [(alpha, beta)]; pb / upd receive the first / last
         preconditioned residual."""
-        import ctypes
-        nd = 2 * self.n1e
-        assert b.dim() == 2 and b.shape[1] == self.sizes[1] and blocks.shape == (self.nEl, nd, nd)
-        x = torch.empty_like(b) if x is None else x
-        assert x.shape == b.shape and (pb is None or pb.shape == b.shape) and (upd is None or upd.shape == b.shape)
-        assert elem_scale is None or elem_scale.shape == (b.shape[0], self.nEl)
-        flat = (ctypes.c_double * (2 * len(coef)))(*[v for ab in coef for v in ab])
-        check(self.L.mimsem_block_chebyshev_solve(self.ctx, OPS[op], lev0, b.shape[0], scale, flags, None, 0, _ptr(blocks),
-                                                  _ptr(elem_scale), elem_scale.stride(0) if elem_scale is not None else 0,
-                                                  _ptr(b), b.stride(0), len(coef), flat, _ptr(x), x.stride(0),
-                                                  _ptr(pb), pb.stride(0) if pb is not None else 0,
-                                                  _ptr(upd), upd.stride(0) if upd is not None else 0), "block_chebyshev_solve(%s)" % op)
+        x, nlev, pb_, px, ppb, pupd = self._solve_rows(b, x, pb, upd)
+        check(self.L.mimsem_block_chebyshev_solve(self.ctx, OPS[op], lev0, nlev, scale, flags, None, 0, self._blocks(blocks, 2 * self.n1e, "blocks")[0],
+                                                  *_ps(self._elem_scale(elem_scale, nlev)), *pb_, len(coef), _coef(coef), *px, *ppb, *pupd),
+              "block_chebyshev_solve(%s)" % op)
         return x
 
     def fric_chebyshev_solve(self, blocks, b, coef, tau, exner, exner_s, x=None, elem_scale=None, lev0=0, scale=1.0, flags=1, pb=None, upd=None):
         """block_chebyshev_solve for (M1 + M1ray(tau)) x = b (mimsem_fric_chebyshev_solve): the element pass of every step is UMAT_FRIC.  exner
         [nlev, n2]: the levels lev0.., exner_s [n2]: level 0; tau = 0 or exner = None: block_chebyshev_solve("UMAT", ...) itself."""
-        import ctypes
-        nd = 2 * self.n1e
-        assert b.dim() == 2 and b.shape[1] == self.sizes[1] and blocks.shape == (self.nEl, nd, nd)
-        x = torch.empty_like(b) if x is None else x
-        assert x.shape == b.shape and (pb is None or pb.shape == b.shape) and (upd is None or upd.shape == b.shape)
-        assert elem_scale is None or elem_scale.shape == (b.shape[0], self.nEl)
-        assert exner is None or (exner.shape == (b.shape[0], self.sizes[2]) and exner.stride(1) == 1 and
-                                 exner_s is not None and exner_s.shape == (self.sizes[2],) and exner_s.is_contiguous())
-        flat = (ctypes.c_double * (2 * len(coef)))(*[v for ab in coef for v in ab])
-        check(self.L.mimsem_fric_chebyshev_solve(self.ctx, OPS["UMAT"], lev0, b.shape[0], scale, flags, None, 0, _ptr(blocks),
-                                                 _ptr(elem_scale), elem_scale.stride(0) if elem_scale is not None else 0,
-                                                 _ptr(b), b.stride(0), len(coef), flat, _ptr(x), x.stride(0),
-                                                 _ptr(pb), pb.stride(0) if pb is not None else 0,
-                                                 _ptr(upd), upd.stride(0) if upd is not None else 0,
-                                                 float(tau), _ptr(exner), exner.stride(0) if exner is not None else 0, _ptr(exner_s)),
+        x, nlev, pb_, px, ppb, pupd = self._solve_rows(b, x, pb, upd)
+        ex2 = self._rows(exner, self.sizes[2], "exner", rows=nlev, optional=True)
+        check(self.L.mimsem_fric_chebyshev_solve(self.ctx, OPS["UMAT"], lev0, nlev, scale, flags, None, 0, self._blocks(blocks, 2 * self.n1e, "blocks")[0],
+                                                 *_ps(self._elem_scale(elem_scale, nlev)), *pb_, len(coef), _coef(coef), *px, *ppb, *pupd,
+                                                 float(tau), *_ps(ex2), self._vec(exner_s, self.sizes[2], "exner_s", optional=ex2 is None)),
               "fric_chebyshev_solve")
         return x
 
@@ -372,46 +422,29 @@ class Engine:
         """the reference's PCBJACOBI blocks (PCBJacobiSetTotalBlocks(size*nElsX*nElsX)): the ASSEMBLED diagonal block of the slots each element
         owns, [nlev, nEl, nd, nd] row-major for geometry levels lev0.. (mimsem_owned_blocks_build; f: [nlev, n_field] rows); invert: their exact
         inverses (mimsem_block_inverse), what owned_blocks_apply and owned_block_chebyshev_solve take"""
-        form = self._OWNED_FORM[op]
-        nd = self.owned_rows(form)
-        _need(f is None or (f.dim() == 2 and f.shape[0] == nlev), "owned_blocks: f must be [nlev, n] rows")
-        out = torch.empty(nlev, self.nEl, nd, nd, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_owned_blocks_build(self.ctx, OPS[op], lev0, nlev, scale, flags, _ptr(f), f.stride(0) if f is not None else 0, _ptr(out)),
+        nd = self.owned_rows(self._OWNED_FORM[op])
+        out = self._new(nlev, self.nEl, nd, nd)
+        check(self.L.mimsem_owned_blocks_build(self.ctx, OPS[op], lev0, nlev, scale, flags, *_ps(self._rows(f, self._fsize(op), "f", rows=nlev, optional=True)), _ptr(out)),
               "mimsem_owned_blocks_build(%s)" % op)
         if invert:
-            check(self.L.mimsem_block_inverse(self.ctx, nlev * self.nEl, nd, out.data_ptr()), "block_inverse")
+            check(self.L.mimsem_block_inverse(self.ctx, nlev * self.nEl, nd, _ptr(out)), "block_inverse")
         return out
 
     def owned_blocks_apply(self, form, blocks, x, out=None):
         """y[slots of block k] = B_k x[slots of block k] for every owned block and every row of x (mimsem_owned_blocks_apply, one launch); blocks
         [nEl, nd, nd] (one set for all rows) or [nlev, nEl, nd, nd].  Slots outside every block keep what `out` held (zeros when not given)."""
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        nlev, nd = x2.shape[0], self.owned_rows(form)
-        _need(x2.shape[1] == self.sizes[form] and x2.stride(1) == 1, "owned_blocks_apply: x rows of the form's length")
-        _need(blocks.is_contiguous() and blocks.shape[-3:] == (self.nEl, nd, nd) and (blocks.dim() == 3 or (blocks.dim() == 4 and blocks.shape[0] == nlev)),
-              "owned_blocks_apply: blocks [nEl, nd, nd] or [nlev, nEl, nd, nd]")
-        y = out if out is not None else torch.zeros(nlev, self.sizes[form], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        _need(y2.shape == x2.shape and y2.stride(1) == 1, "owned_blocks_apply: out like x")
-        check(self.L.mimsem_owned_blocks_apply(self.ctx, form, nlev, _ptr(blocks), blocks.stride(0) if blocks.dim() == 4 else 0,
-                                               _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0)), "mimsem_owned_blocks_apply")
+        x2 = self._rows(x, self.sizes[form], "x")
+        y, y2 = self._out(out, x2.shape[0], self.sizes[form], exact=True, zero=True)
+        check(self.L.mimsem_owned_blocks_apply(self.ctx, form, x2.shape[0], *self._blocks(blocks, self.owned_rows(form), "blocks", nlev=x2.shape[0]),
+                                               *_ps(x2), *_ps(y2)), "mimsem_owned_blocks_apply")
         return y if x.dim() == 2 else y2[0]
 
     def owned_block_chebyshev_solve(self, blocks, b, coef, x=None, lev0=0, scale=1.0, flags=0, pb=None, upd=None):
         """block_chebyshev_solve with the owned-block preconditioner (mimsem_owned_block_chebyshev_solve): len(coef) steps of {element pass,
         owned-block pass} from x = 0 on Umat; blocks: the inverses, [nEl, nd, nd] or [nlev, nEl, nd, nd]"""
-        nd = self.owned_rows(1)
-        _need(b.dim() == 2 and b.shape[1] == self.sizes[1] and b.stride(1) == 1, "owned_block_chebyshev_solve: b [nlev, n1]")
-        _need(blocks.is_contiguous() and blocks.shape[-3:] == (self.nEl, nd, nd) and (blocks.dim() == 3 or (blocks.dim() == 4 and blocks.shape[0] == b.shape[0])),
-              "owned_block_chebyshev_solve: blocks [nEl, nd, nd] or [nlev, nEl, nd, nd]")
-        x = torch.empty_like(b) if x is None else x
-        for t in (x, pb, upd):
-            _need(t is None or (t.shape == b.shape and t.stride(1) == 1), "owned_block_chebyshev_solve: x / pb / upd like b")
-        flat = (C.c_double * (2 * len(coef)))(*[v for ab in coef for v in ab])
-        check(self.L.mimsem_owned_block_chebyshev_solve(self.ctx, OPS["UMAT"], lev0, b.shape[0], scale, flags, _ptr(blocks),
-                                                        blocks.stride(0) if blocks.dim() == 4 else 0, _ptr(b), b.stride(0), len(coef), flat,
-                                                        _ptr(x), x.stride(0), _ptr(pb), pb.stride(0) if pb is not None else 0,
-                                                        _ptr(upd), upd.stride(0) if upd is not None else 0), "owned_block_chebyshev_solve")
+        x, nlev, pb_, px, ppb, pupd = self._solve_rows(b, x, pb, upd)
+        check(self.L.mimsem_owned_block_chebyshev_solve(self.ctx, OPS["UMAT"], lev0, nlev, scale, flags, *self._blocks(blocks, self.owned_rows(1), "blocks", nlev=nlev),
+                                                        *pb_, len(coef), _coef(coef), *px, *ppb, *pupd), "owned_block_chebyshev_solve")
         return x
 
     def sw_dual_chebyshev(self, coefA, blocks, b1, p1, x1, upd1, coefB, tau, h, u, b0, dinv, p0, x0, upd0, pb1=None, pb0=None):
@@ -419,62 +452,41 @@ class Engine:
         on Phmat_up) of one shallow-water Picard iteration, both from x = 0, in SHARED launches (mimsem_sw_dual_chebyshev): the same bits as the
         two sequences of block_chebyshev_sweep / chebyshev_sweep calls on zero iterates.  [1, n] tensors; x1, p1, x0, p0 are outputs / workspaces
         (need not be cleared); upd1 / upd0 receive the last step's preconditioned residual, pb1 / pb0 the first's (P b1, dinv b0)."""
-        nd = 2 * self.n1e
-        for t, n in ((b1, self.sizes[1]), (p1, self.sizes[1]), (x1, self.sizes[1]), (u, self.sizes[1]), (h, self.sizes[2]), (b0, self.sizes[0]), (dinv, self.sizes[0]),
-                     (p0, self.sizes[0]), (x0, self.sizes[0])):
-            assert t.dim() == 2 and t.shape == (1, n) and t.is_contiguous(), (tuple(t.shape), n)
-        assert blocks.shape == (self.nEl, nd, nd) and blocks.is_contiguous()
-        for t, ref in ((upd1, x1), (pb1, x1), (upd0, x0), (pb0, x0)):
-            assert t is None or (t.shape == ref.shape and t.stride(1) == 1)
-        ca = np.ascontiguousarray(np.asarray(coefA, dtype=np.float64).reshape(-1, 2))
-        cb = np.ascontiguousarray(np.asarray(coefB, dtype=np.float64).reshape(-1, 2))
-        check(self.L.mimsem_sw_dual_chebyshev(self.ctx, ca.shape[0], ca.ctypes.data, _ptr(blocks), _ptr(b1), _ptr(p1), _ptr(x1), _ptr(upd1), _ptr(pb1),
-                                              cb.shape[0], cb.ctypes.data, float(tau), _ptr(h), _ptr(u), _ptr(b0), _ptr(dinv), _ptr(p0), _ptr(x0), _ptr(upd0), _ptr(pb0)),
-              "sw_dual_chebyshev")
+        n0, n1, n2 = self.sizes[0], self.sizes[1], self.sizes[2]
+        v = lambda t, n, name, optional=False: self._vec(t, n, name, optional=optional)
+        ca, pca = _host(np.asarray(coefA, dtype=np.float64).reshape(-1, 2), np.float64)
+        cb, pcb = _host(np.asarray(coefB, dtype=np.float64).reshape(-1, 2), np.float64)
+        check(self.L.mimsem_sw_dual_chebyshev(self.ctx, ca.shape[0], pca, self._blocks(blocks, 2 * self.n1e, "blocks")[0], v(b1, n1, "b1"), v(p1, n1, "p1"),
+                                              v(x1, n1, "x1"), v(upd1, n1, "upd1", True), v(pb1, n1, "pb1", True), cb.shape[0], pcb, float(tau), v(h, n2, "h"),
+                                              v(u, n1, "u"), v(b0, n0, "b0"), v(dinv, n0, "dinv"), v(p0, n0, "p0"), v(x0, n0, "x0"), v(upd0, n0, "upd0", True),
+                                              v(pb0, n0, "pb0", True)), "sw_dual_chebyshev")
+
+    def _apply_exner(self, op, x, exner, exner_s, tau, lev0, scale, alpha, flags, out):
+        """the one body of apply_ray and apply_fric: mimsem_op_apply_up with exner as the field and exner_s [n2] (one row) in the velocity's place"""
+        x2 = self._rows(x, self.sizes[1], "x")
+        f2 = self._rows(exner, self.sizes[2], "exner", rows=x2.shape[0])
+        y, y2 = self._out(out, x2.shape[0], self.sizes[1])
+        check(self.L.mimsem_op_apply_up(self.ctx, OPS[op], lev0, x2.shape[0], scale, tau, flags, *_ps(f2), self._vec(exner_s, self.sizes[2], "exner_s"), 0,
+                                        *_ps(x2), *_ps(y2), alpha), "mimsem_op_apply_up(%s)" % op)
+        return y if x.dim() == 2 else y2[0]
 
     def apply_ray(self, x, exner, exner_s, dt, lev0=0, scale=1.0, alpha=1.0, flags=0, out=None):
         """Umat_ray (Held-Suarez friction): x [nlev, n1], exner [nlev, n2] (levels lev0..), exner_s [n2] = level 0."""
-        x2 = x if x.dim() == 2 else x.unsqueeze(0); f2 = exner if exner.dim() == 2 else exner.unsqueeze(0)
-        nlev = x2.shape[0]
-        assert x2.shape[1] == self.sizes[1] and f2.shape == (nlev, self.sizes[2]) and exner_s.shape == (self.sizes[2],)
-        y = out if out is not None else torch.empty(nlev, self.sizes[1], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        check(self.L.mimsem_op_apply_up(self.ctx, OPS["UMAT_RAY"], lev0, nlev, scale, dt, flags, _ptr(f2), f2.stride(0),
-                                        _ptr(exner_s), 0, _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0), alpha),
-              "mimsem_op_apply_up(UMAT_RAY)")
-        return y if x.dim() == 2 else y2[0]
+        return self._apply_exner("UMAT_RAY", x, exner, exner_s, dt, lev0, scale, alpha, flags, out)
 
     def apply_fric(self, x, exner, exner_s, tau, lev0=0, scale=1.0, alpha=1.0, flags=0, out=None):
         """M1 + M1ray(tau) in one element pass (MIMSEM_OP_UMAT_FRIC; eul/Euler_2.cpp:1431-1451): Umat with the vertical flag whose point weights
         carry 1 + tau k_v.  Arguments as apply_ray; flags: FLAG_ACCUM or 0."""
-        x2 = x if x.dim() == 2 else x.unsqueeze(0); f2 = exner if exner.dim() == 2 else exner.unsqueeze(0)
-        nlev = x2.shape[0]
-        assert x2.shape[1] == self.sizes[1] and f2.shape == (nlev, self.sizes[2]) and exner_s.shape == (self.sizes[2],)
-        y = out if out is not None else torch.empty(nlev, self.sizes[1], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        check(self.L.mimsem_op_apply_up(self.ctx, OPS["UMAT_FRIC"], lev0, nlev, scale, tau, flags, _ptr(f2), f2.stride(0),
-                                        _ptr(exner_s), 0, _ptr(x2), x2.stride(0), _ptr(y2), y2.stride(0), alpha),
-              "mimsem_op_apply_up(UMAT_FRIC)")
-        return y if x.dim() == 2 else y2[0]
+        return self._apply_exner("UMAT_FRIC", x, exner, exner_s, tau, lev0, scale, alpha, flags, out)
 
     def prepare_apply(self, op, x, f=None, lev0=0, scale=1.0, flags=0, alpha=1.0, out=None):
         """Validate once, return (call, y): `call()` re-issues the same mimsem_op_apply with pre-marshalled
         arguments (the buffers are fixed) -- the host-side fast path for time-step loops and bench.py."""
-        sin, sf, sout = self._SPACES[op]
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        nlev = x2.shape[0]
-        assert x2.shape[1] == self.sizes[sin]
-        f2 = None
-        if sf is not None:
-            f2 = f if f.dim() == 2 else f.unsqueeze(0)
-            assert f2.shape == (nlev, self.sizes[sf])
-        y = out if out is not None else torch.empty(nlev, self.sizes[sout], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
+        x2, f2, y, y2 = self._op_args(op, x, f, out)
+        (pf, sf), (px, sx), (py, sy) = _ps(f2), _ps(x2), _ps(y2)
         fn = self.L.mimsem_op_apply
-        args = (self.ctx, C.c_int(OPS[op]), C.c_int(lev0), C.c_int(nlev), C.c_double(scale), C.c_uint(flags),
-                C.c_void_p(_ptr(f2)), C.c_longlong(f2.stride(0) if f2 is not None else 0),
-                C.c_void_p(_ptr(x2)), C.c_longlong(x2.stride(0)), C.c_void_p(_ptr(y2)), C.c_longlong(y2.stride(0)),
-                C.c_double(alpha))
+        args = (self.ctx, C.c_int(OPS[op]), C.c_int(lev0), C.c_int(x2.shape[0]), C.c_double(scale), C.c_uint(flags), C.c_void_p(pf), C.c_longlong(sf),
+                C.c_void_p(px), C.c_longlong(sx), C.c_void_p(py), C.c_longlong(sy), C.c_double(alpha))
         keep = (x2, f2, y2)
 
         def call(_fn=fn, _args=args, _keep=keep):
@@ -484,89 +496,78 @@ class Engine:
         return call, y
 
     def element_matrices(self, op, f=None, lev=0, scale=1.0, flags=0):
-        esz = self.L.mimsem_op_elmat_size(self.ctx, OPS[op])
-        out = torch.empty(self.nEl, esz, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_op_element_matrices(self.ctx, OPS[op], lev, scale, flags, _ptr(f), _ptr(out)),
+        out = self._new(self.nEl, self.L.mimsem_op_elmat_size(self.ctx, OPS[op]))
+        check(self.L.mimsem_op_element_matrices(self.ctx, OPS[op], lev, scale, flags, self._vec(f, self._fsize(op), "f", optional=True), _ptr(out)),
               "mimsem_op_element_matrices(%s)" % op)
         return out
+
+    def _elmats_exner(self, op, exner, exner_s, tau, lev, scale):
+        """the one body of element_matrices_ray and element_matrices_fric: exner [n2] at the level, exner_s [n2] at level 0"""
+        out = self._new(self.nEl, self.L.mimsem_op_elmat_size(self.ctx, OPS[op]))
+        check(self.L.mimsem_op_element_matrices_ex(self.ctx, OPS[op], lev, scale, tau, 0, self._vec(exner, self.sizes[2], "exner"),
+                                                   self._vec(exner_s, self.sizes[2], "exner_s"), _ptr(out)), "mimsem_op_element_matrices_ex(%s)" % op)
+        return out
+
+    def element_matrices_ray(self, exner, exner_s, dt, lev=0, scale=1.0):
+        return self._elmats_exner("UMAT_RAY", exner, exner_s, dt, lev, scale)
+
+    def element_matrices_fric(self, exner, exner_s, tau, lev=0, scale=1.0):
+        """the element blocks of M1 + M1ray(tau) at one level (what MatAXPY(M1->M, 1.0, M1ray->M) leaves in M1, eul/Euler_2.cpp:1448)"""
+        return self._elmats_exner("UMAT_FRIC", exner, exner_s, tau, lev, scale)
 
     def elem_block_pc(self, op, f=None, lev=0, scale=1.0, flags=0, out=None):
         """mimsem_elem_block_pc_build: D_e (A_e)^-1 D_e of a 1-form mass operator (UMAT, UHMAT with f = the depth row) in one launch,
         [nEl, 2 n1e, 2 n1e] -- the blocks mimsem_ksp_set_pc_bjacobi builds, for blocks_apply(1, ..., transpose=True)"""
         nd = 2 * self.n1e
-        out = torch.empty(self.nEl, nd, nd, dtype=torch.float64, device=self.device) if out is None else out
-        _need(out.shape == (self.nEl, nd, nd) and out.is_contiguous(), "out: a contiguous [nEl, 2 n1e, 2 n1e] tensor")
-        check(self.L.mimsem_elem_block_pc_build(self.ctx, OPS[op], lev, scale, flags, _ptr(f), _ptr(out)), "mimsem_elem_block_pc_build(%s)" % op)
+        out = self._new(self.nEl, nd, nd) if out is None else out
+        check(self.L.mimsem_elem_block_pc_build(self.ctx, OPS[op], lev, scale, flags, self._vec(f, self._fsize(op), "f", optional=True), self._blocks(out, nd, "out")[0]),
+              "mimsem_elem_block_pc_build(%s)" % op)
         return out
 
     def elem_block_pc_levels(self, op, nlev, f=None, lev0=0, lev_step=1, scale=1.0, flags=0, out=None):
         """mimsem_elem_block_pc_build_levels: the blocks of elem_block_pc for nlev rows in one launch, [nlev, nEl, 2 n1e, 2 n1e]; row r at
         geometry level lev0 + r lev_step with the field row f[r] (UMAT, UHMAT, UTMAT_H)"""
         nd = 2 * self.n1e
-        out = torch.empty(nlev, self.nEl, nd, nd, dtype=torch.float64, device=self.device) if out is None else out
-        _need(out.shape == (nlev, self.nEl, nd, nd) and out.is_contiguous(), "out: a contiguous [nlev, nEl, 2 n1e, 2 n1e] tensor")
-        _need(f is None or (f.dim() == 2 and f.shape == (nlev, self.sizes[2]) and f.stride(1) == 1), "f: [nlev, n2] with contiguous rows")
-        check(self.L.mimsem_elem_block_pc_build_levels(self.ctx, OPS[op], lev0, lev_step, nlev, scale, flags, _ptr(f),
-                                                       f.stride(0) if f is not None else 0, _ptr(out)), "mimsem_elem_block_pc_build_levels(%s)" % op)
-        return out
-
-    def element_matrices_ray(self, exner, exner_s, dt, lev=0, scale=1.0):
-        esz = self.L.mimsem_op_elmat_size(self.ctx, OPS["UMAT_RAY"])
-        out = torch.empty(self.nEl, esz, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_op_element_matrices_ex(self.ctx, OPS["UMAT_RAY"], lev, scale, dt, 0, _ptr(exner), _ptr(exner_s), _ptr(out)),
-              "mimsem_op_element_matrices_ex(UMAT_RAY)")
-        return out
-
-    def element_matrices_fric(self, exner, exner_s, tau, lev=0, scale=1.0):
-        """the element blocks of M1 + M1ray(tau) at one level (what MatAXPY(M1->M, 1.0, M1ray->M) leaves in M1, eul/Euler_2.cpp:1448)"""
-        esz = self.L.mimsem_op_elmat_size(self.ctx, OPS["UMAT_FRIC"])
-        out = torch.empty(self.nEl, esz, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_op_element_matrices_ex(self.ctx, OPS["UMAT_FRIC"], lev, scale, tau, 0, _ptr(exner), _ptr(exner_s), _ptr(out)),
-              "mimsem_op_element_matrices_ex(UMAT_FRIC)")
+        out = self._new(nlev, self.nEl, nd, nd) if out is None else out
+        _need(out.dim() == 4, "out: a contiguous [nlev, nEl, 2 n1e, 2 n1e] tensor")
+        check(self.L.mimsem_elem_block_pc_build_levels(self.ctx, OPS[op], lev0, lev_step, nlev, scale, flags,
+                                                       *_ps(self._rows(f, self.sizes[2], "f", rows=nlev, optional=True)), self._blocks(out, nd, "out", nlev=nlev)[0]),
+              "mimsem_elem_block_pc_build_levels(%s)" % op)
         return out
 
     def blocks_apply(self, form, blocks, x, transpose=False, alpha=1.0, accum=False, out=None, elem_scale=None):
         """y = alpha * sum_e P_e^T B_e P_e x with caller-supplied element blocks [nEl, nd, nd] (same on every level, optionally
         times elem_scale[lev, e]) or [nlev, nEl, nd, nd]; form 0/1/2 (1-forms: nd = 2*n1e, x-edges then y-edges)."""
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
+        x2 = self._rows(x, self.sizes[form], "x")
         nlev = x2.shape[0]
-        nd = {0: self.n0e, 1: 2 * self.n1e, 2: self.n2e}[form]
-        assert blocks.shape[-3:] == (self.nEl, nd, nd) and x2.shape[1] == self.sizes[form]
-        bstride = blocks.stride(0) if blocks.dim() == 4 else 0
-        assert blocks.dim() == 3 or blocks.shape[0] == nlev
-        y = out if out is not None else torch.empty(nlev, self.sizes[form], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        flags = (4 if transpose else 0) | (2 if accum else 0)
-        if elem_scale is not None:
-            assert blocks.dim() == 3 and elem_scale.shape == (nlev, self.nEl)
-        check(self.L.mimsem_elem_blocks_apply(self.ctx, form, nlev, flags, _ptr(blocks), bstride, _ptr(elem_scale),
-                                              elem_scale.stride(0) if elem_scale is not None else 0, _ptr(x2), x2.stride(0),
-                                              _ptr(y2), y2.stride(0), alpha), "mimsem_elem_blocks_apply")
+        pb, bstride = self._blocks(blocks, {0: self.n0e, 1: 2 * self.n1e, 2: self.n2e}[form], "blocks", nlev=nlev)
+        _need(elem_scale is None or blocks.dim() == 3, "elem_scale goes with one set of blocks [nEl, nd, nd]")
+        y, y2 = self._out(out, nlev, self.sizes[form])
+        check(self.L.mimsem_elem_blocks_apply(self.ctx, form, nlev, (4 if transpose else 0) | (2 if accum else 0), pb, bstride,
+                                              *_ps(self._elem_scale(elem_scale, nlev)), *_ps(x2), *_ps(y2), alpha), "mimsem_elem_blocks_apply")
         return y if x.dim() == 2 else y2[0]
-
-    def _tsw_vec(self, form, t, what):
-        _need(t is not None and t.dim() == 1 and t.shape[0] == self.sizes[form], "%s: a [%d] row" % (what, self.sizes[form]))
-        return _ptr(t)
 
     def tsw_diagnose(self, h, S, u, m2inv, s=None, Phi=None, h2=None):
         """mimsem_tsw_diagnose: s = M2h(h)^-1 M2 S, Phi = K(u) u + 1/2 M2 S + 1/4 M2h(s) h, h2 = M2^-1 M2h(h) h in one launch
         (src/ThermalSW_EEC_2.cpp diagnose_s, diagnose_Phi, rhs_u).  h, S: 2-form rows, u: a 1-form row, m2inv: the WMATINV element
         matrices [nEl, n2e * n2e]."""
-        _need(m2inv.numel() == self.nEl * self.n2e * self.n2e, "m2inv: the WMATINV element matrices")
+        n1, n2 = self.sizes[1], self.sizes[2]
+        v = lambda t, n, name: self._vec(t, n, name)
         s = torch.empty_like(h) if s is None else s
         Phi = torch.empty_like(h) if Phi is None else Phi
         h2 = torch.empty_like(h) if h2 is None else h2
-        check(self.L.mimsem_tsw_diagnose(self.ctx, self._tsw_vec(2, h, "h"), self._tsw_vec(2, S, "S"), self._tsw_vec(1, u, "u"), _ptr(m2inv),
-                                         self._tsw_vec(2, s, "s"), self._tsw_vec(2, Phi, "Phi"), self._tsw_vec(2, h2, "h2")), "mimsem_tsw_diagnose")
+        check(self.L.mimsem_tsw_diagnose(self.ctx, v(h, n2, "h"), v(S, n2, "S"), v(u, n1, "u"), v(m2inv, self.nEl * self.n2e * self.n2e, "m2inv"),
+                                         v(s, n2, "s"), v(Phi, n2, "Phi"), v(h2, n2, "h2")), "mimsem_tsw_diagnose")
         return s, Phi, h2
 
     def tsw_update(self, F, G, grad_s, s, m2inv, h_i, S_i, h_j, S_j, alpha, beta, dt):
         """mimsem_tsw_update: h_j <- alpha h_i + beta (h_j - dt E21 F), S_j <- alpha S_i + beta S_j - beta dt M2^-1 fS with
         fS = 1/2 M2 E21 G + 1/2 M2h(s) E21 F + K(grad_s) F (src/ThermalSW_EEC_2.cpp solve_rk, rhs_S), h_j and S_j in place"""
-        _need(m2inv.numel() == self.nEl * self.n2e * self.n2e, "m2inv: the WMATINV element matrices")
-        check(self.L.mimsem_tsw_update(self.ctx, self._tsw_vec(1, F, "F"), self._tsw_vec(1, G, "G"), self._tsw_vec(1, grad_s, "grad_s"),
-                                       self._tsw_vec(2, s, "s"), _ptr(m2inv), self._tsw_vec(2, h_i, "h_i"), self._tsw_vec(2, S_i, "S_i"),
-                                       self._tsw_vec(2, h_j, "h_j"), self._tsw_vec(2, S_j, "S_j"), alpha, beta, dt), "mimsem_tsw_update")
+        n1, n2 = self.sizes[1], self.sizes[2]
+        v = lambda t, n, name: self._vec(t, n, name)
+        check(self.L.mimsem_tsw_update(self.ctx, v(F, n1, "F"), v(G, n1, "G"), v(grad_s, n1, "grad_s"), v(s, n2, "s"),
+                                       v(m2inv, self.nEl * self.n2e * self.n2e, "m2inv"), v(h_i, n2, "h_i"), v(S_i, n2, "S_i"), v(h_j, n2, "h_j"),
+                                       v(S_j, n2, "S_j"), alpha, beta, dt), "mimsem_tsw_update")
         return h_j, S_j
 
     def wvec(self, rho, lev0=0, scale=1.0, vert_scale=True, out=None):
@@ -581,48 +582,37 @@ class Engine:
         return self.apply("WTQUMAT", vel1, f=vel2, lev0=lev0, scale=scale, out=out)
 
     def pvec(self, lev0=0, nlev=1, scale=1.0, h2=None):
-        y = torch.empty(nlev, self.sizes[0], dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_pvec(self.ctx, lev0, nlev, scale, _ptr(h2), h2.stride(0) if h2 is not None else 0,
-                                 _ptr(y), y.stride(0)), "mimsem_pvec")
+        y = self._new(nlev, self.sizes[0])
+        check(self.L.mimsem_pvec(self.ctx, lev0, nlev, scale, *_ps(self._rows(h2, self.sizes[2], "h2", min_rows=nlev, optional=True)), *_ps(y)), "mimsem_pvec")
         return y
 
     def incidence(self, which, x):
         """which: 'E10','E21','E12','E01'"""
         w = dict(E10=0, E21=1, E12=2, E01=3)[which]
-        nout = {0: self.sizes[1], 1: self.sizes[2], 2: self.sizes[1], 3: self.sizes[0]}[w]
-        nin = {0: self.sizes[0], 1: self.sizes[1], 2: self.sizes[2], 3: self.sizes[1]}[w]
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        assert x2.shape[1] == nin, (which, x2.shape, nin)          # the C ABI takes raw pointers: lengths are checked here
-        y = torch.empty(x2.shape[0], nout, dtype=torch.float64, device=self.device)      # (every entry is written: faces directly, edges / nodes by the gather pass over all slots)
-        check(self.L.mimsem_incidence_apply(self.ctx, w, x2.shape[0], _ptr(x2), x2.stride(0), _ptr(y), y.stride(0)), "incidence")
+        x2 = self._rows(x, self.sizes[(0, 1, 2, 1)[w]], "x of " + which)
+        y = self._new(x2.shape[0], self.sizes[(1, 2, 1, 0)[w]])      # (every entry is written: faces directly, edges / nodes by the gather pass over all slots)
+        check(self.L.mimsem_incidence_apply(self.ctx, w, x2.shape[0], *_ps(x2), *_ps(y)), "incidence")
         return y if x.dim() == 2 else y[0]
 
     def interp_quad(self, form, x, push_forward=True):
         """Row A7, Geom::interp0 / interp1_l|_g / interp2_l|_g (eul/Geom.cpp:328-417) at every quadrature point:
         x [nlev, n_form] (or [n_form]) -> [nlev, nEl, mp12] (forms 0, 2) or [nlev, nEl, mp12, 2] (1-forms)."""
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        assert x2.shape[1] == self.sizes[form], (form, x2.shape)
-        nc = 2 if form == 1 else 1
-        out = torch.empty(x2.shape[0], self.nEl*self.mp12*nc, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_interp_quad(self.ctx, form, 1 if push_forward else 0, x2.shape[0], _ptr(x2), x2.stride(0),
-                                        _ptr(out), out.stride(0)), "interp_quad")
+        x2 = self._rows(x, self.sizes[form], "x")
+        out = self._new(x2.shape[0], self.nEl * self.mp12 * (2 if form == 1 else 1))
+        check(self.L.mimsem_interp_quad(self.ctx, form, 1 if push_forward else 0, x2.shape[0], *_ps(x2), *_ps(out)), "interp_quad")
         out = out.view(x2.shape[0], self.nEl, self.mp12, 2) if form == 1 else out.view(x2.shape[0], self.nEl, self.mp12)
         return out if x.dim() == 2 else out[0]
 
     def energetics_horiz(self, velx, rho, rt, exner, theta, out=None):
         """mimsem_euler_energetics_horiz: [keh, ie, entr, mass] of Euler::diagnostics (eul/Euler_2.cpp:600-744) over the rows' levels
         0 .. nlev-1 as a device tensor of 4; velx [nlev, n1], the others [nlev, n2] (rows contiguous, any row stride)"""
-        nlev = velx.shape[0] if velx.dim() == 2 else -1
-        _need(velx.dim() == 2 and velx.shape[1] == self.sizes[1] and velx.stride(1) == 1, "velx: [nlev, n1] with contiguous rows")
-        for t, name in ((rho, "rho"), (rt, "rt"), (exner, "exner"), (theta, "theta")):
-            _need(t.dim() == 2 and t.shape == (nlev, self.sizes[2]) and t.stride(1) == 1, "%s: [nlev, n2] with contiguous rows" % name)
-        out = torch.empty(4, dtype=torch.float64, device=self.device) if out is None else out
-        _need(out.numel() == 4 and out.is_contiguous(), "out: 4 contiguous doubles")
-        for t in (velx, rho, rt, exner, theta):             # (rows may lie apart -- a slice of a wider array -- so not _ptr, which wants one block)
-            _need(t.dtype == torch.float64 and t.is_cuda and (nlev == 1 or t.stride(0) >= 0), "float64 device rows")
-        st = lambda t: t.stride(0) if nlev > 1 else 0
-        check(self.L.mimsem_euler_energetics_horiz(self.ctx, nlev, velx.data_ptr(), st(velx), rho.data_ptr(), st(rho), rt.data_ptr(), st(rt),
-                                                   exner.data_ptr(), st(exner), theta.data_ptr(), st(theta), _ptr(out)), "euler_energetics_horiz")
+        vx = self._rows(velx, self.sizes[1], "velx", strided="r")
+        nlev = vx.shape[0]
+        r2, t2, e2, th2 = self._like(self.sizes[2], nlev, strided="r", rho=rho, rt=rt, exner=exner, theta=theta)
+        out = self._new(4) if out is None else out
+        ps = _ps if nlev > 1 else (lambda v2: (_ps(v2)[0], 0))                       # (one level: row stride 0)
+        check(self.L.mimsem_euler_energetics_horiz(self.ctx, nlev, *ps(vx), *ps(r2), *ps(t2), *ps(e2), *ps(th2), self._vec(out, 4, "out")),
+              "euler_energetics_horiz")
         return out
 
     def energetics_column(self, velz, rho, zv, out=None):
@@ -632,11 +622,10 @@ class Engine:
         the DeviceMesh is made"""
         _need(self.nk >= 2, "energetics_column needs at least one interface (nk >= 2)")
         self._col(velz, self.nk - 1, "velz"); self._col(rho, self.nk, "rho"); self._col(zv, self.nk, "zv")
-        out = torch.empty(4, dtype=torch.float64, device=self.device) if out is None else out
-        _need(out.numel() == 4 and out.is_contiguous(), "out: 4 contiguous doubles")
+        out = self._new(4) if out is None else out
         if self._linear_inv is None:                        # (first call: one allocation and the launches of colop_blocks -- warm up before recording)
             self._linear_inv = self.colop_blocks("LINEAR_INV")
-        check(self.L.mimsem_euler_energetics_column(self.ctx, _ptr(velz), _ptr(rho), _ptr(zv), _ptr(self._linear_inv), _ptr(out)),
+        check(self.L.mimsem_euler_energetics_column(self.ctx, _ptr(velz), _ptr(rho), _ptr(zv), _ptr(self._linear_inv), self._vec(out, 4, "out")),
               "euler_energetics_column")
         return out
 
@@ -644,76 +633,64 @@ class Engine:
         """mimsem_horiz_bernoulli: HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470) of every level in one launch; velx1, velx2 [nk, n1],
         velz1, velz2 [nk-1, n2] (horizontal layout) -> Phi [nk, n2].  Rows contiguous, any row stride (the two of a pair share it); velx1 is
         velx2 and velz1 is velz2 are allowed"""
-        nk = velx1.shape[0] if velx1.dim() == 2 else -1
-        _need(nk >= 2, "bernoulli needs at least one interface (nk >= 2)")
-        for t, rows, n, name in ((velx1, nk, 1, "velx1"), (velx2, nk, 1, "velx2"), (velz1, nk - 1, 2, "velz1"), (velz2, nk - 1, 2, "velz2")):
-            _need(t.dim() == 2 and t.shape == (rows, self.sizes[n]) and t.stride(1) == 1 and t.stride(0) >= 0,
-                  "%s: [%d, n%d] with contiguous rows" % (name, rows, n))
-            _need(t.dtype == torch.float64 and t.is_cuda, "float64 device rows")
-        _need(velx1.stride(0) == velx2.stride(0), "velx1, velx2: one row stride")
-        _need(nk == 2 or velz1.stride(0) == velz2.stride(0), "velz1, velz2: one row stride")
-        out = torch.empty(nk, self.sizes[2], dtype=torch.float64, device=self.device) if out is None else out
-        _need(out.dim() == 2 and out.shape == (nk, self.sizes[2]) and out.stride(1) == 1 and out.stride(0) >= self.sizes[2]
-              and out.dtype == torch.float64 and out.is_cuda, "out: [nk, n2] float64 device rows")
-        check(self.L.mimsem_horiz_bernoulli(self.ctx, nk, velx1.data_ptr(), velx2.data_ptr(), velx1.stride(0), velz1.data_ptr(), velz2.data_ptr(),
-                                            velz1.stride(0) if nk > 2 else 0, scale, out.data_ptr(), out.stride(0)), "horiz_bernoulli")
+        x1 = self._rows(velx1, self.sizes[1], "velx1", min_rows=2, strided="r")          # (at least one interface: nk >= 2)
+        nk = x1.shape[0]
+        x2 = self._rows(velx2, self.sizes[1], "velx2", rows=nk, strided="r")
+        z1, z2 = self._like(self.sizes[2], nk - 1, strided="r", velz1=velz1, velz2=velz2)
+        _need(x1.stride(0) == x2.stride(0), "velx1, velx2: one row stride")
+        _need(z1 is not None and z2 is not None and (nk == 2 or z1.stride(0) == z2.stride(0)), "velz1, velz2: [nk-1, n2] with one row stride")
+        out, o2 = self._out(out, nk, self.sizes[2], exact=True, strided="w")
+        check(self.L.mimsem_horiz_bernoulli(self.ctx, nk, _ps(x1)[0], *_ps(x2), _ps(z1)[0], _ps(z2)[0], z1.stride(0) if nk > 2 else 0, scale, *_ps(o2)),
+              "horiz_bernoulli")
         return out
+
+    def _sw_rows(self, x, out):
+        """packed rows [u | h] of the sw_operator family (contiguous rows, any row stride): the view of x, the result and its view"""
+        x2 = self._rows(x, self.sizes[1] + self.sizes[2], "x", strided="r")
+        return (x2,) + self._out(out, x2.shape[0], x2.shape[1], strided="w")
+
+    def _sw_f0(self, f0, nlev):
+        """(address, stride) of the Coriolis rows f0 [n0] or [1, n0] (one row for all: stride 0) or [nlev, n0]"""
+        f2 = self._rows(f0, self.sizes[0], "f0", strided="r")
+        _need(f2.shape[0] in (1, nlev), "f0: one row, or one per row of x")
+        return _ps(f2)[0], 0 if f2.shape[0] == 1 else f2.stride(0)
 
     def sw_operator(self, a, grav, H, f0, x, out=None):
         """SWEqn::assemble_operator + MatMult (src/SWEqn_Picard.cpp:622-725) in one element pass: x, y packed rows [u | h]"""
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        assert x2.shape[1] == self.sizes[1] + self.sizes[2] and x2.stride(1) == 1, x2.shape
-        f2 = f0 if f0.dim() == 2 else f0.unsqueeze(0)
-        assert f2.shape[1] == self.sizes[0] and f2.shape[0] in (1, x2.shape[0])
-        y = out if out is not None else torch.empty(x2.shape[0], x2.shape[1], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        check(self.L.mimsem_sw_operator_apply(self.ctx, x2.shape[0], a, grav, H, f2.data_ptr(), 0 if f2.shape[0] == 1 else f2.stride(0),
-                                              x2.data_ptr(), x2.stride(0), y2.data_ptr(), y2.stride(0)), "sw_operator")
+        x2, y, y2 = self._sw_rows(x, out)
+        check(self.L.mimsem_sw_operator_apply(self.ctx, x2.shape[0], a, grav, H, *self._sw_f0(f0, x2.shape[0]), *_ps(x2), *_ps(y2)), "sw_operator")
         return y if (x.dim() == 2 or out is not None) else y[0]
 
     def sw_operator_precond(self, a, grav, H, f0, blocks, x, out=None):
         """z = P (A x) in three launches (mimsem_sw_operator_precond_apply): the Krylov body of the shallow-water solve"""
-        nd = 2 * self.n1e + self.n2e
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        assert x2.shape[1] == self.sizes[1] + self.sizes[2] and x2.stride(1) == 1 and blocks.shape == (self.nEl, nd, nd)
-        f2 = f0 if f0.dim() == 2 else f0.unsqueeze(0)
-        assert f2.shape[1] == self.sizes[0] and f2.shape[0] in (1, x2.shape[0])
-        z = out if out is not None else torch.empty(x2.shape[0], x2.shape[1], dtype=torch.float64, device=self.device)
-        z2 = z if z.dim() == 2 else z.unsqueeze(0)
-        check(self.L.mimsem_sw_operator_precond_apply(self.ctx, x2.shape[0], a, grav, H, f2.data_ptr(), 0 if f2.shape[0] == 1 else f2.stride(0),
-                                                      _ptr(blocks), x2.data_ptr(), x2.stride(0), z2.data_ptr(), z2.stride(0)), "sw_operator_precond")
+        x2, z, z2 = self._sw_rows(x, out)
+        check(self.L.mimsem_sw_operator_precond_apply(self.ctx, x2.shape[0], a, grav, H, *self._sw_f0(f0, x2.shape[0]),
+                                                      self._blocks(blocks, 2 * self.n1e + self.n2e, "blocks")[0], *_ps(x2), *_ps(z2)), "sw_operator_precond")
         return z if (x.dim() == 2 or out is not None) else z[0]
 
     def sw_operator_precond_chebyshev(self, a, grav, H, f0, blocks, ca, cb, x, r, d):
         """one Chebyshev step on B = P A in three launches (mimsem_sw_operator_precond_chebyshev): x += d; r -= P A d; d = ca d + cb r, in place"""
-        nd = 2 * self.n1e + self.n2e
-        assert x.dim() == 2 and x.shape == r.shape == d.shape and x.shape[1] == self.sizes[1] + self.sizes[2] and blocks.shape == (self.nEl, nd, nd)
-        f2 = f0 if f0.dim() == 2 else f0.unsqueeze(0)
-        assert f2.shape[1] == self.sizes[0] and f2.shape[0] in (1, x.shape[0])
-        check(self.L.mimsem_sw_operator_precond_chebyshev(self.ctx, x.shape[0], a, grav, H, f2.data_ptr(), 0 if f2.shape[0] == 1 else f2.stride(0),
-                                                          _ptr(blocks), float(ca), float(cb), _ptr(x), x.stride(0), _ptr(r), r.stride(0),
-                                                          _ptr(d), d.stride(0)), "sw_operator_precond_chebyshev")
+        x2 = self._rows(x, self.sizes[1] + self.sizes[2], "x")
+        r2, d2 = self._like(x2.shape[1], x2.shape[0], r=r, d=d)
+        check(self.L.mimsem_sw_operator_precond_chebyshev(self.ctx, x2.shape[0], a, grav, H, *self._sw_f0(f0, x2.shape[0]),
+                                                          self._blocks(blocks, 2 * self.n1e + self.n2e, "blocks")[0], float(ca), float(cb),
+                                                          *_ps(x2), *_ps(r2), *_ps(d2)), "sw_operator_precond_chebyshev")
 
     def sw_operator_precond_orthogonalize(self, a, grav, H, f0, blocks, x, V, k, h, out, alpha=-1.0):
         """out = P (A x); h[:k] = V[:k] out; out += alpha V[:k]^T h -- the Krylov body and the first Gram-Schmidt pass of the Arnoldi step in four
         launches (mimsem_sw_operator_precond_orthogonalize; bit-identical to sw_operator_precond + orthogonalize, which take five)"""
-        nd = 2 * self.n1e + self.n2e
         n = self.sizes[1] + self.sizes[2]
-        assert x.numel() == n and out.numel() == n and x.is_contiguous() and out.is_contiguous() and blocks.shape == (self.nEl, nd, nd)
-        assert f0.numel() == self.sizes[0] and V.stride(1) == 1 and V.shape[1] == n and 0 <= k <= V.shape[0] and h.numel() >= k
-        check(self.L.mimsem_sw_operator_precond_orthogonalize(self.ctx, a, grav, H, f0.data_ptr(), _ptr(blocks), x.data_ptr(), out.data_ptr(),
-                                                              k, _ptr(V), V.stride(0), alpha, _ptr(h)), "sw_operator_precond_orthogonalize")
+        _need(k >= 0, "k >= 0")
+        check(self.L.mimsem_sw_operator_precond_orthogonalize(self.ctx, a, grav, H, self._vec(f0, self.sizes[0], "f0"),
+                                                              self._blocks(blocks, 2 * self.n1e + self.n2e, "blocks")[0], self._vec(x, n, "x"), self._vec(out, n, "out"),
+                                                              k, *_ps(self._rows(V, n, "V", min_rows=k)), alpha, self._vec(h, k, "h", atleast=True)),
+              "sw_operator_precond_orthogonalize")
         return out
 
     def sw_blocks_apply(self, blocks, x, out=None):
         """z = sum_e R_e^T B_e R_e x on packed rows [u | h]; blocks [nEl, ND, ND] stored column-major per element (mimsem_sw_blocks_apply)"""
-        nd = 2 * self.n1e + self.n2e
-        x2 = x if x.dim() == 2 else x.unsqueeze(0)
-        assert x2.shape[1] == self.sizes[1] + self.sizes[2] and x2.stride(1) == 1 and blocks.shape == (self.nEl, nd, nd)
-        y = out if out is not None else torch.empty(x2.shape[0], x2.shape[1], dtype=torch.float64, device=self.device)
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        check(self.L.mimsem_sw_blocks_apply(self.ctx, x2.shape[0], _ptr(blocks), x2.data_ptr(), x2.stride(0), y2.data_ptr(), y2.stride(0)),
-              "sw_blocks_apply")
+        x2, y, y2 = self._sw_rows(x, out)
+        check(self.L.mimsem_sw_blocks_apply(self.ctx, x2.shape[0], self._blocks(blocks, 2 * self.n1e + self.n2e, "blocks")[0], *_ps(x2), *_ps(y2)), "sw_blocks_apply")
         return y if (x.dim() == 2 or out is not None) else y[0]
 
     # ---- column operators -------------------------------------------------------------------
@@ -722,8 +699,12 @@ class Engine:
         if t is None:
             _need(optional, name + " is required")
             return
-        _need(t.dim() == 2 and t.shape[0] == self.nEl and t.shape[1] == slots * self.n2e,
-              "%s must be [nEl=%d, %d*n2e=%d], got %s" % (name, self.nEl, slots, slots * self.n2e, tuple(t.shape)))
+        if not (t.dim() == 2 and t.shape[0] == self.nEl and t.shape[1] == slots * self.n2e):
+            _need(False, "%s must be [nEl=%d, %d*n2e=%d], got %s" % (name, self.nEl, slots, slots * self.n2e, tuple(t.shape)))
+
+    def _cols(self, slots):
+        """a new vertical array [nEl, slots*n2e]"""
+        return self._new(self.nEl, slots * self.n2e)
 
     def _colop_slots(self, colop, transpose=False):
         """(input slots, output slots) of a column operator in units of n2e (eul/VertOps.cpp: rows x cols of each Assemble*)"""
@@ -758,27 +739,26 @@ class Engine:
     def l2_horiz_to_vert(self, vh):
         _need(vh.dim() == 2 and vh.shape[1] == self.sizes[2] and vh.shape[0] in (self.nk - 1, self.nk, self.nk + 1), "vh must be [nk-1|nk|nk+1, n2], got %s" % (tuple(vh.shape),))
         nkv = vh.shape[0]
-        vz = torch.empty(self.nEl, nkv * self.n2e, dtype=torch.float64, device=self.device)
+        vz = self._cols(nkv)
         check(self.L.mimsem_l2_transpose(self.ctx, 0, nkv, _ptr(vh), vh.stride(0), _ptr(vz)), "l2_transpose")
         return vz
 
     def l2_vert_to_horiz(self, vz, nkv):
         self._col(vz, nkv, "vz")
-        vh = torch.empty(nkv, self.sizes[2], dtype=torch.float64, device=self.device)
+        vh = self._new(nkv, self.sizes[2])
         check(self.L.mimsem_l2_transpose(self.ctx, 1, nkv, _ptr(vh), vh.stride(0), _ptr(vz)), "l2_transpose")
         return vh
 
     def colop_blocks(self, colop, f1=None, f2=None, flags=0):
         self._check_colop(colop, f1, f2)
-        nb = self.L.mimsem_colop_nblocks(self.ctx, COLOPS[colop])
-        out = torch.empty(self.nEl, nb, self.n2e, self.n2e, dtype=torch.float64, device=self.device)
+        out = self._new(self.nEl, self.L.mimsem_colop_nblocks(self.ctx, COLOPS[colop]), self.n2e, self.n2e)
         check(self.L.mimsem_colop_blocks(self.ctx, COLOPS[colop], flags, _ptr(f1), _ptr(f2), _ptr(out)), "colop_blocks(%s)" % colop)
         return out
 
     def colop_apply(self, colop, x, f1=None, f2=None, flags=0, transpose=False, nout_slots=None):
         """nout_slots: rows of the operator in units of n2e (required; checked against the operator's shape)"""
         self._check_colop(colop, f1, f2, x, nout_slots, transpose)
-        y = torch.empty(self.nEl, nout_slots * self.n2e, dtype=torch.float64, device=self.device)
+        y = self._cols(nout_slots)
         check(self.L.mimsem_colop_apply(self.ctx, COLOPS[colop], flags, int(transpose), _ptr(f1), _ptr(f2), _ptr(x), _ptr(y)),
               "colop_apply(%s)" % colop)
         return y
@@ -788,7 +768,7 @@ class Engine:
         self._check_colop(colop, None, None, x, nout_slots, transpose)
         _need(blocks.dim() == 4 and blocks.shape[0] == self.nEl and blocks.shape[1] == self.L.mimsem_colop_nblocks(self.ctx, COLOPS[colop])
               and blocks.shape[2:] == (self.n2e, self.n2e), "blocks of %s have shape %s" % (colop, tuple(blocks.shape)))
-        y = torch.empty(self.nEl, nout_slots * self.n2e, dtype=torch.float64, device=self.device)
+        y = self._cols(nout_slots)
         check(self.L.mimsem_colop_apply_blocks(self.ctx, COLOPS[colop], int(transpose), _ptr(blocks), _ptr(x), _ptr(y)),
               "colop_apply_blocks(%s)" % colop)
         return y
@@ -796,15 +776,14 @@ class Engine:
     def colop_blocks_ex(self, colop, param=0.0, f1=None, f2=None, uh=None, flags=0):
         """the Strang / Held-Suarez colops: param = dt_fric or dt, uh = [nk, n1] horizontal velocity (local 1-forms)"""
         self._check_colop(colop, f1, f2, uh=uh)
-        nb = self.L.mimsem_colop_nblocks(self.ctx, COLOPS[colop])
-        out = torch.empty(self.nEl, nb, self.n2e, self.n2e, dtype=torch.float64, device=self.device)
+        out = self._new(self.nEl, self.L.mimsem_colop_nblocks(self.ctx, COLOPS[colop]), self.n2e, self.n2e)
         check(self.L.mimsem_colop_blocks_ex(self.ctx, COLOPS[colop], flags, param, _ptr(f1), _ptr(f2), _ptr(uh),
                                             uh.stride(0) if uh is not None else 0, _ptr(out)), "colop_blocks_ex(%s)" % colop)
         return out
 
     def colop_apply_ex(self, colop, x, nout_slots, param=0.0, f1=None, f2=None, uh=None, flags=0, transpose=False):
         self._check_colop(colop, f1, f2, x, nout_slots, transpose, uh=uh)
-        y = torch.empty(self.nEl, nout_slots * self.n2e, dtype=torch.float64, device=self.device)
+        y = self._cols(nout_slots)
         check(self.L.mimsem_colop_apply_ex(self.ctx, COLOPS[colop], flags, int(transpose), param, _ptr(f1), _ptr(f2), _ptr(uh),
                                            uh.stride(0) if uh is not None else 0, _ptr(x), _ptr(y)), "colop_apply_ex(%s)" % colop)
         return y
@@ -813,53 +792,52 @@ class Engine:
         """'V10' | 'V01' | 'V10_full' applied to every column (VertOps::vertOps)"""
         w = dict(V10=0, V01=1, V10_full=2)[which]
         self._col(x, (self.nk - 1, self.nk, self.nk + 1)[w], "x of " + which)
-        ny = self.nk - 1 if w == 1 else self.nk
-        y = torch.empty(self.nEl, ny * self.n2e, dtype=torch.float64, device=self.device)
+        y = self._cols(self.nk - 1 if w == 1 else self.nk)
         check(self.L.mimsem_column_incidence(self.ctx, w, _ptr(x), _ptr(y)), "column_incidence")
         return y
 
     def diag_theta_up(self, dt, rho, rt, uh):
         self._col(rho, self.nk, "rho"); self._col(rt, self.nk, "rt")
         _need(uh.dim() == 2 and uh.shape == (self.nk, self.sizes[1]), "uh must be [nk, n1]")
-        th = torch.empty(self.nEl, (self.nk + 1) * self.n2e, dtype=torch.float64, device=self.device)
+        th = self._cols(self.nk + 1)
         check(self.L.mimsem_column_diag_theta_up(self.ctx, dt, _ptr(rho), _ptr(rt), _ptr(uh), uh.stride(0), _ptr(th)), "diag_theta_up")
         return th
 
     def temp_forcing_hs(self, lat, exner, theta, rho):
         _need(lat.dim() == 2 and lat.shape == (self.nEl, self.mp12), "lat must be [nEl, mp12] (latitude of the quadrature points)")
         self._col(exner, self.nk, "exner"); self._col(theta, self.nk + 1, "theta"); self._col(rho, self.nk, "rho")
-        out = torch.empty(self.nEl, self.nk * self.n2e, dtype=torch.float64, device=self.device)
+        out = self._cols(self.nk)
         check(self.L.mimsem_column_temp_forcing_hs(self.ctx, _ptr(lat), _ptr(exner), _ptr(theta), _ptr(rho), _ptr(out)), "temp_forcing_hs")
         return out
+
+    def _col_ptrs(self, *named):
+        """the addresses of vertical arrays given as (tensor, slots, name) triples, each checked by _col (and _ptr)"""
+        for t, slots, name in named:
+            self._col(t, slots, name)
+        return [_ptr(t) for t, _, _ in named]
 
     def solve_schur_3(self, dt, theta, velz, rho, rt, pi, F_u, F_rho, F_rt, F_pi, want_L=False, flags=0):
         """solve_schur_column_3 for every column; F_* updated in place; returns d_u, d_rho, d_rt, d_pi (, L [nEl,nk,5,n2e,n2e]);
         flags = 3 reproduces the box twin (box/VertSolve.cpp:879-1058)"""
         nk = self.nk
-        for a, sl, nm in ((theta, nk + 1, "theta"), (velz, nk - 1, "velz"), (rho, nk, "rho"), (rt, nk, "rt"), (pi, nk, "pi"),
-                          (F_u, nk - 1, "F_u"), (F_rho, nk, "F_rho"), (F_rt, nk, "F_rt"), (F_pi, nk, "F_pi")):
-            self._col(a, sl, nm)
-        N, Nm = self.nk * self.n2e, (self.nk - 1) * self.n2e
-        mk = lambda n: torch.empty(self.nEl, n, dtype=torch.float64, device=self.device)
-        d_u, d_rho, d_rt, d_pi = mk(Nm), mk(N), mk(N), mk(N)
-        L = torch.empty(self.nEl, self.nk, 5, self.n2e, self.n2e, dtype=torch.float64, device=self.device) if want_L else None
-        check(self.L.mimsem_column_solve_schur_3(self.ctx, dt, flags, _ptr(theta), _ptr(velz), _ptr(rho), _ptr(rt), _ptr(pi),
-                                                 _ptr(F_u), _ptr(F_rho), _ptr(F_rt), _ptr(F_pi),
-                                                 _ptr(d_u), _ptr(d_rho), _ptr(d_rt), _ptr(d_pi), _ptr(L)), "solve_schur_3")
+        ins = self._col_ptrs((theta, nk + 1, "theta"), (velz, nk - 1, "velz"), (rho, nk, "rho"), (rt, nk, "rt"), (pi, nk, "pi"),
+                             (F_u, nk - 1, "F_u"), (F_rho, nk, "F_rho"), (F_rt, nk, "F_rt"), (F_pi, nk, "F_pi"))
+        d_u, d_rho, d_rt, d_pi = self._cols(nk - 1), self._cols(nk), self._cols(nk), self._cols(nk)
+        L = self._new(self.nEl, self.nk, 5, self.n2e, self.n2e) if want_L else None
+        check(self.L.mimsem_column_solve_schur_3(self.ctx, dt, flags, *ins, _ptr(d_u), _ptr(d_rho), _ptr(d_rt), _ptr(d_pi), _ptr(L)), "solve_schur_3")
         return (d_u, d_rho, d_rt, d_pi, L) if want_L else (d_u, d_rho, d_rt, d_pi)
 
     def column_eos(self, which, a, b=None, p0=0.0, p1=0.0):
         _need(which in (0, 1, 2, 3), "column_eos which = 0..3")
         self._col(a, self.nk, "a"); self._col(b, self.nk, "b", optional=which in (1, 2))
-        out = torch.empty(self.nEl, self.nk * self.n2e, dtype=torch.float64, device=self.device)
+        out = self._cols(self.nk)
         check(self.L.mimsem_column_eos(self.ctx, which, _ptr(a), _ptr(b), p0, p1, _ptr(out)), "column_eos")
         return out
 
     def diag_theta(self, which, rho, rt):
         _need(which in (0, 1), "diag_theta which = 0 (diagTheta_L2) | 1 (diagTheta2)")
         self._col(rho, self.nk, "rho"); self._col(rt, self.nk, "rt")
-        nl = self.nk + (1 if which == 1 else 0)
-        th = torch.empty(self.nEl, nl * self.n2e, dtype=torch.float64, device=self.device)
+        th = self._cols(self.nk + (1 if which == 1 else 0))
         check(self.L.mimsem_column_diag_theta(self.ctx, which, _ptr(rho), _ptr(rt), _ptr(th)), "diag_theta")
         return th
 
@@ -868,9 +846,8 @@ class Engine:
         (mimsem_column_diag_theta_blend).  Returns (theta2 [nEl, (nk+1) n2e] | None, thetaL [nEl, nk n2e] | None)."""
         self._col(rho, self.nk, "rho"); self._col(rt, self.nk, "rt")
         self._col(blend2, self.nk + 1, "blend2", optional=True); self._col(blendL, self.nk, "blendL", optional=True)
-        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
-        th2 = mk(self.nk + 1) if want2 else None
-        thL = mk(self.nk) if wantL else None
+        th2 = self._cols(self.nk + 1) if want2 else None
+        thL = self._cols(self.nk) if wantL else None
         check(self.L.mimsem_column_diag_theta_blend(self.ctx, _ptr(rho), _ptr(rt), _ptr(th2), _ptr(blend2), _ptr(thL), _ptr(blendL), wa, wb),
               "diag_theta_blend")
         return th2, thL
@@ -879,110 +856,87 @@ class Engine:
                         add_w=None, add_rho=None, add_rt=None):
         """mimsem_column_newton_residual: (F_w, F_rho, F_eta, F_exner, th_w3, eta, k2i) for every column (VertSolve.cpp:1806-1851)"""
         nk = self.nk
-        for a, sl, nm in ((theta, nk, "theta"), (Pi, nk, "Pi"), (velz_i, nk - 1, "velz_i"), (velz_j, nk - 1, "velz_j"), (rho_i, nk, "rho_i"),
-                          (rho_j, nk, "rho_j"), (zv, nk, "zv"), (rt_i, nk, "rt_i"), (rt_j, nk, "rt_j"), (rho_h, nk, "rho_h"), (rt_h, nk, "rt_h"),
-                          (exner_j, nk, "exner_j")):
-            self._col(a, sl, nm)
+        ins = self._col_ptrs((theta, nk, "theta"), (Pi, nk, "Pi"), (velz_i, nk - 1, "velz_i"), (velz_j, nk - 1, "velz_j"), (rho_i, nk, "rho_i"),
+                             (rho_j, nk, "rho_j"), (zv, nk, "zv"), (rt_i, nk, "rt_i"), (rt_j, nk, "rt_j"), (rho_h, nk, "rho_h"), (rt_h, nk, "rt_h"),
+                             (exner_j, nk, "exner_j"))
         self._col(add_w, nk - 1, "add_w", optional=True); self._col(add_rho, nk, "add_rho", optional=True); self._col(add_rt, nk, "add_rt", optional=True)
-        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
-        F_w, F_rho, F_eta, F_ex, th_w3, eta, k2i = mk(nk - 1), mk(nk), mk(nk), mk(nk), mk(nk), mk(nk), mk(nk - 1)
-        check(self.L.mimsem_column_newton_residual(self.ctx, dt, rayleigh, _ptr(theta), _ptr(Pi), _ptr(velz_i), _ptr(velz_j), _ptr(rho_i), _ptr(rho_j),
-                                                   _ptr(zv), _ptr(rt_i), _ptr(rt_j), _ptr(rho_h), _ptr(rt_h), _ptr(exner_j),
-                                                   _ptr(add_w), _ptr(add_rho), _ptr(add_rt),
-                                                   _ptr(F_w), _ptr(F_rho), _ptr(F_eta), _ptr(F_ex), _ptr(th_w3), _ptr(eta), _ptr(k2i)), "newton_residual")
-        return F_w, F_rho, F_eta, F_ex, th_w3, eta, k2i
+        outs = [self._cols(s) for s in (nk - 1, nk, nk, nk, nk, nk, nk - 1)]          # F_w, F_rho, F_eta, F_exner, th_w3, eta, k2i
+        check(self.L.mimsem_column_newton_residual(self.ctx, dt, rayleigh, *ins, _ptr(add_w), _ptr(add_rho), _ptr(add_rt), *[_ptr(t) for t in outs]),
+              "newton_residual")
+        return tuple(outs)
+
+    def _newton_update(self, fn, what, d3, d_w, d_rho, d_3, d_exner, velz_i, rho_i, rt_i, exner_i, velz_j, rho_j, rt_j, exner_j):
+        """the one body of newton_update and newton2_update (d3: the name of the third correction, d_eta or d_rt)"""
+        nk = self.nk
+        ins = self._col_ptrs((d_w, nk - 1, "d_w"), (d_rho, nk, "d_rho"), (d_3, nk, d3), (d_exner, nk, "d_exner"), (velz_i, nk - 1, "velz_i"),
+                             (rho_i, nk, "rho_i"), (rt_i, nk, "rt_i"), (exner_i, nk, "exner_i"), (velz_j, nk - 1, "velz_j"), (rho_j, nk, "rho_j"),
+                             (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j"))
+        velz_h, rho_h, rt_h, exner_h = self._cols(nk - 1), self._cols(nk), self._cols(nk), self._cols(nk)
+        nrm = self._new(8, self.nEl, nk * self.n2e)
+        check(fn(self.ctx, *ins, _ptr(velz_h), _ptr(rho_h), _ptr(rt_h), _ptr(exner_h), _ptr(nrm)), what)
+        return velz_h, rho_h, rt_h, exner_h, nrm
 
     def newton_update(self, d_w, d_rho, d_eta, d_exner, velz_i, rho_i, rt_i, exner_i, velz_j, rho_j, rt_j, exner_j):
         """mimsem_column_newton_update: velz_j / rho_j / rt_j / exner_j are updated IN PLACE; returns (velz_h, rho_h, rt_h, exner_h, norm_squares
         [8, nEl, nk n2e]) (VertSolve.cpp:1858-1912)"""
-        nk = self.nk
-        for a, sl, nm in ((d_w, nk - 1, "d_w"), (d_rho, nk, "d_rho"), (d_eta, nk, "d_eta"), (d_exner, nk, "d_exner"), (velz_i, nk - 1, "velz_i"),
-                          (rho_i, nk, "rho_i"), (rt_i, nk, "rt_i"), (exner_i, nk, "exner_i"), (velz_j, nk - 1, "velz_j"), (rho_j, nk, "rho_j"),
-                          (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j")):
-            self._col(a, sl, nm)
-        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
-        velz_h, rho_h, rt_h, exner_h = mk(nk - 1), mk(nk), mk(nk), mk(nk)
-        nrm = torch.empty(8, self.nEl, nk * self.n2e, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_column_newton_update(self.ctx, _ptr(d_w), _ptr(d_rho), _ptr(d_eta), _ptr(d_exner), _ptr(velz_i), _ptr(rho_i), _ptr(rt_i),
-                                                 _ptr(exner_i), _ptr(velz_j), _ptr(rho_j), _ptr(rt_j), _ptr(exner_j),
-                                                 _ptr(velz_h), _ptr(rho_h), _ptr(rt_h), _ptr(exner_h), _ptr(nrm)), "newton_update")
-        return velz_h, rho_h, rt_h, exner_h, nrm
+        return self._newton_update(self.L.mimsem_column_newton_update, "newton_update", "d_eta", d_w, d_rho, d_eta, d_exner, velz_i, rho_i, rt_i, exner_i,
+                                   velz_j, rho_j, rt_j, exner_j)
 
     def newton2_residual(self, dt, rayleigh, theta_h, Pi, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, exner_j,
                          add_w=None, add_rho_pre=None, add_rt_pre=None, add_rt_post=None):
         """mimsem_column_newton2_residual: (F_w, F_rho, F_rt, F_exner, k2i) of VertSolve::solve_schur_2 for every column
         (VertSolve.cpp:1131-1154); theta_h on the nk+1 interfaces; the additions each enter times dt"""
         nk = self.nk
-        for a, sl, nm in ((theta_h, nk + 1, "theta_h"), (Pi, nk, "Pi"), (velz_i, nk - 1, "velz_i"), (velz_j, nk - 1, "velz_j"), (rho_i, nk, "rho_i"),
-                          (rho_j, nk, "rho_j"), (zv, nk, "zv"), (rt_i, nk, "rt_i"), (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j")):
-            self._col(a, sl, nm)
+        ins = self._col_ptrs((theta_h, nk + 1, "theta_h"), (Pi, nk, "Pi"), (velz_i, nk - 1, "velz_i"), (velz_j, nk - 1, "velz_j"), (rho_i, nk, "rho_i"),
+                             (rho_j, nk, "rho_j"), (zv, nk, "zv"), (rt_i, nk, "rt_i"), (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j"))
         self._col(add_w, nk - 1, "add_w", optional=True); self._col(add_rho_pre, nk, "add_rho_pre", optional=True)
         self._col(add_rt_pre, nk, "add_rt_pre", optional=True); self._col(add_rt_post, nk, "add_rt_post", optional=True)
-        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
-        F_w, F_rho, F_rt, F_ex, k2i = mk(nk - 1), mk(nk), mk(nk), mk(nk), mk(nk - 1)
-        check(self.L.mimsem_column_newton2_residual(self.ctx, dt, rayleigh, _ptr(theta_h), _ptr(Pi), _ptr(velz_i), _ptr(velz_j), _ptr(rho_i), _ptr(rho_j),
-                                                    _ptr(zv), _ptr(rt_i), _ptr(rt_j), _ptr(exner_j),
-                                                    _ptr(add_w), _ptr(add_rho_pre), _ptr(add_rt_pre), _ptr(add_rt_post),
-                                                    _ptr(F_w), _ptr(F_rho), _ptr(F_rt), _ptr(F_ex), _ptr(k2i)), "newton2_residual")
-        return F_w, F_rho, F_rt, F_ex, k2i
+        outs = [self._cols(s) for s in (nk - 1, nk, nk, nk, nk - 1)]                  # F_w, F_rho, F_rt, F_exner, k2i
+        check(self.L.mimsem_column_newton2_residual(self.ctx, dt, rayleigh, *ins, _ptr(add_w), _ptr(add_rho_pre), _ptr(add_rt_pre), _ptr(add_rt_post),
+                                                    *[_ptr(t) for t in outs]), "newton2_residual")
+        return tuple(outs)
 
     def newton2_update(self, d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i, velz_j, rho_j, rt_j, exner_j):
         """mimsem_column_newton2_update: velz_j / rho_j / rt_j / exner_j are updated IN PLACE; returns (velz_h, rho_h, rt_h, exner_h, norm_squares
         [8, nEl, nk n2e]) (VertSolve.cpp:1159-1183)"""
-        nk = self.nk
-        for a, sl, nm in ((d_w, nk - 1, "d_w"), (d_rho, nk, "d_rho"), (d_rt, nk, "d_rt"), (d_exner, nk, "d_exner"), (velz_i, nk - 1, "velz_i"),
-                          (rho_i, nk, "rho_i"), (rt_i, nk, "rt_i"), (exner_i, nk, "exner_i"), (velz_j, nk - 1, "velz_j"), (rho_j, nk, "rho_j"),
-                          (rt_j, nk, "rt_j"), (exner_j, nk, "exner_j")):
-            self._col(a, sl, nm)
-        mk = lambda n: torch.empty(self.nEl, n * self.n2e, dtype=torch.float64, device=self.device)
-        velz_h, rho_h, rt_h, exner_h = mk(nk - 1), mk(nk), mk(nk), mk(nk)
-        nrm = torch.empty(8, self.nEl, nk * self.n2e, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_column_newton2_update(self.ctx, _ptr(d_w), _ptr(d_rho), _ptr(d_rt), _ptr(d_exner), _ptr(velz_i), _ptr(rho_i), _ptr(rt_i),
-                                                  _ptr(exner_i), _ptr(velz_j), _ptr(rho_j), _ptr(rt_j), _ptr(exner_j),
-                                                  _ptr(velz_h), _ptr(rho_h), _ptr(rt_h), _ptr(exner_h), _ptr(nrm)), "newton2_update")
-        return velz_h, rho_h, rt_h, exner_h, nrm
+        return self._newton_update(self.L.mimsem_column_newton2_update, "newton2_update", "d_rt", d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i,
+                                   velz_j, rho_j, rt_j, exner_j)
 
     def max_norms(self, nrm):
         """mimsem_column_max_norms: VertSolve::MaxNorm for the four pairs of newton_update's norm squares -> device tensor [4] (exner, w, rho, eta)"""
-        assert nrm.shape == (8, self.nEl, self.nk * self.n2e) and nrm.is_contiguous()
-        ws = torch.empty(4, self.nEl, dtype=torch.float64, device=self.device)
-        out = torch.empty(4, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_column_max_norms(self.ctx, _ptr(nrm), _ptr(ws), _ptr(out)), "column_max_norms")
+        ws, out = self._new(4, self.nEl), self._new(4)
+        check(self.L.mimsem_column_max_norms(self.ctx, self._vec(nrm, 8 * self.nEl * self.nk * self.n2e, "nrm"), _ptr(ws), _ptr(out)), "column_max_norms")
         return out
 
     def helmholtz_blocks(self, dt, theta, rho, eta, pi):
-        for a, nm in ((theta, "theta"), (rho, "rho"), (eta, "eta"), (pi, "pi")):
-            self._col(a, self.nk, nm)
-        out = torch.empty(self.nEl, self.nk, 3, self.n2e, self.n2e, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_column_helmholtz_blocks(self.ctx, dt, _ptr(theta), _ptr(rho), _ptr(eta), _ptr(pi), _ptr(out)), "helmholtz_blocks")
+        nk = self.nk
+        ins = self._col_ptrs((theta, nk, "theta"), (rho, nk, "rho"), (eta, nk, "eta"), (pi, nk, "pi"))
+        out = self._new(self.nEl, self.nk, 3, self.n2e, self.n2e)
+        check(self.L.mimsem_column_helmholtz_blocks(self.ctx, dt, *ins, _ptr(out)), "helmholtz_blocks")
         return out
 
     def solve_schur_eta(self, dt, theta, rho, eta, pi, F_u, F_rho, F_eta, F_pi):
         """F_* are updated in place (as the reference does); returns d_u, d_rho, d_eta, d_pi"""
         nk = self.nk
-        for a, sl, nm in ((theta, nk, "theta"), (rho, nk, "rho"), (eta, nk, "eta"), (pi, nk, "pi"),
-                          (F_u, nk - 1, "F_u"), (F_rho, nk, "F_rho"), (F_eta, nk, "F_eta"), (F_pi, nk, "F_pi")):
-            self._col(a, sl, nm)
-        N, Nm = self.nk * self.n2e, (self.nk - 1) * self.n2e
-        mk = lambda n: torch.empty(self.nEl, n, dtype=torch.float64, device=self.device)
-        d_u, d_rho, d_eta, d_pi = mk(Nm), mk(N), mk(N), mk(N)
-        check(self.L.mimsem_column_solve_schur_eta(self.ctx, dt, _ptr(theta), _ptr(rho), _ptr(eta), _ptr(pi),
-                                                   _ptr(F_u), _ptr(F_rho), _ptr(F_eta), _ptr(F_pi),
-                                                   _ptr(d_u), _ptr(d_rho), _ptr(d_eta), _ptr(d_pi)), "solve_schur_eta")
+        ins = self._col_ptrs((theta, nk, "theta"), (rho, nk, "rho"), (eta, nk, "eta"), (pi, nk, "pi"),
+                             (F_u, nk - 1, "F_u"), (F_rho, nk, "F_rho"), (F_eta, nk, "F_eta"), (F_pi, nk, "F_pi"))
+        d_u, d_rho, d_eta, d_pi = self._cols(nk - 1), self._cols(nk), self._cols(nk), self._cols(nk)
+        check(self.L.mimsem_column_solve_schur_eta(self.ctx, dt, *ins, _ptr(d_u), _ptr(d_rho), _ptr(d_eta), _ptr(d_pi)), "solve_schur_eta")
         return d_u, d_rho, d_eta, d_pi
 
     def solve_status(self):
         """(columns whose refinement did not converge in the last solve_schur_eta, or -1 when that path keeps no status; per-column status
         array: 0 converged, 1 not converged, 2 refinement off, 3 re-solved by the pivoted fallback, 4 flagged for its conditioning only and accepted on its backward error (set_pivot_fallback); per-column |last correction| / |solution|) -- mimsem_column_solve_status"""
         n = C.c_int(-1)
-        st = np.zeros(max(self.nEl, 1), dtype=np.int32); ratio = np.zeros(max(self.nEl, 1))
-        check(self.L.mimsem_column_solve_status(self.ctx, C.byref(n), st.ctypes.data, ratio.ctypes.data), "column_solve_status")
+        st, pst = _host(np.zeros(max(self.nEl, 1), dtype=np.int32), np.int32)
+        ratio, pratio = _host(np.zeros(max(self.nEl, 1)), np.float64)
+        check(self.L.mimsem_column_solve_status(self.ctx, C.byref(n), pst, pratio), "column_solve_status")
         return n.value, st[:self.nEl], ratio[:self.nEl]
 
     def flag_columns_for_test(self, columns):
         """test hook: the next column solve treats these columns as flagged by its block sweep (mimsem_column_flag_for_test)"""
-        cols = np.ascontiguousarray(columns, dtype=np.int32)
-        check(self.L.mimsem_column_flag_for_test(self.ctx, cols.ctypes.data, int(cols.size)), "column_flag_for_test")
+        cols, p = _host(columns, np.int32)
+        check(self.L.mimsem_column_flag_for_test(self.ctx, p, int(cols.size)), "column_flag_for_test")
 
     def set_pivot_fallback(self, on=True):
         """(on by default) solve_schur_eta / solve_schur_3 re-solve the columns their unpivoted sweep flags by an LU with partial pivoting over
@@ -991,63 +945,75 @@ class Engine:
         check(self.L.mimsem_column_set_pivot_fallback(self.ctx, int(on)), "column_set_pivot_fallback")      # (2: every column, validation mode)
 
     # ---- Krylov building blocks ----------------------------------------------------------------
+    def _basis(self, V, w, k):
+        """(k, n, address and row stride of V, address of w) as the Gram-Schmidt kernels take them: w one contiguous block of n entries, V at
+        least k rows of length n (k None: all of them)"""
+        k = V.shape[0] if k is None else k
+        _need(k >= 0, "k >= 0")
+        return (k, w.numel()) + _ps(self._rows(V, w.numel(), "V", min_rows=k)) + (self._vec(w, w.numel(), "w"),)
+
     def mdot(self, V, w, k=None, out=None):
         """h[i] = <V[i], w> for i < k; V: [m, n] contiguous rows"""
-        k = V.shape[0] if k is None else k
-        h = out if out is not None else torch.empty(k, dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_krylov_mdot(self.ctx, k, w.numel(), _ptr(V), V.stride(0), _ptr(w), _ptr(h)), "krylov_mdot")
+        k, n, pV, ldv, pw = self._basis(V, w, k)
+        h = out if out is not None else self._new(k)
+        check(self.L.mimsem_krylov_mdot(self.ctx, k, n, pV, ldv, pw, self._vec(h, k, "out", atleast=True)), "krylov_mdot")
         return h
 
     def maxpy(self, V, h, w, alpha=1.0, k=None):
         """w += alpha * sum_{i<k} h[i] V[i]  (in place)"""
-        k = V.shape[0] if k is None else k
-        check(self.L.mimsem_krylov_maxpy(self.ctx, k, w.numel(), _ptr(V), V.stride(0), _ptr(h), alpha, _ptr(w)), "krylov_maxpy")
+        k, n, pV, ldv, pw = self._basis(V, w, k)
+        check(self.L.mimsem_krylov_maxpy(self.ctx, k, n, pV, ldv, self._vec(h, k, "h", atleast=True), alpha, pw), "krylov_maxpy")
         return w
 
     def orthogonalize(self, V, w, h, k=None, alpha=-1.0):
         """one classical Gram-Schmidt pass in two launches: h[:k] = V[:k] w, then w += alpha V[:k]^T h (in place)"""
-        k = V.shape[0] if k is None else k
-        check(self.L.mimsem_krylov_orthogonalize(self.ctx, k, w.numel(), _ptr(V), V.stride(0), alpha, _ptr(w), _ptr(h)), "krylov_orthogonalize")
+        k, n, pV, ldv, pw = self._basis(V, w, k)
+        check(self.L.mimsem_krylov_orthogonalize(self.ctx, k, n, pV, ldv, alpha, pw, self._vec(h, k, "h", atleast=True)), "krylov_orthogonalize")
         return w
+
+    def _gs_args(self, V, w, v, k, h1, h2, col, norm_slot):
+        """the arguments cgs2 and reorthonormalize share: V, w as in _basis, v like w, h1 / h2 at least k entries, col (a _word) long enough
+        for its k entries and for norm_slot"""
+        _need(norm_slot >= 0, "norm_slot >= 0")
+        return self._basis(V, w, k) + (self._vec(v, w.numel(), "v"), self._vec(h1, k, "h1", atleast=True), self._vec(h2, k, "h2", atleast=True),
+                                       self._word(col, max(k, norm_slot + 1), "col"), norm_slot)
 
     def cgs2(self, V, w, v, k, h1, h2, col, norm_slot, flag=None):
         """both Gram-Schmidt passes of an Arnoldi step + normalisation + Hessenberg column in three launches (mimsem_krylov_cgs2)"""
-        assert w.numel() == v.numel() and v.is_contiguous() and w.is_contiguous() and col.dtype == torch.float64 and col.is_contiguous()
-        assert col.is_cuda or col.is_pinned(), "col must be device or pinned host memory"
-        assert col.numel() > max(k - 1, norm_slot) and h1.numel() >= k and h2.numel() >= k
-        check(self.L.mimsem_krylov_cgs2(self.ctx, k, w.numel(), _ptr(V), V.stride(0), _ptr(w), _ptr(v), _ptr(h1), _ptr(h2),
-                                        col.data_ptr(), norm_slot, flag.data_ptr() if flag is not None else None), "krylov_cgs2")
+        check(self.L.mimsem_krylov_cgs2(self.ctx, *self._gs_args(V, w, v, k, h1, h2, col, norm_slot), self._word(flag, 1, "flag", _I32)), "krylov_cgs2")
 
     def reorthonormalize(self, V, w, v, k, h1, h2, col, norm_slot, fused=None, flag=None):
         """second Gram-Schmidt pass + normalisation in two launches: h2[:k] = V[:k] w; w -= V[:k]^T h2; v = w/|w|;
         col[:k] = h1 + h2; col[norm_slot] = |w| (col: device or pinned host tensor).  fused / flag given: the explicit form
         (mimsem_krylov_reorthonormalize_ex: the caller's own flag word, nothing shared through the context)"""
-        assert w.numel() == v.numel() and v.is_contiguous() and col.dtype == torch.float64 and col.is_contiguous()
-        assert col.is_cuda or col.is_pinned(), "col must be device or pinned host memory"
-        assert col.numel() > max(k - 1, norm_slot)
+        args = self._gs_args(V, w, v, k, h1, h2, col, norm_slot)
         if fused is not None:
-            assert flag is None or (flag.dtype == torch.int32 and (flag.is_cuda or flag.is_pinned()))
-            check(self.L.mimsem_krylov_reorthonormalize_ex(self.ctx, k, w.numel(), _ptr(V), V.stride(0), _ptr(w), _ptr(v), _ptr(h1), _ptr(h2),
-                                                           col.data_ptr(), norm_slot, 1 if fused else 0,
-                                                           flag.data_ptr() if flag is not None else None), "krylov_reorthonormalize_ex")
+            check(self.L.mimsem_krylov_reorthonormalize_ex(self.ctx, *args, 1 if fused else 0, self._word(flag, 1, "flag", _I32)), "krylov_reorthonormalize_ex")
             return
-        check(self.L.mimsem_krylov_reorthonormalize(self.ctx, k, w.numel(), _ptr(V), V.stride(0), _ptr(w), _ptr(v), _ptr(h1), _ptr(h2),
-                                                    col.data_ptr(), norm_slot), "krylov_reorthonormalize")
+        check(self.L.mimsem_krylov_reorthonormalize(self.ctx, *args), "krylov_reorthonormalize")
         return v
 
     def normalize(self, w, v, k, h1, h2, col, norm_slot):
         """v = w/|w|; col[:k] = h1 + h2; col[norm_slot] = |w|.  col: device tensor or PINNED host tensor (written by the kernel)"""
-        assert w.numel() == v.numel() and v.is_contiguous() and col.dtype == torch.float64 and col.is_contiguous()
-        assert col.is_cuda or col.is_pinned(), "col must be device or pinned host memory"
-        assert col.numel() > max(k - 1, norm_slot)
-        check(self.L.mimsem_krylov_normalize(self.ctx, w.numel(), _ptr(w), _ptr(v), k, _ptr(h1), _ptr(h2) if h2 is not None else None,
-                                             col.data_ptr(), norm_slot), "krylov_normalize")
+        n = w.numel()
+        _need(norm_slot >= 0, "norm_slot >= 0")
+        check(self.L.mimsem_krylov_normalize(self.ctx, n, self._vec(w, n, "w"), self._vec(v, n, "v"), k, self._vec(h1, k, "h1", atleast=True, optional=True),
+                                             self._vec(h2, k, "h2", atleast=True, optional=True), self._word(col, max(k, norm_slot + 1), "col"), norm_slot),
+              "krylov_normalize")
         return v
+
+    def _rowwise(self, **named):
+        """operands of a row-wise update: [nrows, n] tensors of one shape -- that of the first --, each one contiguous block (None: an absent
+        optional one); (nrows, n, their (address, stride) pairs in the order given)"""
+        name, t = next(iter(named.items()))
+        nrows, n = self._rows(t, None, name).shape
+        return (nrows, n) + tuple(_ps(t2) for t2 in self._like(n, nrows, **named))
 
     def rowdot(self, A, B, out=None):
         """out[i] = <A[i], B[i]> for [nrows, n] tensors (rows contiguous)"""
-        out = out if out is not None else torch.empty(A.shape[0], dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_krylov_rowdot(self.ctx, A.shape[0], A.shape[1], _ptr(A), A.stride(0), _ptr(B), B.stride(0), _ptr(out)), "rowdot")
+        nrows, n, pA, pB = self._rowwise(A=A, B=B)
+        out = out if out is not None else self._new(nrows)
+        check(self.L.mimsem_krylov_rowdot(self.ctx, nrows, n, *pA, *pB, self._vec(out, nrows, "out", atleast=True)), "rowdot")
         return out
 
     def rowdot_local(self, A, B, out=None, space=None):
@@ -1056,81 +1022,77 @@ class Engine:
 
     def cg_update(self, num, den, p, Ap, x, r):
         """x += (num/den) p ; r -= (num/den) Ap  row-wise, in place"""
-        check(self.L.mimsem_krylov_cg_update(self.ctx, p.shape[0], p.shape[1], _ptr(num), _ptr(den), _ptr(p), p.stride(0),
-                                             _ptr(Ap), Ap.stride(0), _ptr(x), x.stride(0), _ptr(r), r.stride(0)), "cg_update")
+        nrows, n, pp, pAp, px, pr = self._rowwise(p=p, Ap=Ap, x=x, r=r)
+        check(self.L.mimsem_krylov_cg_update(self.ctx, nrows, n, self._vec(num, nrows, "num", atleast=True), self._vec(den, nrows, "den", atleast=True),
+                                             *pp, *pAp, *px, *pr), "cg_update")
 
     def chebyshev_start(self, c, s, theta, r, d, x):
         """r = s c ; d = r / theta ; x = 0 row-wise (one launch: mimsem_krylov_chebyshev_start); r may be c"""
-        check(self.L.mimsem_krylov_chebyshev_start(self.ctx, x.shape[0], x.shape[1], float(s), float(theta), _ptr(c), c.stride(0), _ptr(r), r.stride(0),
-                                                   _ptr(d), d.stride(0), _ptr(x), x.stride(0)), "chebyshev_start")
+        nrows, n, px, pc, pr, pd = self._rowwise(x=x, c=c, r=r, d=d)
+        check(self.L.mimsem_krylov_chebyshev_start(self.ctx, nrows, n, float(s), float(theta), *pc, *pr, *pd, *px), "chebyshev_start")
 
     def chebyshev_px(self, alpha, beta, y, p, x, b=None, dinv=None, upd=None):
         """z = dinv (b - y) (or y when dinv is None); p = z + beta p; x += alpha p; upd = z -- row-wise, one launch (mimsem_krylov_chebyshev_px: the
         vector algebra of a Chebyshev step on a sharded mesh, where the operator result is completed over the halo between the passes)"""
-        st = lambda t: t.stride(0) if t is not None else 0
-        check(self.L.mimsem_krylov_chebyshev_px(self.ctx, x.shape[0], x.shape[1], float(alpha), float(beta), _ptr(y), y.stride(0), _ptr(b), st(b), _ptr(dinv), st(dinv),
-                                                _ptr(p), p.stride(0), _ptr(x), x.stride(0), _ptr(upd), st(upd)), "chebyshev_px")
+        nrows, n, px, py, pb, pdinv, pp, pupd = self._rowwise(x=x, y=y, b=b, dinv=dinv, p=p, upd=upd)
+        check(self.L.mimsem_krylov_chebyshev_px(self.ctx, nrows, n, float(alpha), float(beta), *py, *pb, *pdinv, *pp, *px, *pupd), "chebyshev_px")
 
     def axpy_dots(self, dx, x, out):
         """x += dx ; out[0] = dx . dx ; out[1] = x . x over ALL entries of the (contiguous) tensors (one launch: mimsem_krylov_axpy_dots)"""
-        assert dx.is_contiguous() and x.is_contiguous() and dx.numel() == x.numel() and out.numel() == 2 and out.is_contiguous()
-        check(self.L.mimsem_krylov_axpy_dots(self.ctx, x.numel(), _ptr(dx), _ptr(x), _ptr(out)), "axpy_dots")
+        check(self.L.mimsem_krylov_axpy_dots(self.ctx, x.numel(), self._vec(dx, x.numel(), "dx"), self._vec(x, x.numel(), "x"), self._vec(out, 2, "out")),
+              "axpy_dots")
 
     def chebyshev_update(self, a, b, Bd, x, r, d):
         """x += d ; r -= Bd ; d = a d + b r  row-wise, in place (one launch: mimsem_krylov_chebyshev_update)"""
-        check(self.L.mimsem_krylov_chebyshev_update(self.ctx, x.shape[0], x.shape[1], float(a), float(b), _ptr(Bd), Bd.stride(0),
-                                                    _ptr(x), x.stride(0), _ptr(r), r.stride(0), _ptr(d), d.stride(0)), "chebyshev_update")
+        nrows, n, px, pBd, pr, pd = self._rowwise(x=x, Bd=Bd, r=r, d=d)
+        check(self.L.mimsem_krylov_chebyshev_update(self.ctx, nrows, n, float(a), float(b), *pBd, *px, *pr, *pd), "chebyshev_update")
 
     def cg_direction(self, num, den, z, p):
         """p = z + (num/den) p  row-wise, in place"""
-        check(self.L.mimsem_krylov_cg_direction(self.ctx, p.shape[0], p.shape[1], _ptr(num), _ptr(den), _ptr(z), z.stride(0),
-                                                _ptr(p), p.stride(0)), "cg_direction")
+        nrows, n, pp, pz = self._rowwise(p=p, z=z)
+        check(self.L.mimsem_krylov_cg_direction(self.ctx, nrows, n, self._vec(num, nrows, "num", atleast=True), self._vec(den, nrows, "den", atleast=True),
+                                                *pz, *pp), "cg_direction")
 
     def combine(self, a, alpha=1.0, op=None, b=None, beta=0.0, c=None, out=None):
         """out = alpha * (a, a*b or a/b) + beta * c, row by row ([nrows, n] tensors whose rows are contiguous; slices along the first
         dimension are fine); out may be a or c (mimsem_vec_combine)"""
-        a2 = a if a.dim() == 2 else a.unsqueeze(0)
+        a2 = self._rows(a, None, "a", strided="r")
+        nrows, n = a2.shape
         out = torch.empty_like(a2) if out is None else out
-        o2 = out if out.dim() == 2 else out.unsqueeze(0)
         opc = {None: 0, "mul": 1, "div": 2}[op]
-        ts = [a2, o2] + ([b] if b is not None else []) + ([c] if c is not None else [])
-        for t in ts:
-            t2 = t if t.dim() == 2 else t.unsqueeze(0)
-            if t2.shape != a2.shape or t2.stride(1) != 1 or t2.dtype != torch.float64 or t2.device != a2.device:
-                raise _lib.MimsemError("combine: operands must be float64 [nrows, n] with contiguous rows on one device, got %s vs %s" % (tuple(t2.shape), tuple(a2.shape)))
-        b2 = None if b is None else (b if b.dim() == 2 else b.unsqueeze(0))
-        c2 = None if c is None else (c if c.dim() == 2 else c.unsqueeze(0))
-        if opc and b2 is None:
-            raise _lib.MimsemError("combine: op needs b")
-        check(self.L.mimsem_vec_combine(self.ctx, a2.shape[0], a2.shape[1], float(alpha), a2.data_ptr(), a2.stride(0), opc,
-                                        None if b2 is None else b2.data_ptr(), 0 if b2 is None else b2.stride(0), float(beta),
-                                        None if c2 is None else c2.data_ptr(), 0 if c2 is None else c2.stride(0), o2.data_ptr(), o2.stride(0)), "vec_combine")
+        _need(not opc or b is not None, "combine: op needs b")
+        b2, c2 = self._like(n, nrows, strided="r", b=b, c=c)
+        check(self.L.mimsem_vec_combine(self.ctx, nrows, n, float(alpha), *_ps(a2), opc, *_ps(b2), float(beta), *_ps(c2),
+                                        *_ps(self._rows(out, n, "out", rows=nrows, strided="w"))), "vec_combine")
         return out
 
     def interface_average(self, a, nk):
         """[nk-1, n] interface field -> [nk, n] level field, 0.5*(k-1) + 0.5*(k) with the missing boundary interfaces left out"""
-        out = torch.empty(nk, a.shape[1], dtype=torch.float64, device=a.device)
-        check(self.L.mimsem_interface_average(self.ctx, nk, a.shape[1], a.data_ptr(), a.stride(0), out.data_ptr(), out.stride(0)), "interface_average")
+        a2 = self._rows(a, None, "a", min_rows=nk - 1, strided="r")
+        out = self._new(nk, a2.shape[1])
+        check(self.L.mimsem_interface_average(self.ctx, nk, a2.shape[1], *_ps(a2), *_ps(out)), "interface_average")
         return out
+
+    def _block_inverse(self, blocks, status):
+        """the one body of block_inverse and block_inverse_status: (the inverses as a new tensor, the library's count of bad pivots)"""
+        _need(blocks.dim() == 3 and blocks.shape[1] == blocks.shape[2] and blocks.dtype == _F64, "block_inverse: [nblocks, n, n] float64 tensor required")
+        out = blocks.contiguous().clone()
+        ns = C.c_int(0)
+        if status:
+            check(self.L.mimsem_block_inverse_status(self.ctx, out.shape[0], out.shape[1], _ptr(out), C.byref(ns)), "block_inverse_status")
+        else:
+            check(self.L.mimsem_block_inverse(self.ctx, out.shape[0], out.shape[1], _ptr(out)), "block_inverse")
+        return out, ns.value
 
     def block_inverse(self, blocks):
         """inverse of every [n, n] block of a [nblocks, n, n] tensor by the library's batched Gauss-Jordan (mimsem_block_inverse);
         returns a new tensor"""
-        if blocks.dim() != 3 or blocks.shape[1] != blocks.shape[2] or blocks.dtype != torch.float64:
-            raise _lib.MimsemError("block_inverse: [nblocks, n, n] float64 tensor required")
-        out = blocks.contiguous().clone()
-        check(self.L.mimsem_block_inverse(self.ctx, out.shape[0], out.shape[1], out.data_ptr()), "block_inverse")
-        return out
+        return self._block_inverse(blocks, False)[0]
 
     def block_inverse_status(self, blocks):
         """block_inverse plus the number of blocks for which the reference's LinAlg::Inv reports a (near-)singular pivot
         (mimsem_block_inverse_status; eul/LinAlg.cpp:243-246)"""
-        if blocks.dim() != 3 or blocks.shape[1] != blocks.shape[2] or blocks.dtype != torch.float64:
-            raise _lib.MimsemError("block_inverse: [nblocks, n, n] float64 tensor required")
-        out = blocks.contiguous().clone()
-        ns = C.c_int(0)
-        check(self.L.mimsem_block_inverse_status(self.ctx, out.shape[0], out.shape[1], out.data_ptr(), C.byref(ns)), "block_inverse_status")
-        return out, ns.value
+        return self._block_inverse(blocks, True)
 
     def norm(self, x):
         """2-norm of a whole (single-rank) vector by the library's two-stage row-dot; DistEngine overrides with the ownership-weighted,
@@ -1155,22 +1117,25 @@ class Engine:
     def space(self, key):
         """context manager naming the vector space of the inner products inside (0, 1, 2 or "uh" = packed [1-form, 2-form]);
         a no-op on one rank, the ownership weights on a DistEngine"""
-        import contextlib
         return contextlib.nullcontext()
 
     # ---- halo pack / unpack ---------------------------------------------------------------------
     def halo_segments(self, idx, seg_off, s_begin, s_end, mode, buf, v):
         """all neighbours in one launch (mimsem_halo_segments): mode 0 pack, 1 insert, 2 add; seg_off: host int32 array"""
-        v2 = v if v.dim() == 2 else v.unsqueeze(0)
-        check(self.L.mimsem_halo_segments(self.ctx, _ptr(idx), len(seg_off) - 1, seg_off.ctypes.data, s_begin, s_end,
-                                          v2.shape[0], mode, _ptr(buf), _ptr(v2), v2.stride(0)), "halo_segments")
+        _need(isinstance(seg_off, np.ndarray) and seg_off.dtype == np.int32 and seg_off.ndim == 1 and seg_off.size >= 1, "seg_off: a host int32 array")
+        off, poff = _host(seg_off, np.int32)
+        v2 = self._rows(v, None, "v")
+        total = int(off[-1])                                # (buf: segment-major [neighbour][level][slot], idx: the slots of all neighbours)
+        check(self.L.mimsem_halo_segments(self.ctx, self._vec(idx, total, "idx", atleast=True, dtype=_I32), off.size - 1, poff, s_begin, s_end, v2.shape[0], mode,
+                                          self._vec(buf, total * v2.shape[0], "buf", atleast=True), *_ps(v2)), "halo_segments")
 
     def halo_pack(self, idx, v):
-        v2 = v if v.dim() == 2 else v.unsqueeze(0)
-        buf = torch.empty(v2.shape[0], idx.numel(), dtype=torch.float64, device=self.device)
-        check(self.L.mimsem_halo_pack(self.ctx, _ptr(idx), idx.numel(), v2.shape[0], _ptr(v2), v2.stride(0), _ptr(buf)), "halo_pack")
+        v2 = self._rows(v, None, "v")
+        buf = self._new(v2.shape[0], idx.numel())
+        check(self.L.mimsem_halo_pack(self.ctx, self._vec(idx, None, "idx", dtype=_I32), idx.numel(), v2.shape[0], *_ps(v2), _ptr(buf)), "halo_pack")
         return buf
 
     def halo_unpack(self, idx, buf, v, add):
-        v2 = v if v.dim() == 2 else v.unsqueeze(0)
-        check(self.L.mimsem_halo_unpack(self.ctx, _ptr(idx), idx.numel(), v2.shape[0], int(add), _ptr(buf), _ptr(v2), v2.stride(0)), "halo_unpack")
+        v2 = self._rows(v, None, "v")
+        check(self.L.mimsem_halo_unpack(self.ctx, self._vec(idx, None, "idx", dtype=_I32), idx.numel(), v2.shape[0], int(add),
+                                        self._vec(buf, v2.shape[0] * idx.numel(), "buf"), *_ps(v2)), "halo_unpack")

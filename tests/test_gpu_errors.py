@@ -64,9 +64,9 @@ def test_argument_errors(small):
     assert L.mimsem_krylov_orthogonalize(ctx, 2, dm.n1, px, 5, -1.0, py, py) == ERR_ARG                              # ldv < n
     for code in (-1, -2, -3, -4, -5):
         assert len(L.mimsem_strerror(code)) > 5
-    with pytest.raises(AssertionError):                                  # vector lengths are checked by the host layer
+    with pytest.raises(MimsemError):                                     # vector lengths are checked by the host layer
         eng.incidence("E10", x)
-    with pytest.raises(AssertionError):
+    with pytest.raises(MimsemError):
         eng.apply("UHMAT", x, f=h[:, :5].contiguous())
     with pytest.raises(MimsemError):
         eng.apply("UTMAT", x, lev0=0, scale=SCALE)                        # needs thick[lev+1]: the ABI's error code surfaces as an exception
@@ -138,6 +138,106 @@ def test_column_wrappers_reject_wrong_shapes(small):
     y = eng.colop_apply("CONLIN_W", col(nk - 1), f1=col(nk - 1), nout_slots=nk)
     yt = eng.colop_apply("CONLIN_W", col(nk), f1=col(nk - 1), nout_slots=nk - 1, transpose=True)
     assert y.shape == (nEl, nk * n2) and yt.shape == (nEl, (nk - 1) * n2) and bool(torch.isfinite(y).all())
+
+
+def test_horizontal_and_krylov_wrappers_reject_wrong_shapes(small):
+    """the horizontal, solver and Krylov entry points take raw pointers just as the column ones do: one malformed call per wrapper family
+    -- short rows, swapped dimensions, too few rows, float32, int64 indices, a host tensor -- must raise MimsemError (no assert: also under
+    python -O) and never reach a launch.  Every malformed operand is a view into, or has, an allocation at least as large as the well-formed
+    one's, so a call that slipped through would stay inside memory this test owns and only fail the test."""
+    import torch
+    from mimsem_amd._lib import MimsemError
+    eng, dm, P = small
+    nk, n0, n1, n2, nEl, nd, ndsw = 4, dm.n0, dm.n1, dm.n2, dm.nEl, 2 * eng.n1e, 2 * eng.n1e + eng.n2e
+    ones = lambda *shape: eng.zeros(*shape) + 1.0
+    x0, x1, h, xp, f0 = ones(nk, n0), ones(nk, n1), ones(nk, n2), ones(1, n1 + n2), ones(1, n0)
+    B = (0.01 * torch.eye(nd, dtype=torch.float64, device=eng.device)).repeat(nEl, 1, 1)
+    coef = [(1.0, 0.0), (1.0, 0.1)]
+    V, w, hk = ones(4, n1)[:3], ones(n1), ones(3)
+    idx = torch.arange(5, dtype=torch.int32, device=eng.device)
+    xa, xb, xc, pa = x1.clone(), x1.clone(), x1.clone(), x1.clone()
+    big = ones(4 * nEl * ndsw * ndsw)                                            # larger than every operand below
+    assert big.numel() > 2 * (nk + 1) * (n0 + n1 + n2)
+    view = lambda *shape: big[:int(np.prod(shape))].view(*shape)                # a contiguous tensor of any shape inside big
+    f32 = lambda rows, n: torch.ones(2 * rows, n, dtype=torch.float32, device=eng.device)[:rows]     # the bytes of a float64 [rows, n]
+    cut = lambda t: t.clone()[:-1]                                              # a row (an entry) too few, sliced from a full array
+    bad = [lambda: eng.apply("UMAT", view(nk, n1 - 1), scale=SCALE),                                  # the operator applies: short rows
+           lambda: eng.apply("UMAT", view(n1, nk), scale=SCALE),                                      # dimensions swapped
+           lambda: eng.apply("UMAT", f32(nk, n1), scale=SCALE),
+           lambda: eng.apply("UMAT", x1.cpu(), scale=SCALE),                                          # host tensor
+           lambda: eng.apply("UHMAT", x1, f=cut(h), scale=SCALE),                                     # a field row missing
+           lambda: eng.apply("UMAT", x1, scale=SCALE, out=view(nk, n1 - 1)),
+           lambda: eng.apply_levels("WMAT", view(nk, n2 - 1), 0, scale=SCALE),
+           lambda: eng.apply_part("UMAT", "all", x1, scale=SCALE, out=cut(x1)),
+           lambda: eng.apply_up("UMAT_UP", x1, x1, view(nk, n1 - 1), scale=SCALE, tau=1.0),           # short velocity rows
+           lambda: eng.apply_ray(x1, h, view(n2 - 1), 1.0, scale=SCALE),                              # short surface exner
+           lambda: eng.apply_fric(x1, f32(nk, n2), h[0], 1.0, scale=SCALE),
+           lambda: eng.prepare_apply("UHMAT", x1, f=view(nk, n2 - 1), scale=SCALE),
+           lambda: eng.richardson_sweep("PMAT", x0.clone(), x0, view(nk, n0 - 1), scale=SCALE),       # the sweeps
+           lambda: eng.chebyshev_sweep("PMAT", x0.clone(), x0, x0, cut(x0), 1.0, 0.0, scale=SCALE),
+           lambda: eng.block_richardson_sweep("UMAT", view(nEl, nd, nd - 1), xa, x1, scale=SCALE),
+           lambda: eng.block_chebyshev_sweep("UMAT", B, xa, x1, pa, 1.0, 0.0, elem_scale=view(nk, nEl - 1), scale=SCALE),
+           lambda: eng.block_chebyshev_solve("UMAT", B, view(nk, n1 - 1), coef, scale=SCALE, flags=1),   # the Chebyshev solves
+           lambda: eng.block_chebyshev_solve("UMAT", B, x1, coef, scale=SCALE, flags=1, pb=f32(nk, n1)),
+           lambda: eng.block_chebyshev_solve("UMAT", torch.ones(2 * nEl, nd, nd, dtype=torch.float32, device=eng.device)[:nEl], x1, coef, scale=SCALE, flags=1),
+           lambda: eng.owned_block_chebyshev_solve(view(nEl, eng.owned_rows(1), eng.owned_rows(1) - 1), x1, coef, scale=SCALE),
+           lambda: eng.sw_operator(1.0, 9.8, 1e4, f0, view(1, n1 + n2 - 1)),                          # the sw_operator family
+           lambda: eng.sw_operator(1.0, 9.8, 1e4, f32(1, n0), xp),
+           lambda: eng.sw_operator(1.0, 9.8, 1e4, f0, xp.cpu()),
+           lambda: eng.sw_operator(1.0, 9.8, 1e4, f0, xp, out=view(1, n1 + n2 - 1)),
+           lambda: eng.sw_operator_precond(1.0, 9.8, 1e4, f0, view(nEl, ndsw, ndsw - 1), xp),
+           lambda: eng.sw_blocks_apply(view(nEl, ndsw - 1, ndsw), xp),
+           lambda: eng.blocks_apply(1, B, view(nk, n1 - 1)),                                          # blocks_apply
+           lambda: eng.blocks_apply(1, view(nEl, nd, nd - 1), x1),
+           lambda: eng.blocks_apply(1, B, x1, elem_scale=cut(ones(nk, nEl))),
+           lambda: eng.incidence("E21", view(nk, n1 - 1)),                                            # incidence, interp_quad
+           lambda: eng.incidence("E21", f32(nk, n1)),
+           lambda: eng.interp_quad(1, view(n1, nk)),
+           lambda: eng.interp_quad(2, x1),
+           lambda: eng.mdot(V, view(n1 - 1)),                                                         # Gram-Schmidt: w and V's rows differ
+           lambda: eng.mdot(V, w, k=4),                                                               # more rows than V has
+           lambda: eng.mdot(V, w, out=cut(hk)),
+           lambda: eng.maxpy(V, cut(hk), w.clone()),
+           lambda: eng.maxpy(f32(3, n1), hk, w.clone()),
+           lambda: eng.orthogonalize(V, w.clone(), cut(hk)),
+           lambda: eng.cgs2(V, w.clone(), view(n1 - 1), 3, hk, hk.clone(), ones(5), 4),
+           lambda: eng.normalize(w.clone(), w.clone(), 3, hk, None, ones(4), 4),                      # col has no slot 4
+           lambda: eng.rowdot(x1, view(nk, n1 - 1)),                                                  # the row-wise updates
+           lambda: eng.rowdot(x1, x1, out=cut(ones(nk))),
+           lambda: eng.cg_update(cut(ones(nk)), ones(nk), x1, pa, xa, xb),
+           lambda: eng.cg_update(ones(nk), ones(nk), x1, view(nk, n1 - 1), xa, xb),
+           lambda: eng.cg_direction(ones(nk), ones(nk), cut(x1), xa),
+           lambda: eng.chebyshev_start(view(n1, nk), 1.0, 0.8, xa, xb, xc),
+           lambda: eng.chebyshev_px(0.5, 0.1, view(nk, n1 - 1), pa, xa),
+           lambda: eng.chebyshev_px(0.5, 0.1, x1, pa, xa, upd=f32(nk, n1)),
+           lambda: eng.chebyshev_update(0.5, 0.1, x1, xa, cut(xb), xc),
+           lambda: eng.axpy_dots(view(x1.numel() - 1), xa, eng.zeros(2)),
+           lambda: eng.interface_average(cut(ones(nk - 1, n1)), nk),                                  # interface_average
+           lambda: eng.interface_average(f32(nk - 1, n1), nk),
+           lambda: eng.halo_pack(idx.long(), x1),                                                     # halo pack / unpack: int64 indices
+           lambda: eng.halo_unpack(idx, cut(ones(nk, 5)), xc, add=True),                              # a buffer row missing
+           lambda: eng.halo_unpack(idx, f32(nk, 5), xc, add=True),
+           lambda: eng.element_matrices("UHMAT", f=view(n2 - 1), scale=SCALE),                        # element matrices
+           lambda: eng.element_matrices_ray(h[0], view(n2 - 1), 1.0, scale=SCALE),
+           lambda: eng.element_matrices_fric(f32(1, n2)[0], h[0], 1.0, scale=SCALE)]
+    for i, fn in enumerate(bad):
+        with pytest.raises(MimsemError):
+            fn()
+    # and one well-formed call of each family still works
+    buf = eng.halo_pack(idx, x1)
+    eng.halo_unpack(idx, buf, xc, add=True)
+    eng.cg_update(ones(nk), ones(nk) + 1.0, x1, pa, xa, xb)
+    eng.chebyshev_px(0.5, 0.1, x1, pa, xa)
+    good = [eng.apply("UHMAT", x1, f=h, scale=SCALE), eng.block_richardson_sweep("UMAT", B, x1.clone(), x1, scale=SCALE),
+            eng.block_chebyshev_solve("UMAT", B, x1, coef, scale=SCALE, flags=1), eng.sw_operator(1.0, 9.8, 1e4, f0, xp), eng.blocks_apply(1, B, x1),
+            eng.incidence("E10", x0), eng.interp_quad(1, x1), eng.mdot(V, w), eng.maxpy(V, hk, w.clone()), eng.rowdot(x1, x1), xa, xb, pa,
+            eng.interface_average(ones(nk - 1, n1), nk), buf, xc, eng.element_matrices("UHMAT", f=h[0], scale=SCALE)]
+    assert good[0].shape == (nk, n1) and good[3].shape == (1, n1 + n2) and good[7].shape == (3,) and buf.shape == (nk, 5)
+    for t in good:
+        assert bool(torch.isfinite(t).all())
+    assert torch.equal(xc[:, :5], x1[:, :5] * 2.0) and torch.equal(xc[:, 5:], x1[:, 5:])       # the five packed slots came back added
+    # nothing above poisoned the context
+    assert float(eng.apply("UMAT", x1, lev0=0, scale=SCALE).abs().sum()) > 0
 
 
 def test_round2_entry_points_reject_bad_arguments(small):
