@@ -479,11 +479,17 @@ int build_wave_plan(int order, int n1, int nEl, int n1e, int n0e, int G, const i
 //              point's cross-edge DoFs in the order the neighbour's fma chain reads them, t = 3 the point's DoF on the side
 // The side's slots come out of the ghost lanes with the bits of the neighbour's own lanes; the owner's store pair adds them to its own
 // contribution (position WGR + b*4 + point of the level's strip).
+// FOUR-LEVEL pass (own4::k_apply_wave, LCT = 8): a group has at most 4 ghost sides whatever their kinds, so side b takes DPP row b and
+// the row's other direction holds the four levels m of a DOUBLE batch -- x-normal: lane point*4 + m, y-normal: lane m*4 + point, the
+// point along the side where the element keeps that point's coefficients, as above.  One pass serves two batches.
+//   gh4 [g][64] lane b*16 + (point, m): {metric record, element*16 + point, y-normal | qy0 (qx0) = 3 << 1 | no side DoF << 2 | idle
+//               lane << 3, position of the quadruple | result position b*4 + point << 8}; gx and the store entries are shared
 constexpr int WGX = MIMSEM_WGX;     // gathered DoFs of a group: 16 per ghost side
 constexpr int WGS = 4;              // ghost sides of a group: 16-position blocks of the gathered strip
 struct WaveOwn {
-    std::vector<int4> plan, gh; std::vector<int> gx;
+    std::vector<int4> plan, gh, gh4; std::vector<int> gx;
     int ndirect = 0, nsides = 0, maxsides = 0, maxgx = 0, nfull = 0;      // nfull: groups with 4 ghost sides of both kinds
+    int mix[4] = {0, 0, 0, 0};          // groups by their x-normal + y-normal ghost sides: 2 + 2, 4 + 0, 0 + 4, anything else
 };
 int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, const int* iy, const WavePlan& P, WaveOwn& W) {
     if (order != 3 || G != 4 || n1e != 12 || (n1 & 1) || P.ntiles || P.nbgroups) return MIMSEM_ERR_UNSUPPORTED;
@@ -535,6 +541,7 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
     // ---- per group: ghost rows, gathered DoFs, store entries ----
     W.plan.assign((size_t)P.ngroups*64, int4{0, 0, 0, 0});
     W.gh.assign((size_t)P.ngroups*32, int4{0, 0, 0, 0});
+    W.gh4.assign((size_t)P.ngroups*64, int4{0, 0, 0, 0});
     W.gx.assign((size_t)P.ngroups*64, 0);
     std::vector<std::vector<int>> owned(P.ngroups);
     for (int p = 0; p < n1/2; p++) owned[owner[p]].push_back(p);
@@ -545,6 +552,7 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
         const int lane0slot = P.lane[(size_t)g*64].y;
         for (int l = 0; l < 32; l++)                               // idle lanes: points of the group's first element, results into a dump
             W.gh[(size_t)g*32 + l] = int4{g*64 + l%lpe, e0*lpe + l%lpe, 0, (16 + l%lpe) << 8};
+        for (int l = 0; l < 64; l++) W.gh4[(size_t)g*64 + l] = int4{g*64 + l%lpe, e0*lpe + l%lpe, 8, 0};
         int nxs = 0, nys = 0;                                      // x-normal sides (columns of their row), y-normal ones (rows)
         for (int l = 0; l < 64; l++) W.gx[(size_t)g*64 + l] = lane0slot;     // positions nobody reads re-read a pair of the group
         for (size_t si = 0; si < sides.size(); si++) {
@@ -555,6 +563,10 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
                 const int l = yn ? 16 + nys*4 + pt : pt*4 + nxs;
                 W.gh[(size_t)g*32 + l] = int4{grp[e]*64 + kin[e]*lpe + q, e*lpe + q, (c0 == 3 ? 2 : 0) | (!yn && pt == 3 ? 4 : 0),
                                               (int)(si*16 + pt*4) | (int)(si*4 + pt) << 8};
+                for (int m = 0; m < 4; m++)                                     // the four-level pass: row si, the levels across the side
+                    W.gh4[(size_t)g*64 + si*16 + (yn ? m*4 + pt : pt*4 + m)] =
+                        int4{grp[e]*64 + kin[e]*lpe + q, e*lpe + q, (yn ? 1 : 0) | (c0 == 3 ? 2 : 0) | (!yn && pt == 3 ? 4 : 0),
+                             (int)(si*16 + pt*4) | (int)(si*4 + pt) << 8};
                 int* gxp = &W.gx[(size_t)g*64 + si*16 + pt*4];
                 for (int t = 0; t < 3; t++) {
                     // x-normal: Y(t, pt) for t = 0, 1, 2 (dpp_quad order); y-normal: X(pt, row) in dpp_rows rotation order from row c0
@@ -585,6 +597,7 @@ int build_wave_own(int order, int n1, int nEl, int n1e, int G, const int* ix, co
         for (int t = 0; t < 64; t++) W.plan[(size_t)g*64 + t] = ent[t%ent.size()];
         W.nsides += (int)sides.size(); W.maxsides = std::max(W.maxsides, (int)sides.size());
         if (sides.size() == 4 && nxs > 0 && nys > 0) W.nfull++;
+        W.mix[nxs == 2 && nys == 2 ? 0 : (nxs == 4 && nys == 0 ? 1 : (nxs == 0 && nys == 4 ? 2 : 3))]++;
         W.maxgx = std::max(W.maxgx, 16*(int)sides.size());
     }
     return MIMSEM_OK;
@@ -769,10 +782,13 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
     WaveOwn W;
     const bool want_own = !marked && es.n == 3 && !want_fin && !want_tile && !singles && mixed &&
                           !(getenv("MIMSEM_WAVE_OWN") && atoi(getenv("MIMSEM_WAVE_OWN")) == 0);
+    // ... and which ghost pass the LCT = 8 kernel runs: unset -- one pass per four levels (own4::k_apply_wave); MIMSEM_WAVE_OWN=1 -- the pass
+    // per batch of two levels for every call (the A/B partner; single-level calls always run it)
+    const bool own4 = !getenv("MIMSEM_WAVE_OWN");
     const bool own = want_own && build_wave_own(es.n, c->n1, c->nEl, es.n1e, 64/lpe, c->h_i1x.data(), c->h_i1y.data(), P, W) == MIMSEM_OK;
     void* old[] = {c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin,
-                   c->d_woplan, c->d_wgh, c->d_wgx};
-    c->d_woplan = nullptr; c->d_wgh = nullptr; c->d_wgx = nullptr; c->w_own = false;
+                   c->d_woplan, c->d_wgh, c->d_wgx, c->d_wgh4};
+    c->d_woplan = nullptr; c->d_wgh = nullptr; c->d_wgx = nullptr; c->d_wgh4 = nullptr; c->w_own = false;
     c->d_wtfin = nullptr; c->w_ntiles = 0;
     for (void* p : old) if (p) c->retired.push_back(p);
     c->d_wlane = nullptr; c->d_wplan = nullptr; c->d_wprec = nullptr; c->d_wnode = nullptr; c->d_wsing = nullptr; c->d_wG = nullptr; c->d_wR = nullptr;
@@ -790,6 +806,7 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
         if ((rc = upload(&c->d_woplan, W.plan.data(), W.plan.size(), c))) return rc;
         if ((rc = upload(&c->d_wgh, W.gh.data(), W.gh.size(), c))) return rc;
         if ((rc = upload(&c->d_wgx, W.gx.data(), W.gx.size(), c))) return rc;
+        if (own4 && (rc = upload(&c->d_wgh4, W.gh4.data(), W.gh4.size(), c))) return rc;
         c->w_own = true;
     }
     if (P.nsing && (rc = upload(&c->d_wsing, P.sing.data(), P.sing.size(), c))) return rc;
@@ -837,7 +854,9 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
                 P.npwritten, P.nsides, c->n1, c->w_fin ? "on" : "off", P.ntiles, P.ninner, P.tpmax);
     if (getenv("MIMSEM_VERBOSE") && own)
         fprintf(stderr, "[mimsem] owner-computes form: %d pairs, %d ghost sides (at most %d per group; %d groups with 4 of both kinds), "
-                        "at most %d gathered DoFs per group\n", c->n1/2, W.nsides, W.maxsides, W.nfull, W.maxgx);
+                        "at most %d gathered DoFs per group; side mixes (x-normal + y-normal): %d groups 2 + 2, %d groups 4 + 0, %d groups 0 + 4, "
+                        "%d other; ghost pass per %s\n", c->n1/2, W.nsides, W.maxsides, W.nfull, W.maxgx, W.mix[0], W.mix[1], W.mix[2], W.mix[3],
+                own4 ? "four levels" : "batch");
     return MIMSEM_OK;
 }
 
@@ -1065,7 +1084,7 @@ void mimsem_ctx_destroy(mimsem_ctx* c) {
     (void)hipSetDevice(c->device);
     orphan_graphs(c);
     void* ptrs[] = {c->d_xn, c->d_E, c->d_w, c->d_U, c->d_V, c->d_W, c->d_P, c->d_J, c->d_det, c->d_th, c->d_tI, c->d_tIp, c->d_tIn,
-                    c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_iq, c->d_fperm, c->d_flid, c->d_fslot, c->d_fcnt, c->d_pslot, c->d_ppart, c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin, c->d_woplan, c->d_wgh, c->d_wgx, c->d_wpart, c->d_wsplit, c->d_colstat, c->d_forceflag, c->d_rdcnt, c->d_cheb, c->d_colratio, c->d_g1, c->d_bplan, c->d_g0, c->d_ye, c->d_col, c->d_lu, c->d_kry,
+                    c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_iq, c->d_fperm, c->d_flid, c->d_fslot, c->d_fcnt, c->d_pslot, c->d_ppart, c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin, c->d_woplan, c->d_wgh, c->d_wgx, c->d_wgh4, c->d_wpart, c->d_wsplit, c->d_colstat, c->d_forceflag, c->d_rdcnt, c->d_cheb, c->d_colratio, c->d_g1, c->d_bplan, c->d_g0, c->d_ye, c->d_col, c->d_lu, c->d_kry,
                     c->d_d0, c->d_d1x, c->d_d1y, c->d_sh0, c->d_sh1, c->d_own[1], c->d_own[2], c->d_pcw};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (void* p : c->retired) (void)hipFree(p);
@@ -1453,6 +1472,8 @@ static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
         if (splits && part == MIMSEM_PART_INTERIOR) { g0 = c->w_nbgroups; r0 = c->w_nbrec; }
         a.wlane = c->d_wlane; a.wplan = own ? c->d_woplan : c->d_wplan; a.wgroups = g1 - g0; a.wg0 = g0; a.wdump = own ? 0 : c->w_npart;
         a.wgh = own ? c->d_wgh : nullptr; a.wgx = c->d_wgx;
+        // (the four-level pass adds a pair row to a 32-bit lane offset of the thickInv pair table: half the range of wave_fits)
+        a.wgh4 = (own && (long long)c->nEl*es.mp12 < (1LL << 27)) ? c->d_wgh4 : nullptr;
         a.wsing = c->w_nsing ? c->d_wsing : nullptr; a.wnode = c->d_wnode; a.wG = c->d_wG; a.wR = c->d_wR;
         if (c->d_tIn) { a.tIp = c->d_tIn; a.tps = (long long)c->n0*2; a.tnode = 1; }     // (MIMSEM_WAVE_TNODE=1: thickInv per node)
         a.lch = wave_level_chunk(c, nlev);

@@ -121,12 +121,14 @@ struct mimsem_ctx {
     std::vector<int> h_e1x, h_e1y;      // element -> 1-form slot lists, kept on EVERY context (edge multiplicities of the PCBJACOBI builders, ksp.hip)
     int4* d_wlane = nullptr;            // [w_ngroups][64] {element of the lane, load pair: even slot b, staging positions of x[b] and of x[b+1]
                                         //   (two 16-bit positions each; the dump position where nobody wants the value)}
-    // owner-computes form (round 7, build_wave_own; Umat at p = 3, default, MIMSEM_WAVE_OWN=0: off): every store pair written finished by
+    // owner-computes form (round 7, build_wave_own; Umat at p = 3, default, MIMSEM_WAVE_OWN=0: off, =1: ghost pass per batch): every store pair written finished by
     // its one owner group, which computes the neighbour's contribution across its ghost sides -- one launch, no perimeter pass
     bool w_own = false;
     int4* d_woplan = nullptr;           // [w_ngroups][64] store pairs of the form (as d_wplan; every destination in y)
     int4* d_wgh = nullptr;              // [w_ngroups][16] packed ghost lanes (side*4 + point; round 9)
     int* d_wgx = nullptr;               // [w_ngroups][64] slot the lane gathers per level (16 per ghost side)
+    int4* d_wgh4 = nullptr;             // [w_ngroups][64] ghost lanes of the four-level pass (own4::k_apply_wave: DPP row = ghost side), or
+                                        //   null: MIMSEM_WAVE_OWN=1 keeps the pass per batch of two levels for every call
     int4* d_wtfin = nullptr; int w_ntiles = 0, w_ninner = 0;      // tile mode (round 5): [w_ntiles][64] {slot, LDS position of part A, of part B, 0}
     int4* d_wplan = nullptr;            // [w_ngroups][64] store pair {dst, result positions of its first and second slot (2 x 16 bit, the
                                         //   strip's zero for a missing contributor), 0}: dst >= 0: y[dst], y[dst+1]; dst <= -2: partial sums
@@ -232,6 +234,7 @@ struct ElemArgs {
     // direct path: DoFs touched by exactly ONE element are written straight into y (no ye round trip, no pass 2 for them)
     const int *d0, *d1x, *d1y;       // [nEl][n0e|n1e]: the slot when the element is its only contributor, else -1 (null = off)
     int lstep = 1;                   // geometry level of row r: lev0 + r lstep; 0 = every row at lev0 (mimsem_op_apply_levels, k_elem_apply only)
+    const int4* wgh4 = nullptr;      // owner-computes form: ghost lanes of the four-level pass (build_wave_own), or null: the pass per batch
 };
 
 // The vector update a Chebyshev step still owes (mimsem_block_chebyshev_solve: the gather epilogue of step k folded into the element pass of

@@ -1689,6 +1689,17 @@ static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     if (tile && (!TILEABLE || a.wgroups%4 != 0 || a.wg0 != 0 || a.lch*a.wcpp > MIMSEM_WTLEV)) return MIMSEM_ERR_STATE;
     const bool own = a.wgh != nullptr;                   // owner-computes form (Umat at p = 3): one launch, no perimeter pass
     if (own && (N != 3 || op != MIMSEM_OP_UMAT || tile || a.wnp < 1)) return MIMSEM_ERR_STATE;
+    if constexpr (N == 3 && MIMSEM_WLB == 2 && MIMSEM_WAHEAD == 2) {      // (the A/B builds of those two knobs keep the form below)
+        if (own && a.wgh4 && a.lch == WLC) {             // the ghost pass per four levels (single-level calls keep the form below)
+#define MIMSEM_WL4(ACC) \
+            if (c->ev_k1[0]) hipExtLaunchKernelGGL((own4::k_apply_wave<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
+            else hipLaunchKernelGGL((own4::k_apply_wave<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, a)
+            if (a.accum) { MIMSEM_WL4(true); } else { MIMSEM_WL4(false); }
+#undef MIMSEM_WL4
+            MIMSEM_HIP_TRY(hipGetLastError());
+            return MIMSEM_OK;
+        }
+    }
 #define MIMSEM_WL2(OPV, LCT, ACC, TL, OW) \
         if (c->ev_k1[0]) hipExtLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL, OW>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
         else hipLaunchKernelGGL((k_apply_wave<N, OPV, LCT, ACC, TL, OW>), dim3(grid), dim3(64*WNW), 0, c->stream, a)

@@ -579,6 +579,208 @@ levels_done: ;
 #endif
 }
 
+// own4::k_apply_wave<3, UMAT, 8, ACCUM>: the owner-computes form of k_apply_wave<3, UMAT, 8, ACCUM, false, true> with ONE ghost pass per
+// FOUR levels (build_wave_own, gh4).  The packed pass above lays two levels out as x-normal | y-normal rows, each with room for 4
+// sides, but a group has at most 4 ghost sides in all: half of its lanes idle.  Here ghost side b IS DPP row b and the row's other
+// direction holds the four levels m of a double batch (x-normal: qx = m, qy = point; y-normal: qy = m, qx = point), so the point along
+// the side still sits where the element keeps that point's coefficients and every slot comes out of the fma sequence above -- the
+// same bits.  The pass runs at the EVEN batches of the ring, for the batch being computed and the next one: the next batch's gathered
+// DoFs are staged one batch early (their wait moves with them), a lane of the second batch (m >= 2) keeps its result in a register
+// and puts it into its level's strip in the next batch's result phase; the lanes with nothing to put write to a dump position.  An
+// item with an odd number of batches runs its last pass half empty, on the clamped loads of the batch it does not have.  Everything
+// else -- the element's algebra, the level pipeline, the stores, the exits -- is the kernel above, written out for its one case.
+namespace own4 {
+template <int N, int OP, int LCT, bool ACCUM>
+__global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_apply_wave(ElemArgs a) {
+    using D = Dims<N>;
+    static_assert(N == 3 && OP == MIMSEM_OP_UMAT && LCT == 8 && MIMSEM_WLB == 2 && MIMSEM_WAHEAD == 2, "owner-computes Umat at p = 3, rings of four batches of two levels");
+    constexpr int LPE = D::LPE, EPW = 64/LPE, ND = 2*D::n1e, NW = WNW;
+    constexpr int NACC = EPW*ND, ZERO = NACC + 128;
+    constexpr int RS = D::mp1 + (D::mp1 & 1);
+    constexpr int XT = D::n1e + D::mp1*RS;
+    constexpr int SXE = XT + 2*(LPE - D::n1e) + ((XT + 2*(LPE - D::n1e)) & 1);
+    constexpr int WGR = NACC + 136;                      // the ghost results of a level, side*4 + point; behind them 16 dump positions
+    constexpr int SW = (EPW*SXE > WGR + 32) ? EPW*SXE : WGR + 32;
+    constexpr int LB = 2, AHEAD = 2, WGX = MIMSEM_WGX;
+    static_assert(LPE == 16 && EPW == 4 && ZERO >= EPW*SXE && ZERO < SW, "an element is one DPP row; the zero entry lies beyond the staged x and the results");
+    __shared__ double sE[NW][D::mp1*N];
+    __shared__ double s_x[NW][LB][SW];
+    __shared__ __attribute__((aligned(16))) double s_g[NW][2*LB][WGX];      // the gathered ghost DoFs of the four levels of a pass
+
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63, el = lane/LPE, q = lane%LPE;
+    const unsigned nchunk = (unsigned)a.wnp;
+    const unsigned nitems = (unsigned)a.wgroups*nchunk;
+    const unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x, a.swz & 1);
+    const unsigned item = bid*NW + (unsigned)wv;
+    if (item >= nitems) return;                          // wave-uniform
+    unsigned g, ch;
+    if (a.swz & 2) { g = item/nchunk; ch = item%nchunk; }
+    else           { g = item%(unsigned)a.wgroups; ch = item/(unsigned)a.wgroups; }
+    g += (unsigned)a.wg0;
+    int lbeg = 2*((int)ch*a.wpb + min((int)ch, a.wpr));
+    const int lend = min(a.nlev, lbeg + 2*(a.wpb + ((int)ch < a.wpr ? 1 : 0)));
+    const int4 wl = a.wlane[(size_t)g*64 + lane];
+    const int4 wp = a.wplan[(size_t)g*64 + lane];
+    const int4 gh = a.wgh4[(size_t)g*64 + lane];
+    const int gxs = a.wgx[(size_t)g*64 + lane];
+    const double2* hp = (const double2*)(a.wG + (size_t)gh.x*4);
+    const double2 h01 = hp[0], h23 = hp[1];
+    const bool gyn = (gh.z & 1) != 0, gsz = (gh.z & 4) != 0, gidle = (gh.z & 8) != 0;
+    const int gc0 = (gh.z & 2) ? 3 : 0;
+    const int gm = gyn ? (lane >> 2) & 3 : lane & 3;     // the ghost lane's level of the double batch
+    const unsigned gxo = 8u*(unsigned)gxs;
+    // thickInv of the ghost lane: its level's half of a pair; a lane of the second batch takes the NEXT pair row (same parity, the
+    // batch's first level + 2) -- only where the call has that level: otherwise it stays on the first batch's row, for nothing
+    const unsigned tgo = 16u*(unsigned)gh.y + 8u*(unsigned)(gm & 1), ghi = gm >= 2 ? 0xFFFFFFFFu : 0u;
+    const double2* gp = (const double2*)(a.wG + ((size_t)g*64 + lane)*4);
+    const double2 g01 = gp[0], g23 = gp[1];
+    const double gaa = a.scale*g01.x, gab = a.scale*g01.y, gbb = a.scale*g23.x;
+    const int e = wl.x;
+    const int qx = q%D::mp1, qy = q/D::mp1;
+    const unsigned gq = (unsigned)e*D::mp12 + (unsigned)q;
+    const unsigned xo = 8u*(unsigned)wl.y;
+    const unsigned to = 16u*gq;
+    double2 px[LCT]; double pt0[LCT], pg[LCT], ptg[LCT/(2*LB)];
+    auto load_batch = [&](int r0, int lev0_) {
+        {
+            const int L = a.lev0 + min(lev0_, a.nlev - 1);   // (a level beyond the range reads a valid pair; nothing is stored for it)
+            const char* row = (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps);
+            const double2 tp = WLOAD(double2, row + to);
+            pt0[r0] = tp.x; pt0[r0 + 1] = tp.y;
+            if ((r0/LB)%2 == 0) {                            // ONE load per ghost pass
+                const unsigned nx = lev0_ + 2 <= a.nlev - 1 ? 8u*(unsigned)a.tps : 0u;      // wave-uniform
+                ptg[r0/(2*LB)] = *(const double*)(row + (tgo + (ghi & nx)));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < LB; i++) {
+            const int r = r0 + i;
+            const int lev = min(lev0_ + i, a.nlev - 1);      // beyond the last level: re-read it (nothing is stored for it)
+            px[r] = WLOAD(double2, (const char*)(a.x + (size_t)lev*a.xs) + xo);
+            pg[r] = *(const double*)((const char*)(a.x + (size_t)lev*a.xs) + gxo);
+        }
+    };
+#pragma unroll
+    for (int b = 0; b < AHEAD; b++) { load_batch(b*LB, lbeg + b*LB); __builtin_amdgcn_sched_barrier(0); }   // in THIS order: vmcnt is in-order
+    {
+        double* se = sE[wv];
+#pragma unroll
+        for (int k = 0; k < D::mp1*N; k++) se[k] = a.Etab[k];
+    }
+    wave_fence();
+
+    // ---- level-invariant registers (as above) ----
+    const bool vert = (a.flags & MIMSEM_FLAG_VERT) != 0;
+    double Ex[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) Ex[j] = sE[wv][qx*N + j];
+    double cu[4], cp[4], pq[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int j = (qy - k) & 3;
+        cu[k] = j < 3 ? sE[wv][qy*N + j] : 0.0;
+        cp[k] = qy < 3 ? a.alpha*sE[wv][j*N + qy] : 0.0;
+        pq[k] = qx < 3 ? a.alpha*sE[wv][k*N + qx] : 0.0;
+    }
+    double kc[3];
+    const double hgaa = a.scale*h01.x, hgab = a.scale*h01.y, hgbb = a.scale*h23.x;
+    const double gm0 = gyn ? hgab : hgaa, gm1 = gyn ? hgbb : hgab;
+#pragma unroll
+    for (int t = 0; t < 3; t++) {
+        const int tt = !gyn ? t : (gc0 == 0 ? (t == 0 ? 0 : 3 - t) : 2 - t);
+        kc[t] = sE[wv][gc0*N + tt];
+    }
+    const double* const sgl = &s_g[wv][gm][gh.w & 0xFF];  // the ghost lane's quadruple {cross 0, cross 1, cross 2, side DoF} at its level
+    // where its result goes: WGR + side*4 + point of its level's strip -- in the pass's own batch (m < 2) or in the next one (m >= 2);
+    // in the other of the two, and on an idle lane in both, a dump position behind the results
+    double* const sdump = &s_x[wv][(lane >> 5) & 1][WGR + 16 + (lane & 15)];
+    double* const sgr0 = (!gidle && gm < 2) ? &s_x[wv][gm & 1][WGR + (gh.w >> 8)] : sdump;
+    double* const sgr1 = (!gidle && gm >= 2) ? &s_x[wv][gm & 1][WGR + (gh.w >> 8)] : sdump;
+    const int xd00 = wl.z & 0xFFFF, xd01 = (wl.z >> 16) & 0xFFFF, xd10 = wl.w & 0xFFFF, xd11 = (wl.w >> 16) & 0xFFFF;
+    const bool hasx = q < D::n1e;
+    const int aci0 = hasx ? el*ND + q : NACC + lane;
+    const int aci1 = qx < 3 ? el*ND + D::n1e + qy*3 + qx : NACC + 64 + lane;
+    const int ldx = q < D::n1e ? q : 0, ldy = D::n1e + qy*RS + (qx < 3 ? qx : 0);
+    const bool okx = q < D::n1e, oky = qx < 3;
+    const int wp00 = wp.y & 0xFFFF, wp01 = (wp.y >> 16) & 0xFFFF, wp10 = wp.z & 0xFFFF, wp11 = (wp.z >> 16) & 0xFFFF;
+    const bool wy = wp.x >= 0;
+    gchar* wo = (gchar*)(wy ? (a.y + (size_t)lbeg*a.ys + wp.x) : (a.out + (size_t)lbeg*a.os + (-wp.x - 2)));
+    const long long wst = 8*(wy ? a.ys : a.os);
+#pragma unroll
+    for (int i = 0; i < LB; i++) s_x[wv][i][ZERO] = 0.0;
+    gchar* const dumpp = (gchar*)(a.out + a.wdump + 2*lane);
+    double gkeep = 0.0;                                  // the ghost result of a lane of the pass's second batch
+    for (; lbeg < lend; lbeg += LCT) {                   // wave-uniform: one trip = the ring of LCT levels
+    const int nl = lend - lbeg;
+#pragma unroll
+    for (int b0 = 0; b0 < LCT; b0 += LB) {
+        const bool pass = (b0/LB)%2 == 0;                // (unrolled: a constant)
+        __builtin_amdgcn_sched_barrier(0);
+        load_batch((b0 + AHEAD*LB)%LCT, lbeg + b0 + AHEAD*LB);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < LB; i++) {
+            double* st = s_x[wv][i];
+            st[xd00] = px[b0 + i].x; st[xd01] = px[b0 + i].x; st[xd10] = px[b0 + i].y; st[xd11] = px[b0 + i].y;
+        }
+        if (pass) {
+#pragma unroll
+            for (int i = 0; i < 2*LB; i++) s_g[wv][i][lane] = pg[b0 + i];
+        }
+        wave_fence();
+        double yxr[LB], yyr[LB];
+#pragma unroll
+        for (int i = 0; i < LB; i++) {
+            const int l = b0 + i;
+            const double* sx = s_x[wv][i] + el*SXE;
+            double X = sx[ldx], Y = sx[ldy];
+            if (!okx) X = 0.0;
+            if (!oky) Y = 0.0;
+            const double u = dpp_rows(cu, X);
+            const double v = dpp_quad<3>(Ex, Y);
+            const double fac = vert ? pt0[l] : 1.0;
+            const double ra = fac*fma(gab, v, gaa*u), rb = fac*fma(gbb, v, gab*u);
+            yxr[i] = dpp_rows(cp, ra); yyr[i] = dpp_quad<4>(pq, rb);
+        }
+        double gyr = 0.0;
+        if (pass) {                                       // the ghost pass: every side point of four levels at once
+            const double2 c01 = *(const double2*)sgl, c2s = *(const double2*)(sgl + 2);
+            const double S = gsz ? 0.0 : c2s.y;
+            double C = fma(kc[0], c01.x, gyn ? 0.0 : -0.0);
+            C = fma(kc[1], c01.y, C);
+            C = fma(kc[2], c2s.x, C);
+            const double Ar = dpp_rows(cu, S), Aq = dpp_quad<3>(Ex, S);
+            const double gu_ = gyn ? C : Ar, gv_ = gyn ? Aq : C;
+            const double gf = vert ? ptg[b0/(2*LB)] : 1.0;
+            const double gr = gf*fma(gm1, gv_, gm0*gu_);
+            const double Pr = dpp_rows(cp, gr), Pq = dpp_quad<4>(pq, gr);
+            gyr = gyn ? Pq : Pr;
+        }
+        wave_fence();
+#pragma unroll
+        for (int i = 0; i < LB; i++) { double* sacc = s_x[wv][i]; sacc[aci0] = yxr[i]; sacc[aci1] = yyr[i]; }
+        if (pass) { *sgr0 = gyr; gkeep = gyr; }
+        else *sgr1 = gkeep;
+        wave_fence();
+#pragma unroll
+        for (int i = 0; i < LB; i++) {
+            const int l = b0 + i;
+            const double* sacc = s_x[wv][i];
+            double2 val;
+            val.x = sacc[wp00] + sacc[wp01]; val.y = sacc[wp10] + sacc[wp11];
+            gdouble* o = (gdouble*)(l < nl ? wo : dumpp);
+            if constexpr (ACCUM) { double o0 = o[0], o1 = o[1]; if (!wy) { o0 = 0.0; o1 = 0.0; } val.x += o0; val.y += o1; }
+            o[0] = val.x; o[1] = val.y;
+            wo += wst;
+        }
+        wave_fence();
+        if (b0 + LB < LCT) wave_exit_if_done(nl - (b0 + LB));     // (nothing follows the level loop: see wave_exit_if_done)
+    }
+    }
+}
+}  // namespace own4
+
 // k_apply_wave2<OP, LCT, ACCUM>: the 2-form-valued operators at p = 3 -- Wmat, Whmat (2-form in), WtQUmat, WtQdUdz_mat (1-form in, 1-form
 // coefficient field; eul/Assembly.cpp:330-360, 1262-1290, 940-1000, 1585-1640) -- on the same footing as k_apply_wave: one wavefront per
 // (wave-group of 2 x 2 elements, chunks of 8 levels), the packed metric record, the level pipeline, a branch-free body, and ALL of the
