@@ -310,6 +310,20 @@ int mimsem_euler_energetics_column(mimsem_ctx* ctx, const double* velz, const do
 int mimsem_horiz_bernoulli(mimsem_ctx* ctx, int nk, const double* velx1, const double* velx2, long long ldu,
                            const double* velz1, const double* velz2, long long ldz, double scale, double* out, long long ldo);
 
+/* The mass-flux right-hand side of HorizSolve::diagnose_fluxes (eul/HorizSolve.cpp:298-306) and HorizSolve::momentum_rhs (:538-547) for
+ * levels 0 .. nk-1 in TWO launches (k_horiz_flux_rhs, csrc/flux_rhs.inc, and the 1-form gather) instead of four accumulating Uhmat applies:
+ *   out_k = sum_ab c_ab Uvec::assemble_hu(k, scale, u_a[k], h_b[k], false, c_ab), assembled (the reverse ADD_VALUES scatter)
+ *   c_11 = c_22 = 1/3, c_12 = c_21 = 1/6                                                       (eul/Assembly.cpp:2198-2279)
+ * u1, u2: local 1-form rows [nk][n1] at the row stride ldu; h1, h2: 2-form rows [nk][n2] at the row stride ldh; out: 1-form rows [nk][n1]
+ * at the row stride ldo (strides in doubles); scale: the SCALE of the assembled matrices.  u1 == u2 and h1 == h2 are allowed (the first
+ * stage of Euler::Strang calls it so); out must not overlap an input.  Element orders 1..7.  The element pass leaves element-local results
+ * in the context's element workspace, the gather sums every edge slot's contributions in the plan's order: no atomics, a fixed summation
+ * order -- two calls on the same input give the same bits; no host synchronisation; capturable once a call outside the capture has sized
+ * the workspace (MIMSEM_ERR_STATE if it had to grow inside one).  A null pointer, a negative stride, out equal to an input or nk outside
+ * 1..ctx nk: MIMSEM_ERR_ARG; an order outside 1..7: MIMSEM_ERR_UNSUPPORTED; nothing launched, out untouched.                           */
+int mimsem_horiz_flux_rhs(mimsem_ctx* ctx, int nk, const double* u1, const double* u2, long long ldu,
+                          const double* h1, const double* h2, long long ldh, double scale, double* out, long long ldo);
+
 /* Row N3: the packed [u,h] operator of the shallow-water Picard step, SWEqn::assemble_operator (src/SWEqn_Picard.cpp:622-725),
  * which the reference forms with MatMatMult / MatGetRow / MatSetValues and hands to KSPSolve(kspA):
  *     y_u = (M1 + a R(f)) u + a g E12 M2 h        y_h = M2 (a H E21 u + h)        a = ROS_ALPHA dt, g = grav, H = H_MEAN

@@ -2164,3 +2164,4 @@ int launch_halo_unpack(mimsem_ctx* c, const int* idx, int count, int nlev, int m
 #include "elem_block_pc.inc"
 #include "energetics.inc"
 #include "bernoulli.inc"
+#include "flux_rhs.inc"

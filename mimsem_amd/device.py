@@ -644,6 +644,24 @@ class Engine:
               "horiz_bernoulli")
         return out
 
+    def flux_rhs(self, u1, u2, h1, h2, scale=1.0, out=None):
+        """mimsem_horiz_flux_rhs: the assembled mass-flux right-hand side sum_ab c_ab Uvec::assemble_hu(u_a, h_b) of HorizSolve::diagnose_fluxes
+        and momentum_rhs (eul/HorizSolve.cpp:298-306, :538-547) of every level in two launches; u1, u2 [nk, n1], h1, h2 [nk, n2] -> [nk, n1].
+        Rows contiguous, any row stride (the two of a pair share it); u1 is u2 and h1 is h2 are allowed, out must not overlap an input"""
+        x1 = self._rows(u1, self.sizes[1], "u1", min_rows=1, strided="r")
+        nk = x1.shape[0]
+        x2 = self._rows(u2, self.sizes[1], "u2", rows=nk, strided="r")
+        r1, r2 = self._like(self.sizes[2], nk, strided="r", h1=h1, h2=h2)
+        _need(nk <= self.nk, "u1: at most the context's %d levels" % self.nk)
+        _need(nk == 1 or x1.stride(0) == x2.stride(0), "u1, u2: one row stride")
+        _need(r1 is not None and r2 is not None and (nk == 1 or r1.stride(0) == r2.stride(0)), "h1, h2: [nk, n2] with one row stride")
+        out, o2 = self._out(out, nk, self.sizes[1], exact=True, strided="w")
+        ins = [_ps(t)[0] for t in (x1, x2, r1, r2)]
+        _need(_ps(o2)[0] not in ins, "out: must not be an input")
+        ld = (lambda t: t.stride(0)) if nk > 1 else (lambda t: 0)                    # (one level: row stride 0)
+        check(self.L.mimsem_horiz_flux_rhs(self.ctx, nk, ins[0], ins[1], ld(x2), ins[2], ins[3], ld(r2), scale, _ps(o2)[0], ld(o2)), "horiz_flux_rhs")
+        return out
+
     def _sw_rows(self, x, out):
         """packed rows [u | h] of the sw_operator family (contiguous rows, any row stride): the view of x, the result and its view"""
         x2 = self._rows(x, self.sizes[1] + self.sizes[2], "x", strided="r")

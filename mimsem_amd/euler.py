@@ -1,4 +1,5 @@
-"""Euler::Strang_ec (eul/Euler_2.cpp:1366-1557): one time step of the 3-D compressible Euler equations -- explicit horizontal momentum
+"""Euler::Strang_ec (eul/Euler_2.cpp:1366-1557) and Euler::Strang (:1146-1364; Euler.strang says where it differs): one time step of the 3-D
+compressible Euler equations -- explicit horizontal momentum
 predictor, implicit vertical Newton solve with the horizontal transport re-evaluated in every iteration, explicit horizontal corrector --
 joined from the parts that each run on the device already:
 
@@ -57,6 +58,9 @@ class Euler:
     # diagnose_Phi inside the step: the one-launch kernel (mimsem_horiz_bernoulli) or the eight composed launches -- decided by the
     # measurement of scripts/prof_strang.py (profiles/strang_ec.txt)
     FUSED_PHI = True
+    # the mass-flux right-hand side inside strang: the two-launch kernel (mimsem_horiz_flux_rhs) or four accumulated Uhmat applies -- to be
+    # decided by the measurement of scripts/prof_strang2.py (profiles/strang.txt); that file does not exist yet, so the composed route
+    FUSED_HU = False
 
     def __init__(self, eng, dt, levs, quad_coords, hs_forcing=False, hs_lat=None, newton_maxit=20, newton_tol=1e-12, do_visc=True):
         """eng: Engine (one context, global numbering, nk >= 2); levs: interface heights on the quadrature grid [nk+1, nq] (VertSolve.init_gz);
@@ -85,11 +89,16 @@ class Euler:
         self.init1_redone = 0            # init1 solves run again after a missed check
         self._m2inv = self._last = self._thick = None
 
-    def _step(self, velx, velz, rho, rt, exner, carried):
+    def _step(self, velx, velz, rho, rt, exner, carried, ec=True):
         """one evaluation of the step from `carried` = (first_step, u_curr, uz); changes nothing of self.first_step / u_* / uz*.
+        ec: Strang_ec (theta in the levels, the _ec right-hand sides, solve_schur_eta); else Strang (theta on the interfaces, momentum_rhs /
+        advection_rhs, solve_schur_2) -- the comments name the lines of Strang_ec, Strang's are :1170-1300 in the same order.
         Returns the new fields, the carried vectors of the step and whether every HorizSolve.verify() along the way passed"""
         eng, nk, horiz, vert, vort = self.eng, self.nk, self.horiz, self.vert, self.vort
         first, u_curr, uz_last = carried
+        rows_th = nk if ec else nk + 1                                                  # theta: L2 in the levels / on the nk+1 interfaces
+        mom_rhs, adv_rhs = (horiz.momentum_rhs_ec, horiz.advection_rhs_ec) if ec else (horiz.momentum_rhs, horiz.advection_rhs)
+        solve = vert.solve_schur_eta if ec else vert.solve_schur_2
         to_v = eng.l2_horiz_to_vert
         to_h = lambda a, rows=nk: eng.l2_vert_to_horiz(a.contiguous(), rows)
         # 0. the initial fields in both layouts (:1390-1395); the carried vectors of this step (:1399-1417)
@@ -98,13 +107,13 @@ class Euler:
         uz_prev = None if first else uz_last
         u_prev, u_curr = u_curr, velx.clone()
         # 1. explicit horizontal momentum solve, the predictor (:1421-1457)
-        theta_0 = to_h(eng.diag_theta(0, rho_v, rt_v))
+        theta_0 = to_h(eng.diag_theta(0 if ec else 1, rho_v, rt_v), rows_th)
         uz = vort.horiz_pot_vort(velx, rho)
         dwdx1 = vort.vert_vort(velz_h0, rho)
         if first:
             uz_prev = uz                                                                # :1425
         Fz = vort.vert_mass_flux(velz_h0, velz_h0, rho, rho)
-        Fu = horiz.momentum_rhs_ec(theta_0, uz, uz, velz_h0, velz_h0, exner, velx, velx, rho, rho, Fz=Fz, dwdx1=dwdx1, dwdx2=dwdx1)
+        Fu = mom_rhs(theta_0, uz, uz, velz_h0, velz_h0, exner, velx, velx, rho, rho, Fz=Fz, dwdx1=dwdx1, dwdx2=dwdx1)
         velx_p = self.hmom.predictor(velx, u_prev, Fu, exner, first)
         ok = [horiz.verify()]
         # 2. implicit vertical solve (:1461-1466): advection_rhs_ec(velx_0, velx, rho_i, rho_j, theta_l2_h) at the head of every Newton iteration
@@ -112,11 +121,11 @@ class Euler:
 
         def forcing(rho_i, rho_j, theta_l2_h):
             ok.append(horiz.verify())                                                   # (the solves of the iteration before)
-            dF, dG, _, _ = horiz.advection_rhs_ec(velx, velx_p, rho, to_h(rho_j), to_h(theta_l2_h))
+            dF, dG, _, _ = adv_rhs(velx, velx_p, rho, to_h(rho_j), to_h(theta_l2_h, rows_th))
             return to_v(dF), to_v(dG)
-        velz_n, rho_nv, rt_nv, exner_nv = vert.solve_schur_eta(velz, rho_v, rt_v, exner_v, self.zv, horiz_forcing=forcing, udwdx=None,
-                                                               hs_lat=self.hs_lat if self.hs_forcing else None,
-                                                               maxit=self.newton_maxit, tol=self.newton_tol)
+        velz_n, rho_nv, rt_nv, exner_nv = solve(velz, rho_v, rt_v, exner_v, self.zv, horiz_forcing=forcing, udwdx=None,
+                                                hs_lat=self.hs_lat if self.hs_forcing else None,
+                                                maxit=self.newton_maxit, tol=self.newton_tol)
         rho_n, rt_n, exner_n = to_h(rho_nv), to_h(rt_nv), to_h(exner_nv)
         velz_hn = to_h(velz_n, nk - 1)
         # 3. explicit horizontal solve, the corrector (:1470-1493): the time-centred theta_l2_h, exner_h the vertical solve left; the friction
@@ -124,8 +133,9 @@ class Euler:
         uz = vort.horiz_pot_vort(velx_p, rho_n)
         dwdx2 = vort.vert_vort(velz_hn, rho_n)
         Fz = vort.vert_mass_flux(velz_h0, velz_hn, rho, rho_n)
-        Fu = horiz.momentum_rhs_ec(to_h(vert.theta_l2_h), uz, uz_prev, velz_hn, velz_h0, to_h(vert.exner_h), velx, velx_p, rho, rho_n,
-                                   Fz=Fz, dwdx1=dwdx1, dwdx2=dwdx2, Fk=horiz.Fk)
+        theta_h = to_h(vert.theta_l2_h if ec else vert.theta_h, rows_th)
+        Fu = mom_rhs(theta_h, uz, uz_prev, velz_hn, velz_h0, to_h(vert.exner_h), velx, velx_p, rho, rho_n,
+                     Fz=Fz, dwdx1=dwdx1, dwdx2=dwdx2, Fk=horiz.Fk)
         velx_n = self.hmom.corrector(velx, Fu, exner_n)
         ok.append(horiz.verify())
         return (velx_n, velz_n, rho_n, rt_n, exner_n), (u_prev, u_curr, uz, uz_prev), all(ok)
@@ -133,15 +143,31 @@ class Euler:
     def strang_ec(self, velx, velz, rho, rt, exner, diagnostics=True):
         """one step; the inputs are not changed.  Returns (velx, velz, rho, rt, exner, values): the new fields and the twelve numbers of
         Energetics.diagnostics on them (None with diagnostics=False)"""
+        return self._checked_step("strang_ec", True, velx, velz, rho, rt, exner, diagnostics)
+
+    def strang(self, velx, velz, rho, rt, exner, diagnostics=True):
+        """Euler::Strang (eul/Euler_2.cpp:1146-1364), the integrator of eul/HeldSuarez.cpp: the skeleton of strang_ec -- the same carried state,
+        check points, redo on a miss and energetics line -- with theta on the nk+1 interfaces:
+          stage 1 (:1199-1251)  theta_0 = diagTheta (= VertSolve::diagTheta2), HorizSolve.momentum_rhs in place of momentum_rhs_ec
+          stage 2 (:1253-1260)  VertSolve.solve_schur_2 with HorizSolve.advection_rhs(velx_0, velx, rho_0, rho_j, theta_h) as its forcing
+          stage 3 (:1262-1300)  momentum_rhs on vert.theta_h, vert.exner_h with Fk of the last advection_rhs; the corrector takes the new exner
+        The mass-flux right-hand sides of the two take the route FUSED_HU names.  Two lines of the reference are not mirrored: :1180 fills
+        vert->theta_h on the first step, which solve_schur_2 overwrites before any read; :1269 hands stage 3 the local velocity copies in the
+        other order than the global vectors (the :1475 quirk of Strang_ec) -- each velocity is paired with itself, as strang_ec does.
+        Same arguments and result as strang_ec"""
+        self.horiz.fused_hu = self.FUSED_HU
+        return self._checked_step("strang", False, velx, velz, rho, rt, exner, diagnostics)
+
+    def _checked_step(self, name, ec, velx, velz, rho, rt, exner, diagnostics):
         carried = (self.first_step, self.u_curr, self.uz)
         for attempt in range(2):
-            new, kept, ok_m1 = self._step(velx, velz, rho, rt, exner, carried)
+            new, kept, ok_m1 = self._step(velx, velz, rho, rt, exner, carried, ec)
             ok_vort = self.vort.check()                                                 # (the log is read and cleared)
             if ok_m1 and ok_vort:
                 break
             self.redone += 1
         else:
-            raise RuntimeError("Euler.strang_ec: a solve missed its check again after the switch to the adaptive solvers")
+            raise RuntimeError("Euler.%s: a solve missed its check again after the switch to the adaptive solvers" % name)
         self.u_prev, self.u_curr, self.uz, self.uz_prev = kept
         self.first_step = False
         self.steps += 1
@@ -192,17 +218,21 @@ class Euler:
         return self.init1(uq), velz, self.init2(rho), self.init2(rt), self.init2(exner)
 
     # ---- the loop, the `save` branch and the restart (eul/UMJS14.cpp:334-353, eul/Euler_2.cpp:1503-1534) -------------------------------------
-    def run(self, state, nsteps, dump_every=0, outdir="output", start_step=0, on_step=None):
-        """the driver's loop (eul/UMJS14.cpp:347-353): step = start_step dump_every + 1 .. nsteps, each one strang_ec whose twelve numbers go to
+    def run(self, state, nsteps, dump_every=0, outdir="output", start_step=0, on_step=None, integrator="strang_ec"):
+        """the driver's loop (eul/UMJS14.cpp:347-353): step = start_step dump_every + 1 .. nsteps, each one strang_ec (or, with
+        integrator="strang", strang: eul/HeldSuarez.cpp:352) whose twelve numbers go to
         outdir/energetics.dat (Energetics.write_line); on a step with step % dump_every == 0 the dump counter self.step (which starts at
         start_step) goes up by one and dump() writes under it.  on_step(step, values), when given, is called after every step.  Returns the
         final state"""
+        if integrator not in ("strang_ec", "strang"):
+            raise ValueError("Euler.run: integrator is 'strang_ec' or 'strang', got %r" % (integrator,))
+        one_step = getattr(self, integrator)
         self.step = start_step
         os.makedirs(outdir, exist_ok=True)
         path = os.path.join(outdir, "energetics.dat")
         state = tuple(state)
         for step in range(start_step * dump_every + 1, nsteps + 1):
-            out = self.strang_ec(*state)
+            out = one_step(*state)
             state = out[:5]
             Energetics.write_line(path, out[5])
             if dump_every and step % dump_every == 0:

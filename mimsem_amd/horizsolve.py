@@ -1,6 +1,6 @@
 """Host-side mirror of the reference's HorizSolve (eul/HorizSolve.cpp): the weak-form differential operators (grad, curl,
-laplacian :208-283) and the right-hand sides of the horizontal dynamics (diagnose_fluxes :285-327, advection_rhs_ec :380-417,
-diagnose_Phi :419-470, diagnose_q :472-493, momentum_rhs_ec :637-786) composed from engine applies, incidence stencils and
+laplacian :208-283) and the right-hand sides of the horizontal dynamics (diagnose_fluxes :285-327, advection_rhs :330-375,
+advection_rhs_ec :380-417, diagnose_Phi :419-470, diagnose_q :472-493, momentum_rhs :496-635, momentum_rhs_ec :637-786) composed from engine applies, incidence stencils and
 the device mass solves -- EVERY LEVEL IN ONE CALL of each operator (the reference loops `for(kk...)` around per-level
 assemble + MatMult + KSPSolve).  SURVEY 8(f) row N2.  Single GPU, global numbering (local == global vectors).
 
@@ -31,6 +31,8 @@ class HorizSolve:
         self.fg = None
         self.k2i_dev = None
         self.fused_phi = False                                  # diagnose_Phi: True = the one-launch kernel (Engine.bernoulli), False = the eight composed launches
+        self.fused_hu = False                                   # the mass-flux right-hand side of advection_rhs / momentum_rhs: True = Engine.flux_rhs
+                                                                # (two launches), False = _uvec_hu4 (four accumulated applies); the _ec methods keep _uvec_hu4
         if quad_coords is not None:
             self.coriolis(quad_coords)
 
@@ -79,12 +81,37 @@ class HorizSolve:
         self._ap("UHMAT", ub, f=hb, flags=VERT | ACCUM, alpha=1.0 / 3.0, out=hu)
         return hu
 
+    def _hu(self, ua, ub, ha, hb):
+        """_uvec_hu4 as the two non-_ec right-hand sides form it: by the fused kernel when fused_hu is set"""
+        if self.fused_hu:
+            return self.eng.flux_rhs(ua, ub, ha, hb, scale=SCALE)
+        return self._uvec_hu4(ua, ub, ha, hb)
+
+    def _theta_levels(self, theta):
+        """1/2 theta_k + 1/2 theta_{k+1} of theta on the nk+1 interfaces (:314-316, :515-517)"""
+        return self.eng.combine(theta[:-1], 0.5, beta=0.5, c=theta[1:])
+
     # ---- fluxes and the transport right-hand side ---------------------------------------------------------------------
-    def diagnose_fluxes(self, u1, u2, h1, h2, theta):
-        """:285-327 (theta_in_Wt = false): F = M1^-1 (hu), G = M1^-1 F(theta) F   -- all levels"""
-        F, _ = self.m1.solve(self._uvec_hu4(u1, u2, h1, h2))
-        G, _ = self.m1.solve(self._ap("UHMAT", F, f=theta, flags=VERT))
+    def diagnose_fluxes(self, u1, u2, h1, h2, theta, theta_in_Wt=False):
+        """:285-327: F = M1^-1 (hu), G = M1^-1 F(theta) F   -- all levels.  theta_in_Wt = false (the _ec callers): theta [nk, n2] in the
+        levels, F(theta_k; vert_scale).  theta_in_Wt = true (advection_rhs): theta [nk+1, n2] on the interfaces,
+        F(1/2 theta_k + 1/2 theta_{k+1}; no vert_scale) (:313-317), and the mass-flux right-hand side by fused_hu"""
+        if not theta_in_Wt:
+            F, _ = self.m1.solve(self._uvec_hu4(u1, u2, h1, h2))
+            G, _ = self.m1.solve(self._ap("UHMAT", F, f=theta, flags=VERT))
+            return F, G
+        F, _ = self.m1.solve(self._hu(u1, u2, h1, h2))
+        G, _ = self.m1.solve(self._ap("UHMAT", F, f=self._theta_levels(theta), flags=0))
         return F, G
+
+    def advection_rhs(self, u1, u2, h1, h2, theta):
+        """:330-375, theta [nk+1, n2] on the interfaces; returns dF = E21 Fk, dG = E21 Gk [nk, n2] in the horizontal layout (no M2 factor:
+        VertSolve::solve_schur_2 applies VB after adding them) and Fk, Gk, which are kept in self.Fk, self.Gk.  The do_temp_visc branch
+        (:341-364) is not built: the flag is false in the reference's constructor and no driver sets it"""
+        Fk, Gk = self.diagnose_fluxes(u1, u2, h1, h2, theta, theta_in_Wt=True)
+        dF, dG = self.eng.incidence("E21", Fk), self.eng.incidence("E21", Gk)
+        self.Fk, self.Gk = Fk, Gk
+        return dF, dG, Fk, Gk
 
     def advection_rhs_ec(self, u1, u2, h1, h2, theta):
         """:380-417 ; returns dF, dG in the horizontal layout (the caller's HorizToVert is mimsem_l2_transpose) and Fk, Gk"""
@@ -148,7 +175,12 @@ class HorizSolve:
         eng.combine(dp, 0.5, beta=1.0, c=fu, out=fu)
         if Fk is not None:
             self.k2i_dev = self.eng.wsum(1, eng.combine(Fk, 1.0, "mul", dp)) / SCALE   # stays on the device (no host sync: hipGraph-capturable)
-        # second vorticity term: interface i feeds levels i and i+1 (:704-746)
+        return self._vorticity_and_viscosity(fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2)
+
+    def _vorticity_and_viscosity(self, fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2):
+        """the end both momentum right-hand sides share (:565-623, :710-768): the second vorticity term and the biharmonic viscosity, added to fu"""
+        eng = self.eng
+        # second vorticity term: interface i feeds levels i and i+1
         dz = eng.combine(dudz1, 0.5, beta=0.5, c=dudz2)
         if dwdx1 is not None:
             eng.combine(dwdx1, -0.5, beta=1.0, c=dz, out=dz)
@@ -160,3 +192,23 @@ class HorizSolve:
         if self.do_visc:
             self._ap("UMAT", self.laplacian(self.laplacian(uh)), flags=VERT | ACCUM, out=fu)
         return fu
+
+    def momentum_rhs(self, theta, dudz1, dudz2, velz1, velz2, Pi, velx1, velx2, rho1, rho2, Fx=None, Fz=None, dwdx1=None, dwdx2=None, Fk=None):
+        """:496-635 for every level at once: momentum_rhs_ec with theta [nk+1, n2] on the interfaces.  There is no grad(theta); the pressure
+        gradient force is the single term fu += F(theta_h; no vert_scale) dPi, theta_h = 1/2 theta_k + 1/2 theta_{k+1} (:514-517, :556-558),
+        and self.k2i = sum_k Fk_k . (F(theta_h) dPi)_k / SCALE (:560-563, needs Fk).  The mass flux of the rotational term (Fx None) is
+        formed by fused_hu.  Returns fu [nk, n1]"""
+        eng = self.eng
+        Phi = self.diagnose_Phi(velx1, velx2, velz1, velz2)
+        dPi = self.grad(Pi)
+        fu = eng.incidence("E12", Phi)
+        uh = eng.combine(velx1, 0.5, beta=0.5, c=velx2)
+        q = self.diagnose_q(eng.combine(rho1, 0.5, beta=0.5, c=rho2), uh)
+        if Fx is None:
+            Fx, _ = self.m1.solve(self._hu(velx1, velx2, rho1, rho2))
+        self._ap("ROTMAT", Fx, f=q, flags=ACCUM, out=fu)
+        dp = self._ap("UHMAT", dPi, f=self._theta_levels(theta), flags=0)        # pressure gradient force
+        eng.combine(dp, 1.0, beta=1.0, c=fu, out=fu)
+        if Fk is not None:
+            self.k2i_dev = self.eng.wsum(1, eng.combine(Fk, 1.0, "mul", dp)) / SCALE   # stays on the device (no host sync)
+        return self._vorticity_and_viscosity(fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2)

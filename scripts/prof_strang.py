@@ -26,7 +26,9 @@ DT, NEWTON, STEPS = 30.0, 3, 5
 BYTES_PER_UNIT, PEAK = 1512.0, 8.0e12
 
 
-def main(path):
+def setup(what="prof_strang"):
+    """the bench mesh, its engine, an Euler object and the state of the measurements (see the module docstring) as a namespace"""
+    import types
     from mimsem_amd.device import DeviceMesh, Engine
     from mimsem_amd.euler import Euler
     from mimsem_amd.geom import Geom, gll_points
@@ -34,7 +36,7 @@ def main(path):
     from mimsem_amd.topo import Topo
     from mimsem_amd.workloads import z_levels
     if not torch.cuda.is_available():
-        raise SystemExit("prof_strang: no GPU (a timing needs one)")
+        raise SystemExit("%s: no GPU (a timing needs one)" % what)
     cs = CubedSphere(PN, NE, NPATCH); coords = sphere_coords(PN, NE)
     topos = [Topo(cs, p, NK) for p in range(NPATCH)]
     geoms = [Geom(t, cs, coords, NK) for t in topos]
@@ -65,7 +67,14 @@ def main(path):
     velz = eng.tensor(1e-3 * r.standard_normal((nEl, (NK - 1) * n2)) * float(dm.det.mean()) * 4.0 / (PN * PN))
     velz_h = eng.l2_vert_to_horiz(velz, NK - 1)
     velx2 = velx * 1.05
+    return types.SimpleNamespace(eng=eng, dm=dm, eu=eu, hs=hs, Euler=Euler, nEl=nEl, velx=velx, velx2=velx2, velz=velz, velz_h=velz_h,
+                                 rho=rho, rt=rt, exner=exner)
 
+
+def main(path):
+    s = setup()
+    eng, eu, hs, Euler, nEl = s.eng, s.eu, s.hs, s.Euler, s.nEl
+    velx, velx2, velz, velz_h, rho, rt, exner = s.velx, s.velx2, s.velz, s.velz_h, s.rho, s.rt, s.exner
     # ---- 1. diagnose_Phi: fused against composed ------------------------------------------------------------------------------------
     def route(fused):
         def fn():

@@ -3,6 +3,7 @@
 of dump index --start-step, the restart branch) and Euler.run.
 
   python scripts/run_umjs14.py --pn 3 --ne 24 --nk 30 --dt 75 --nsteps 20 --dump-every 10 --start-step 0 --outdir output
+  (--integrator strang: Euler.strang in place of Euler.strang_ec; --hs-forcing: the Held-Suarez forcing on the same initial state)
 
 Prints per step the Newton iterations of the vertical solve with their last norms, the steps redone so far and the energetics line; at the end
 steps per second (host clock between device synchronisations around every step, the first step left out as warm-up: it finds the solvers' fixed
@@ -33,6 +34,9 @@ def parse(argv):
     ap.add_argument("--outdir", default="output")
     ap.add_argument("--vp", type=float, default=None, help="amplitude of the wind perturbation (default: umjs14.VP; 0: the steady state)")
     ap.add_argument("--newton-maxit", type=int, default=20)
+    ap.add_argument("--integrator", choices=("strang_ec", "strang"), default="strang_ec",
+                    help="Euler.strang_ec (eul/UMJS14.cpp) or Euler.strang (the integrator of eul/HeldSuarez.cpp)")
+    ap.add_argument("--hs-forcing", action="store_true", help="Held-Suarez friction and temperature forcing (Euler's hs_forcing)")
     ap.add_argument("--patches", type=int, default=0, help="patches of the mesh (default: 24 for an even ne >= 8, else 6)")
     ap.add_argument("--profile", default=None, help="write the summary to this file as well")
     ap.add_argument("--time-limit", type=float, default=1200.0)
@@ -63,9 +67,12 @@ def work(a):
         g.set_levels(um.levels(a.nk, coords[g.loc0]))
     eng = Engine(DeviceMesh(topos, geoms, nk=a.nk, numbering="global"))
     xq = coords[eng.mesh.gidq]
-    eu = Euler(eng, a.dt, um.levels(a.nk, xq), xq, newton_maxit=a.newton_maxit)
-    head = "UMJS14 baroclinic wave, p = %d, %d x %d x 6 sphere (%d elements), %d levels, dt = %g s; %s" \
-        % (a.pn, a.ne, a.ne, eng.nEl, a.nk, a.dt, torch.cuda.get_device_name(0))
+    hs_lat = None
+    if a.hs_forcing:                                     # latitude of the quadrature points [nEl, mp12]
+        hs_lat = eng.tensor(np.ascontiguousarray(np.arcsin(xq[:, 2] / np.linalg.norm(xq, axis=1))[np.asarray(eng.mesh.indsq)]))
+    eu = Euler(eng, a.dt, um.levels(a.nk, xq), xq, newton_maxit=a.newton_maxit, hs_forcing=a.hs_forcing, hs_lat=hs_lat)
+    head = "UMJS14 baroclinic wave, p = %d, %d x %d x 6 sphere (%d elements), %d levels, dt = %g s, Euler.%s%s; %s" \
+        % (a.pn, a.ne, a.ne, eng.nEl, a.nk, a.dt, a.integrator, ", Held-Suarez forcing" if a.hs_forcing else "", torch.cuda.get_device_name(0))
     print(head, flush=True)
     state = eu.load(a.start_step, a.outdir) if a.start_step else eu.initial_state(um.VP if a.vp is None else a.vp)
     torch.cuda.synchronize()
@@ -83,7 +90,7 @@ def work(a):
             torch.cuda.synchronize(); sink.append((time.perf_counter() - t) * 1e3)
             return out
         setattr(eu, name, wrapped)
-    timed("strang_ec", ms); timed("dump", dump_ms)
+    timed(a.integrator, ms); timed("dump", dump_ms)
 
     def on_step(step, values):
         h = eu.vert.history
@@ -93,9 +100,9 @@ def work(a):
         if len(h) >= a.newton_maxit:
             print("  no convergence in %d iterations; norms per iteration:" % len(h))
             for i, n in enumerate(h):
-                print("    %2d  exner %.3e  w %.3e  rho %.3e  eta %.3e" % (i + 1, n["exner"], n["w"], n["rho"], n["eta"]))
+                print("    %2d  %s" % (i + 1, "  ".join("%s %.3e" % kv for kv in n.items())))
         print("  " + "\t".join("%s %.16g" % kv for kv in zip(FIELDS, values)), flush=True)
-    state = eu.run(state, a.nsteps, dump_every=a.dump_every, outdir=a.outdir, start_step=a.start_step, on_step=on_step)
+    state = eu.run(state, a.nsteps, dump_every=a.dump_every, outdir=a.outdir, start_step=a.start_step, on_step=on_step, integrator=a.integrator)
     finite = all(bool(torch.isfinite(x).all()) for x in state)
 
     out = [head, ""]
