@@ -19,8 +19,7 @@ namespace {
 
 template <class T>
 int upload(T** dst, const T* src, size_t count, mimsem_ctx* c) {
-    MIMSEM_HIP_TRY(hipMalloc((void**)dst, std::max<size_t>(count, 1)*sizeof(T)));
-    c->bytes += (long long)(count*sizeof(T));
+    if (int rc = c->alloc((void**)dst, count*sizeof(T))) return rc;
     if (count) MIMSEM_HIP_TRY(hipMemcpy(*dst, src, count*sizeof(T), hipMemcpyHostToDevice));
     return MIMSEM_OK;
 }
@@ -688,68 +687,42 @@ int op_spaces(int op, int* in, int* cf, int* out) {
 
 }  // namespace
 
-// Workspaces only ever grow, and an outgrown buffer is RETIRED, not freed: a hipGraph captured earlier (Krylov / Richardson steps)
-// has the old address baked into its kernel arguments and must keep working on it; retired buffers go with the context.
+// The context's device memory (ctx.hpp: one owner).  The count is the bytes asked for; an empty table still gets an address.
+int mimsem_ctx::alloc(void** p, size_t nbytes, Mem kind) {
+    void* q = nullptr;
+    const size_t sz = std::max<size_t>(nbytes, 1);
+    if (kind == Mem::Plain) MIMSEM_HIP_TRY(hipMalloc(&q, sz));
+    else MIMSEM_HIP_TRY(hipExtMallocWithFlags(&q, sz, kind == Mem::FineGrained ? hipDeviceMallocFinegrained : hipDeviceMallocUncached));
+    adopt(q, nbytes);
+    *p = q;
+    return MIMSEM_OK;
+}
+void mimsem_ctx::release(void* p) {
+    const auto it = std::find_if(owned.begin(), owned.end(), [p](const std::pair<void*, size_t>& o) { return o.first == p; });
+    if (it == owned.end()) return;
+    bytes -= (long long)it->second;
+    owned.erase(it);
+    (void)hipFree(p);
+}
 bool mimsem_ctx::is_capturing() const {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &st) != hipSuccess) return false;
     return st != hipStreamCaptureStatusNone;
 }
-int mimsem_ctx::ensure_ye(long long doubles) {
-    if (doubles <= ye_doubles) return MIMSEM_OK;
-    if (is_capturing()) return MIMSEM_ERR_STATE;
-    if (d_ye) { retired.push_back(d_ye); d_ye = nullptr; ye_doubles = 0; }
-    MIMSEM_HIP_TRY(hipMalloc((void**)&d_ye, (size_t)doubles*sizeof(double)));
-    ye_doubles = doubles; bytes += doubles*8;
-    return MIMSEM_OK;
-}
-int mimsem_ctx::ensure_cheb(long long doubles) {
-    if (doubles <= cheb_doubles) return MIMSEM_OK;
-    if (is_capturing()) return MIMSEM_ERR_STATE;
-    if (d_cheb) { retired.push_back(d_cheb); d_cheb = nullptr; cheb_doubles = 0; }
-    MIMSEM_HIP_TRY(hipMalloc((void**)&d_cheb, (size_t)doubles*sizeof(double)));
-    cheb_doubles = doubles; bytes += doubles*8;
-    return MIMSEM_OK;
-}
-int mimsem_ctx::ensure_wpart(long long doubles) {
-    if (doubles <= wpart_doubles) return MIMSEM_OK;
-    if (is_capturing()) return MIMSEM_ERR_STATE;
-    if (d_wpart) { retired.push_back(d_wpart); d_wpart = nullptr; wpart_doubles = 0; }
-    // UNCACHED device memory: a plain store is acknowledged by the memory side, not by the storing XCD's L2 (MIMSEM_WPART_MEM=finegrained |
-    // plain select other kinds for experiments; `plain` is NOT coherent across XCDs inside one launch)
-    if (w_partmem == 2) MIMSEM_HIP_TRY(hipMalloc((void**)&d_wpart, (size_t)doubles*sizeof(double)));
-    else MIMSEM_HIP_TRY(hipExtMallocWithFlags((void**)&d_wpart, (size_t)doubles*sizeof(double),
-                                              w_partmem == 1 ? hipDeviceMallocFinegrained : hipDeviceMallocUncached));
-    wpart_doubles = doubles; bytes += doubles*8;
-    return MIMSEM_OK;
-}
-int mimsem_ctx::ensure_wsplit(long long doubles) {
-    if (doubles <= wsplit_doubles) return MIMSEM_OK;
-    if (is_capturing() || split.pending) return MIMSEM_ERR_STATE;
-    if (d_wsplit) { retired.push_back(d_wsplit); d_wsplit = nullptr; wsplit_doubles = 0; }
-    MIMSEM_HIP_TRY(hipMalloc((void**)&d_wsplit, (size_t)doubles*sizeof(double)));
-    wsplit_doubles = doubles; bytes += doubles*8;
+int mimsem_ctx::grow(double*& buf, long long& have, long long doubles, Mem kind) {
+    if (doubles <= have) return MIMSEM_OK;
+    if (is_capturing()) return MIMSEM_ERR_STATE;          // growing = hipMalloc, illegal on a capturing stream: warm up outside the capture
+    if (int rc = alloc((void**)&buf, (size_t)doubles*sizeof(double), kind)) return rc;      // (on failure buf still names the old, smaller buffer)
+    have = doubles;                                       // (the old buffer is retired: `owned` keeps it for the recordings that hold it)
     return MIMSEM_OK;
 }
 int mimsem_ctx::ensure_kry(long long doubles) {
     if (doubles <= kry_doubles) return MIMSEM_OK;
-    if (is_capturing()) return MIMSEM_ERR_STATE;
-    if (d_kry) { retired.push_back(d_kry); d_kry = nullptr; kry_doubles = 0; }
-    MIMSEM_HIP_TRY(hipMalloc((void**)&d_kry, (size_t)doubles*sizeof(double)));
-    kry_doubles = doubles; bytes += doubles*8;
-    if (!d_rdcnt) {                                                  // arrival counters of the one-launch rowdot: zeroed once, every call leaves them zero
-        MIMSEM_HIP_TRY(hipMalloc((void**)&d_rdcnt, MIMSEM_RD_COUNTERS*sizeof(unsigned)));
+    if (int rc = grow(d_kry, kry_doubles, doubles)) return rc;
+    if (!d_rdcnt) {                                                 // arrival counters of the one-launch rowdot: zeroed once, every call leaves them zero
+        if (int rc = alloc((void**)&d_rdcnt, MIMSEM_RD_COUNTERS*sizeof(unsigned))) return rc;
         MIMSEM_HIP_TRY(hipMemsetAsync(d_rdcnt, 0, MIMSEM_RD_COUNTERS*sizeof(unsigned), stream));
     }
-    return MIMSEM_OK;
-}
-int mimsem_ctx::ensure_col(long long doubles) {
-    if (doubles <= col_doubles) return MIMSEM_OK;
-    // retired like d_ye / d_kry: a graph captured around a column call (Engine.capture accepts any fn) keeps the old address
-    if (is_capturing()) return MIMSEM_ERR_STATE;          // growing = hipMalloc, illegal on a capturing stream: warm up outside the capture
-    if (d_col) { retired.push_back(d_col); d_col = nullptr; col_doubles = 0; }
-    MIMSEM_HIP_TRY(hipMalloc((void**)&d_col, (size_t)doubles*sizeof(double)));
-    col_doubles = doubles; bytes += doubles*8;
     return MIMSEM_OK;
 }
 
@@ -758,8 +731,29 @@ hipEvent_t mimsem_ctx::next_event() {
     return ev_pool[ev_used++];
 }
 
+// packed metric of the wave kernel: {gaa, gab, gbb, 1/det} = Q/det J^T J per quadrature point (16-byte loads) and the
+// rotational factor (-J00 J11 + J01 J10) Q/det of RotMat, in wave-group order
+static void pack_wave_metric(const mimsem_ctx* c, const WavePlan& P, int lpe, std::vector<double>& G, std::vector<double>& Rv) {
+    const ElemSizes& es = c->es;
+    G.assign((size_t)P.ngroups*64*4, 0.0); Rv.assign((size_t)P.ngroups*64, 0.0);
+    const int gsz = 64/lpe;
+    for (int g = 0; g < P.ngroups; g++)
+        for (int l = 0; l < 64; l++) {
+            const int e = P.perm[(size_t)g*gsz + l/lpe], q = l%lpe;
+            if (e < 0 || q >= es.mp12) continue;                 // padding element / lane beyond the point grid: zeros
+            const double* Jq = c->h_J.data() + ((size_t)e*es.mp12 + q)*4;
+            const double det = c->h_det[(size_t)e*es.mp12 + q];
+            const double Q = c->tab.quad.w[q%es.mp1]*c->tab.quad.w[q/es.mp1];
+            double* o = &G[((size_t)g*64 + l)*4];
+            o[0] = (Jq[0]*Jq[0] + Jq[2]*Jq[2])*Q/det; o[1] = (Jq[0]*Jq[1] + Jq[2]*Jq[3])*Q/det;
+            o[2] = (Jq[1]*Jq[1] + Jq[3]*Jq[3])*Q/det; o[3] = 1.0/det;
+            Rv[(size_t)g*64 + l] = (-Jq[0]*Jq[3] + Jq[1]*Jq[2])*Q/det;
+        }
+}
+
 // (re)build the wave-level plan of a context from its host copies of the mesh; `marked` [n1] flags the 1-form slots that take part
-// in a halo exchange (null: none).  Old device tables are retired, not freed (a captured graph may still hold them).
+// in a halo exchange (null: none).  The context takes the new plan only when all of it is on the device (on failure it keeps the one it had);
+// the tables of the plan it replaces are retired, not freed (a captured graph may still hold them).
 static int setup_wave(mimsem_ctx* c, const char* marked) {
     const ElemSizes& es = c->es;
     WavePlan P;
@@ -786,64 +780,42 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
     // per batch of two levels for every call (the A/B partner; single-level calls always run it)
     const bool own4 = !getenv("MIMSEM_WAVE_OWN");
     const bool own = want_own && build_wave_own(es.n, c->n1, c->nEl, es.n1e, 64/lpe, c->h_i1x.data(), c->h_i1y.data(), P, W) == MIMSEM_OK;
-    void* old[] = {c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin,
-                   c->d_woplan, c->d_wgh, c->d_wgx, c->d_wgh4};
-    c->d_woplan = nullptr; c->d_wgh = nullptr; c->d_wgx = nullptr; c->d_wgh4 = nullptr; c->w_own = false;
-    c->d_wtfin = nullptr; c->w_ntiles = 0;
-    for (void* p : old) if (p) c->retired.push_back(p);
-    c->d_wlane = nullptr; c->d_wplan = nullptr; c->d_wprec = nullptr; c->d_wnode = nullptr; c->d_wsing = nullptr; c->d_wG = nullptr; c->d_wR = nullptr;
-    c->d_wfin = nullptr; c->d_wsslot = nullptr; c->d_wcnt = nullptr;
-    c->wave1 = false; c->w_fin = false;
-    if ((rc = upload(&c->d_wlane, P.lane.data(), P.lane.size(), c))) return rc;
-    if ((rc = upload(&c->d_wplan, P.plan.data(), P.plan.size(), c))) return rc;
-    {
+    WaveTables t;
+    const size_t mark = c->owned.size();
+    rc = [&]() -> int {
+        int rc;
+        if ((rc = upload(&t.lane, P.lane.data(), P.lane.size(), c))) return rc;
+        if ((rc = upload(&t.plan, P.plan.data(), P.plan.size(), c))) return rc;
         std::vector<int4> rec(P.pslot.size());
         for (size_t i = 0; i < rec.size(); i++) rec[i] = int4{P.pslot[i], P.ppart[2*i], P.ppart[2*i + 1], 0};
-        if ((rc = upload(&c->d_wprec, rec.data(), rec.size(), c))) return rc;
-    }
-    if ((rc = upload(&c->d_wnode, P.node.data(), P.node.size(), c))) return rc;
-    if (own) {
-        if ((rc = upload(&c->d_woplan, W.plan.data(), W.plan.size(), c))) return rc;
-        if ((rc = upload(&c->d_wgh, W.gh.data(), W.gh.size(), c))) return rc;
-        if ((rc = upload(&c->d_wgx, W.gx.data(), W.gx.size(), c))) return rc;
-        if (own4 && (rc = upload(&c->d_wgh4, W.gh4.data(), W.gh4.size(), c))) return rc;
-        c->w_own = true;
-    }
-    if (P.nsing && (rc = upload(&c->d_wsing, P.sing.data(), P.sing.size(), c))) return rc;
-    if ((rc = upload(&c->d_wfin, P.fin.data(), P.fin.size(), c))) return rc;
-    if ((rc = upload(&c->d_wsslot, P.sslot.data(), P.sslot.size(), c))) return rc;
-    if (P.ntiles > 0) { if ((rc = upload(&c->d_wtfin, P.tfin.data(), P.tfin.size(), c))) return rc; c->w_ntiles = P.ntiles; c->w_ninner = P.ninner; }
-    {   // arrival counters of the finishing phase: one per (side, work item of a group), zero between launches
+        if ((rc = upload(&t.prec, rec.data(), rec.size(), c))) return rc;
+        if ((rc = upload(&t.node, P.node.data(), P.node.size(), c))) return rc;
+        if (own) {
+            if ((rc = upload(&t.oplan, W.plan.data(), W.plan.size(), c))) return rc;
+            if ((rc = upload(&t.gh, W.gh.data(), W.gh.size(), c))) return rc;
+            if ((rc = upload(&t.gx, W.gx.data(), W.gx.size(), c))) return rc;
+            if (own4 && (rc = upload(&t.gh4, W.gh4.data(), W.gh4.size(), c))) return rc;
+        }
+        if (P.nsing && (rc = upload(&t.sing, P.sing.data(), P.sing.size(), c))) return rc;
+        if ((rc = upload(&t.fin, P.fin.data(), P.fin.size(), c))) return rc;
+        if ((rc = upload(&t.sslot, P.sslot.data(), P.sslot.size(), c))) return rc;
+        if (P.ntiles > 0 && (rc = upload(&t.tfin, P.tfin.data(), P.tfin.size(), c))) return rc;
+        // arrival counters of the finishing phase: one per (side, work item of a group), zero between launches
         const size_t n = (size_t)std::max(P.nsides, 1)*(size_t)std::max(c->nk, 1);
-        MIMSEM_HIP_TRY(hipMalloc((void**)&c->d_wcnt, n*sizeof(int)));
-        MIMSEM_HIP_TRY(hipMemset(c->d_wcnt, 0, n*sizeof(int)));
-        c->bytes += (long long)(n*sizeof(int));
-    }
-    // packed metric of the wave kernel: {gaa, gab, gbb, 1/det} = Q/det J^T J per quadrature point (16-byte loads) and the
-    // rotational factor (-J00 J11 + J01 J10) Q/det of RotMat, in wave-group order
-    {
-        std::vector<double> G((size_t)P.ngroups*64*4, 0.0), Rv((size_t)P.ngroups*64, 0.0);
-        const int gsz = 64/lpe;
-        for (int g = 0; g < P.ngroups; g++)
-            for (int l = 0; l < 64; l++) {
-                const int e = P.perm[(size_t)g*gsz + l/lpe], q = l%lpe;
-                if (e < 0 || q >= es.mp12) continue;                 // padding element / lane beyond the point grid: zeros
-                const double* Jq = c->h_J.data() + ((size_t)e*es.mp12 + q)*4;
-                const double det = c->h_det[(size_t)e*es.mp12 + q];
-                const double Q = c->tab.quad.w[q%es.mp1]*c->tab.quad.w[q/es.mp1];
-                double* o = &G[((size_t)g*64 + l)*4];
-                o[0] = (Jq[0]*Jq[0] + Jq[2]*Jq[2])*Q/det; o[1] = (Jq[0]*Jq[1] + Jq[2]*Jq[3])*Q/det;
-                o[2] = (Jq[1]*Jq[1] + Jq[3]*Jq[3])*Q/det; o[3] = 1.0/det;
-                Rv[(size_t)g*64 + l] = (-Jq[0]*Jq[3] + Jq[1]*Jq[2])*Q/det;
-            }
-        if ((rc = upload(&c->d_wG, G.data(), G.size(), c))) return rc;
-        if ((rc = upload(&c->d_wR, Rv.data(), Rv.size(), c))) return rc;
-    }
-    c->w_ndirect = P.ndirect; c->w_ngroups = P.ngroups; c->w_nsing = P.nsing; c->w_nps = P.nps; c->w_npart = P.npart;
-    c->w_npwritten = P.npwritten; c->w_nsides = P.nsides;
+        if ((rc = c->alloc((void**)&t.cnt, n*sizeof(int)))) return rc;
+        MIMSEM_HIP_TRY(hipMemset(t.cnt, 0, n*sizeof(int)));
+        std::vector<double> G, Rv;
+        pack_wave_metric(c, P, lpe, G, Rv);
+        if ((rc = upload(&t.G, G.data(), G.size(), c))) return rc;
+        return upload(&t.R, Rv.data(), Rv.size(), c);
+    }();
+    if (rc) { while (c->owned.size() > mark) c->release(c->owned.back().first); return rc; }      // (nothing has seen these tables)
+    t.on = true; t.own = own; t.can_fin = P.fin_ok && want_fin; t.split = marked != nullptr;
+    t.ndirect = P.ndirect; t.ngroups = P.ngroups; t.nsing = P.nsing; t.nps = P.nps; t.npart = P.npart; t.npwritten = P.npwritten; t.nsides = P.nsides;
+    if (P.ntiles > 0) { t.ntiles = P.ntiles; t.ninner = P.ninner; }
+    t.nbgroups = P.nbgroups; t.nbrec = P.nbrec;
+    c->wv = t;
     if (const char* kind = exp_env("MIMSEM_WPART_MEM")) c->w_partmem = !strcmp(kind, "plain") ? 2 : (!strcmp(kind, "finegrained") ? 1 : 0);
-    c->w_fin = P.fin_ok && want_fin;
-    c->w_nbgroups = P.nbgroups; c->w_nbrec = P.nbrec; c->w_split = marked != nullptr; c->wave1 = true;
     if (const char* ev = exp_env("MIMSEM_WAVE_ORDER")) c->wave_order = atoi(ev);
     if (const char* ev = exp_env("MIMSEM_WAVE_LCH")) c->wave_lch = atoi(ev);
     if (const char* ev = exp_env("MIMSEM_WAVE_CPP")) c->wave_cpp = atoi(ev);
@@ -851,7 +823,7 @@ static int setup_wave(mimsem_ctx* c, const char* marked) {
     if (getenv("MIMSEM_VERBOSE"))
         fprintf(stderr, "[mimsem] wave plan: %d groups of %d elements (%d on the halo boundary), %d perimeter slots (%d partials in %d sides) of %d; "
                         "in-kernel finishing %s; tiles %d (%d inner slots finished in LDS, widest LDS row %d doubles)\n", P.ngroups, 64/lpe, P.nbgroups, P.nps,
-                P.npwritten, P.nsides, c->n1, c->w_fin ? "on" : "off", P.ntiles, P.ninner, P.tpmax);
+                P.npwritten, P.nsides, c->n1, c->wv.can_fin ? "on" : "off", P.ntiles, P.ninner, P.tpmax);
     if (getenv("MIMSEM_VERBOSE") && own)
         fprintf(stderr, "[mimsem] owner-computes form: %d pairs, %d ghost sides (at most %d per group; %d groups with 4 of both kinds), "
                         "at most %d gathered DoFs per group; side mixes (x-normal + y-normal): %d groups 2 + 2, %d groups 4 + 0, %d groups 0 + 4, "
@@ -1063,12 +1035,8 @@ int mimsem_ctx_create(const mimsem_mesh_desc* d, int device, mimsem_ctx** out) {
     }
     {
         const size_t cnt = (size_t)d->nk*d->nEl*es.mp12;
-        hipError_t he = hipMalloc((void**)&c->d_th, std::max<size_t>(cnt, 1)*sizeof(double));
-        if (he == hipSuccess) he = hipMalloc((void**)&c->d_tI, std::max<size_t>(cnt, 1)*sizeof(double));
-        const size_t cntp = 2*(size_t)(d->nk/2 + 1)*d->nEl*es.mp12*2;
-        if (he == hipSuccess && es.n <= 4) he = hipMalloc((void**)&c->d_tIp, std::max<size_t>(cntp, 1)*sizeof(double));
-        if (he != hipSuccess) return fail(mimsem::hip_fail(he, "hipMalloc(thickness)"));
-        c->bytes += 2*(long long)cnt*8 + (es.n <= 4 ? (long long)cntp*8 : 0);
+        if ((rc = c->alloc((void**)&c->d_th, cnt*sizeof(double))) || (rc = c->alloc((void**)&c->d_tI, cnt*sizeof(double)))) return fail(rc);
+        if (es.n <= 4 && (rc = c->alloc((void**)&c->d_tIp, 2*(size_t)(d->nk/2 + 1)*d->nEl*es.mp12*2*sizeof(double)))) return fail(rc);
     }
     if ((rc = mimsem_ctx_set_levels(c, d->thick, d->thickInv))) return fail(rc);
     // two element-local buffers + one packed [1-form | 2-form] row per level: the largest request of any entry point at nlev <= nk
@@ -1083,11 +1051,7 @@ void mimsem_ctx_destroy(mimsem_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     orphan_graphs(c);
-    void* ptrs[] = {c->d_xn, c->d_E, c->d_w, c->d_U, c->d_V, c->d_W, c->d_P, c->d_J, c->d_det, c->d_th, c->d_tI, c->d_tIp, c->d_tIn,
-                    c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_iq, c->d_fperm, c->d_flid, c->d_fslot, c->d_fcnt, c->d_pslot, c->d_ppart, c->d_wlane, c->d_wplan, c->d_wprec, c->d_wnode, c->d_wsing, c->d_wG, c->d_wR, c->d_wfin, c->d_wsslot, c->d_wcnt, c->d_wtfin, c->d_woplan, c->d_wgh, c->d_wgx, c->d_wgh4, c->d_wpart, c->d_wsplit, c->d_colstat, c->d_forceflag, c->d_rdcnt, c->d_cheb, c->d_colratio, c->d_g1, c->d_bplan, c->d_g0, c->d_ye, c->d_col, c->d_lu, c->d_kry,
-                    c->d_d0, c->d_d1x, c->d_d1y, c->d_sh0, c->d_sh1, c->d_own[1], c->d_own[2], c->d_pcw};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (void* p : c->retired) (void)hipFree(p);
+    for (const auto& o : c->owned) (void)hipFree(o.first);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     if (c->cap_stream) (void)hipStreamDestroy(c->cap_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1175,11 +1139,11 @@ int mimsem_op_level_chunk(const mimsem_ctx* c, int nlev) { return (c && nlev > 0
 int mimsem_op_wave_stats(const mimsem_ctx* c, int nlev, int out[5]) {
     if (!c || !out || nlev < 1) return MIMSEM_ERR_ARG;
     for (int i = 0; i < 5; i++) out[i] = 0;
-    if (!c->wave1) return 0;
-    out[0] = c->w_ngroups; out[1] = c->w_ndirect; out[2] = c->w_npwritten; out[3] = c->w_nps;
-    if (c->w_own) { out[1] = c->n1; out[2] = 0; out[3] = 0; }     // the headline operator's form: every slot written once, no partial sums
-    if (c->w_own && c->es.n == 3 && c->w_ntiles == 0 && !c->d_tIn) out[4] = wave_level_parts(c, nlev, c->w_ngroups).longest;     // the longest item's levels
-    else { const int lch = wave_level_chunk(c, nlev); out[4] = lch*wave_chunks_per_item(c, nlev, lch, c->w_ngroups); }
+    if (!c->wv.on) return 0;
+    out[0] = c->wv.ngroups; out[1] = c->wv.ndirect; out[2] = c->wv.npwritten; out[3] = c->wv.nps;
+    if (c->wv.own) { out[1] = c->n1; out[2] = 0; out[3] = 0; }     // the headline operator's form: every slot written once, no partial sums
+    if (c->wv.own && c->es.n == 3 && c->wv.ntiles == 0 && !c->d_tIn) out[4] = wave_level_parts(c, nlev, c->wv.ngroups).longest;     // the longest item's levels
+    else { const int lch = wave_level_chunk(c, nlev); out[4] = lch*wave_chunks_per_item(c, nlev, lch, c->wv.ngroups); }
     return 1;
 }
 
@@ -1219,7 +1183,7 @@ int mimsem_ctx_set_levels(mimsem_ctx* c, const double* thick, const double* thic
         // the same table per NODE (experiment, MIMSEM_WAVE_TNODE=1): the reference's thickInv lives on the nodes (eul/Geom.cpp:143-146, :761) and
         // the ABI takes it gathered per element: 16 values per element at p = 3 of which 9 are distinct per element on average.  Only when
         // every element holds the same bits at a shared node (and quadrature points are the nodes: mp12 == n0e)
-        if (c->d_tIn) { (void)hipFree(c->d_tIn); c->d_tIn = nullptr; }
+        if (c->d_tIn) { c->release(c->d_tIn); c->d_tIn = nullptr; }
         if (exp_env("MIMSEM_WAVE_TNODE") && atoi(exp_env("MIMSEM_WAVE_TNODE")) == 1 && c->es.mp12 == c->es.n0e && !c->h_i0.empty() && c->n0 > 0) {
             const size_t n0 = (size_t)c->n0;
             std::vector<double> nod((size_t)c->nk*n0, 1.0), tn(2*np*n0*2, 1.0);
@@ -1241,7 +1205,7 @@ int mimsem_ctx_set_levels(mimsem_ctx* c, const double* thick, const double* thic
                 for (size_t nd = 0; nd < n0; nd++) { o[2*nd] = nod[L0*n0 + nd]; o[2*nd + 1] = nod[L1*n0 + nd]; }
             }
             if (same) {
-                MIMSEM_HIP_TRY(hipMalloc((void**)&c->d_tIn, tn.size()*sizeof(double)));
+                if (int rc = c->alloc((void**)&c->d_tIn, tn.size()*sizeof(double))) return rc;
                 MIMSEM_HIP_TRY(hipMemcpy(c->d_tIn, tn.data(), tn.size()*sizeof(double), hipMemcpyHostToDevice));
             }
         }
@@ -1298,17 +1262,23 @@ int mimsem_memset(mimsem_ctx* c, void* dev, int byte, long long bytes) {
 }
 
 // ---- horizontal operators --------------------------------------------------------------------
-static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
-                         const double* f, long long fs, const double* f2, long long f2s, double param,
-                         const double* x, long long xs, double* y, long long ys, double alpha,
-                         const GatherEpilogue* epi = nullptr, const double* blocks = nullptr, int part = 0, int lev_step = 1);
+// one operator apply as the entry points state it: the arguments of mimsem_op_apply, then what only some entries have
+struct ApplyCall {
+    int op, lev0, nlev; double scale; unsigned flags;
+    const double* f; long long fs; const double* x; long long xs; double* y; long long ys; double alpha;
+    const double* f2 = nullptr; long long f2s = 0; double param = 0.0;      // second coefficient field and tau (mimsem_op_apply_up)
+    const GatherEpilogue* epi = nullptr; const double* blocks = nullptr;   // the Richardson / Chebyshev sweeps
+    int part = 0;                                                          // mimsem_op_apply_part
+    int lev_step = 1;                                                      // mimsem_op_apply_levels
+};
+static int op_apply_core(mimsem_ctx* c, const ApplyCall& k);
 static bool is_up_op(int op);
 
 int mimsem_op_apply(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
                     const double* f, long long fs, const double* x, long long xs,
                     double* y, long long ys, double alpha) {
     if (is_up_op(op)) return MIMSEM_ERR_ARG;   // need mimsem_op_apply_up
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, y, ys, alpha);
+    return op_apply_core(c, {op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha});
 }
 
 // HorizSolve::diagVertVort (eul/HorizSolve.cpp:842-850) assembles M2 and F at level 0 for EVERY interface: geom_lev_step 0 evaluates every
@@ -1319,7 +1289,9 @@ int mimsem_op_apply_levels(mimsem_ctx* c, int op, int geom_lev0, int geom_lev_st
     if (geom_lev_step == 1) return mimsem_op_apply(c, op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha);
     if (geom_lev_step != 0) return MIMSEM_ERR_ARG;
     if (op != MIMSEM_OP_WMAT && op != MIMSEM_OP_UHMAT) return MIMSEM_ERR_UNSUPPORTED;
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, y, ys, alpha, nullptr, nullptr, 0, 0);
+    ApplyCall k{op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha};
+    k.lev_step = 0;
+    return op_apply_core(c, k);
 }
 
 static bool is_up_op(int op) {
@@ -1329,8 +1301,8 @@ static bool is_up_op(int op) {
 int mimsem_ctx_set_halo_slots(mimsem_ctx* c, int form, const int* slots, int n) {
     if (!c || form != 1 || n < 0 || (n && !slots)) return MIMSEM_ERR_ARG;
     if (c->is_capturing() || c->split.pending) return MIMSEM_ERR_STATE;      // (a pending BOUNDARY part belongs to the plan in force)
-    if (c->d_pcw) { c->retired.push_back(c->d_pcw); c->d_pcw = nullptr; }      // (the element-block weights count halo edges twice: remade on next use)
-    if (!c->wave1 && c->h_i1x.empty()) {      // two-pass form: nothing to reorder (the split degenerates, see mimsem_op_apply_part); the marks are kept all the same
+    c->d_pcw = nullptr;      // (retired.  The element-block weights count halo edges twice: remade on next use)
+    if (!c->wv.on && c->h_i1x.empty()) {      // two-pass form: nothing to reorder (the split degenerates, see mimsem_op_apply_part); the marks are kept all the same
         c->h_halo1.assign(c->n1, 0);
         for (int i = 0; i < n; i++) { if (slots[i] < 0 || slots[i] >= c->n1) return MIMSEM_ERR_ARG; c->h_halo1[slots[i]] = 1; }
         return MIMSEM_OK;
@@ -1347,7 +1319,9 @@ int mimsem_op_apply_part(mimsem_ctx* c, int op, int geom_lev0, int nlev, double 
                          const double* f, long long fs, const double* x, long long xs,
                          double* y, long long ys, double alpha, int part) {
     if (is_up_op(op) || part < MIMSEM_PART_ALL || part > MIMSEM_PART_INTERIOR) return MIMSEM_ERR_ARG;
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, y, ys, alpha, nullptr, nullptr, part);
+    ApplyCall k{op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha};
+    k.part = part;
+    return op_apply_core(c, k);
 }
 
 int mimsem_op_apply_part_reset(mimsem_ctx* c) {
@@ -1361,201 +1335,218 @@ int mimsem_op_apply_up(mimsem_ctx* c, int op, int geom_lev0, int nlev, double sc
                        const double* x, long long xs, double* y, long long ys, double alpha) {
     if (!is_up_op(op) || !u) return MIMSEM_ERR_ARG;
     if ((flags & MIMSEM_FLAG_TRANSPOSE) && op != MIMSEM_OP_UMAT_UP && op != MIMSEM_OP_UHMAT_UP) return MIMSEM_ERR_ARG;
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, u, us, tau, x, xs, y, ys, alpha);
+    return op_apply_core(c, {op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha, u, us, tau});
 }
 
 }  // extern "C"
 
-static int op_apply_core(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
-                         const double* f, long long fs, const double* f2, long long f2s, double param,
-                         const double* x, long long xs, double* y, long long ys, double alpha,
-                         const GatherEpilogue* epi, const double* blocks, int part, int lev_step) {
-    if (!c || nlev < 0) return MIMSEM_ERR_ARG;
+// The arguments every element and wave kernel shares; a route then sets only what its kernel reads -- everything else is zero or null.
+static ElemArgs elem_args(const mimsem_ctx* c, int lev0, int nlev, unsigned flags, double scale, double alpha) {
+    ElemArgs a{};
+    a.nEl = c->nEl; a.nlev = nlev; a.lev0 = lev0; a.total = c->nEl*nlev;
+    a.flags = flags; a.scale = scale; a.alpha = alpha;
+    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.E = c->d_E; a.w = c->d_w; a.xn = c->d_xn;
+    a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*c->es.mp12*2;
+    a.i0 = c->d_i0; a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2; a.iq = c->d_iq;
+    a.lch = level_chunk(c, nlev);      // (swz stays 0: the natural order already keeps all level-chunks of an element on one XCD, profiles/r01_swizzle_ab.txt)
+    return a;
+}
+// the edge basis and the GLL weights by value (the wave-level kernels, orders <= 4)
+static void basis_by_value(const mimsem_ctx* c, ElemArgs& a) {
+    for (size_t k = 0; k < 20; k++) a.Etab[k] = k < c->tab.E.size() ? c->tab.E[k] : 0.0;
+    for (size_t k = 0; k < 5; k++) a.Wq[k] = k < c->tab.quad.w.size() ? c->tab.quad.w[k] : 0.0;
+}
+// the wave kernels address their rows with 32-bit byte offsets: vectors / metric beyond 4 GB per level stay on the two-pass form
+// (the 2-form-valued kernel touches no node table: `nodes` false leaves n0 out)
+static bool fits_32bit(const mimsem_ctx* c, bool nodes) {
+    const long long lim = 1LL << 28;
+    return (long long)c->n1 < lim && (!nodes || (long long)c->n0 < lim) && (long long)c->n2 < lim && (long long)c->nEl*c->es.mp12 < lim;
+}
+
+#ifdef MIMSEM_STAMPS      // diagnostic build: per-phase s_memtime stamps of every work item of a wave launch, summarised on stderr
+static long long* g_stamps = nullptr; static size_t g_stamp_items = 0;
+static size_t stamps_begin(mimsem_ctx* c, int nlev, ElemArgs& a) {
+    const size_t items = (size_t)c->wv.ngroups*std::max((nlev + a.lch - 1)/a.lch, a.wnp);     // (the kernel stamps item < wgroups x parts: never fewer slots than that)
+    if (!exp_env("MIMSEM_WAVE_STAMPS")) return items;
+    if (items > g_stamp_items) { if (g_stamps) (void)hipFree(g_stamps); (void)hipMalloc((void**)&g_stamps, items*16*8); g_stamp_items = items; }
+    (void)hipMemsetAsync(g_stamps, 0, items*16*8, c->stream);
+    a.wstamps = g_stamps;
+    return items;
+}
+static void stamps_report(mimsem_ctx* c, const ElemArgs& a, size_t items) {
+    if (!a.wstamps) return;
+    (void)hipStreamSynchronize(c->stream);
+    std::vector<long long> h(items*16);
+    (void)hipMemcpy(h.data(), g_stamps, items*16*8, hipMemcpyDeviceToHost);
+    long long t0 = h[0], t1 = 0;
+    for (size_t i = 0; i < items; i++) { t0 = std::min(t0, h[i*16]); t1 = std::max(t1, h[i*16 + 15]); }
+    fprintf(stderr, "[stamps] items %zu lch %d  first entry -> last done: %lld ticks\n", items, a.lch, t1 - t0);
+    const char* names[16] = {"entry(rel. first)", "barrier", "tables requested", "level loads issued", "batch0", "batch1", "batch2", "batch3",
+                             "b4", "b5", "b6", "chunks done", "fin: stores acked", "fin: arrival counted", "fin: sides finished", "stores acked"};
+    for (int k = 0; k < 16; k++) {
+        std::vector<long long> v;
+        for (size_t i = 0; i < items; i++) if (h[i*16 + k]) v.push_back(k == 0 ? h[i*16] - t0 : h[i*16 + k] - h[i*16]);
+        if (v.empty()) continue;
+        std::sort(v.begin(), v.end());
+        fprintf(stderr, "[stamps] %-20s min %8lld  p10 %8lld  median %8lld  p90 %8lld  max %8lld   (ticks since the wave's entry)\n", names[k],
+                v.front(), v[v.size()/10], v[v.size()/2], v[v.size()*9/10], v.back());
+    }
+}
+#endif
+
+// ---- the routes of an apply: each gets the shared arguments `a` of the router and fills in what its kernels read ----
+
+// p = 3: the wave-level kernel of the 2-form-valued operators (no scatter: one launch)
+static int apply_wave2(mimsem_ctx* c, const ApplyCall& k, ElemArgs& a) {
+    if (int rc = c->ensure_ye(64)) return rc;
+    a.wlane = c->wv.lane; a.wgroups = c->wv.ngroups; a.wG = c->wv.G; a.wR = c->wv.R;
+    a.lch = wave_level_chunk(c, k.nlev); a.wcpp = wave_chunks_per_item(c, k.nlev, a.lch, c->wv.ngroups); a.swz = c->wave_order;
+    a.accum = (k.flags & MIMSEM_FLAG_ACCUM) ? 1 : 0; a.y = c->d_ye;       // a.y: the dump for idle lanes
+    basis_by_value(c, a);
+    return launch_apply_wave2(c, k.op, a);
+}
+
+// Richardson sweep: element pass into the workspace, then the gather with the update epilogue (y is the iterate);
+// with `blocks` the element-block preconditioner runs in between on the second half of the workspace
+static int apply_epilogue(mimsem_ctx* c, const ApplyCall& k, ElemArgs& a, int outsp) {
+    const long long per = (long long)c->nEl*(outsp == 1 ? 2*c->es.n1e : c->es.n0e);
+    int rc;
+    if ((rc = c->ensure_ye(per*k.nlev*(k.blocks ? 2 : 1)))) return rc;
+    a.out = c->d_ye; a.os = per;
+    if ((rc = launch_elem_apply(c, k.op, a))) return rc;
+    const double* src = c->d_ye;
+    if (k.blocks) {
+        double* ze = c->d_ye + per*k.nlev;
+        if ((rc = launch_blocks_residual(c, k.nlev, k.blocks, c->d_ye, per, k.epi->b, k.epi->bs, ze, per, k.epi->escale, k.epi->ess))) return rc;
+        src = ze;
+    }
+    return launch_gather_epilogue(c, outsp, k.nlev, src, per, *k.epi, k.y, k.ys);
+}
+
+// fused path (experiments): group-local sums in LDS, complete slots written straight to y, perimeter partials to the workspace
+static int apply_fused(mimsem_ctx* c, const ApplyCall& k, ElemArgs& a) {
+    if (int rc = c->ensure_ye((long long)std::max(c->f_npart, 1)*k.nlev)) return rc;
+    a.fperm = c->d_fperm; a.flid = c->d_flid; a.fslot = c->d_fslot; a.fcnt = c->d_fcnt;
+    a.ngroups = c->f_ngroups; a.lmax = c->f_lmax;
+    a.y = k.y; a.ys = k.ys; a.out = c->d_ye; a.os = c->f_npart;
+    const int rc = launch_elem_apply(c, k.op, a);
+    return rc ? rc : launch_gather_perim(c, k.nlev, c->d_ye, c->f_npart, a.accum, k.y, k.ys);
+}
+
+// wave-level fused path: complete slots straight into y, one partial per perimeter slot into the workspace, perimeter pass
+static int apply_wave1(mimsem_ctx* c, const ApplyCall& k, ElemArgs& a, bool splits) {
+    const WaveTables& w = c->wv;
+    const ElemSizes& es = c->es;
+    const int nlev = k.nlev;
+    // owner-computes (Umat at p = 3, a whole apply): one launch; the workspace row keeps only its dump tail (a ragged last chunk)
+    const bool own = w.own && !splits && k.op == MIMSEM_OP_UMAT && es.n == 3 && !c->d_tIn && w.ntiles == 0;
+    const long long prow = (own ? 0LL : (long long)w.npart) + 128;  // partial sums of a level + the dump tail (64 lanes x 16 bytes)
+    int g0 = 0, g1 = w.ngroups, r0 = 0, r1 = w.nps;
+    if (splits && k.part == MIMSEM_PART_BOUNDARY) { g1 = w.nbgroups; r1 = w.nbrec; }
+    if (splits && k.part == MIMSEM_PART_INTERIOR) { g0 = w.nbgroups; r0 = w.nbrec; }
+    a.wlane = w.lane; a.wplan = own ? w.oplan : w.plan; a.wgroups = g1 - g0; a.wg0 = g0; a.wdump = own ? 0 : w.npart;
+    a.wgh = own ? w.gh : nullptr; a.wgx = w.gx;
+    // (the four-level pass adds a pair row to a 32-bit lane offset of the thickInv pair table: half the range of fits_32bit)
+    a.wgh4 = (own && (long long)c->nEl*es.mp12 < (1LL << 27)) ? w.gh4 : nullptr;
+    a.wsing = w.nsing ? w.sing : nullptr; a.wnode = w.node; a.wG = w.G; a.wR = w.R;
+    if (c->d_tIn) { a.tIp = c->d_tIn; a.tps = (long long)c->n0*2; a.tnode = 1; }     // (MIMSEM_WAVE_TNODE=1: thickInv per node)
+    a.lch = wave_level_chunk(c, nlev);
+    a.wcpp = wave_chunks_per_item(c, nlev, a.lch, g1 - g0);
+    if (own) {                                                       // level ranges instead of chunks (wave_level_parts)
+        const WaveParts wp = wave_level_parts(c, nlev, g1 - g0);
+        a.wnp = wp.np; a.wpb = wp.pb; a.wpr = wp.pr;
+        a.lch = nlev == 1 ? 1 : 8; a.wcpp = 1;                         // (lch only picks the instantiation: single-level calls have their own)
+    }
+    a.swz = c->wave_order;
+    if (w.ntiles > 0) {                                              // tile mode (never together with a halo split: setup_wave)
+        if (splits) return MIMSEM_ERR_STATE;
+        a.wtfin = w.tfin; a.wtile = WTF;
+        a.wcpp = std::min(a.wcpp, MIMSEM_WTLEV/8);                   // the tile's LDS rows hold MIMSEM_WTLEV levels
+        a.swz &= ~2;                                                 // group-minor work items: the four waves of a workgroup = the four groups of a tile
+    }
+    // the whole operator in ONE launch: each side of the perimeter is finished by the group that reaches it second (not for the
+    // parts of a split apply: their partial sums wait for the other part, and the perimeter pass finishes them)
+    const bool fin = !own && w.can_fin && !splits && !a.wtfin && (nlev + a.lch*a.wcpp - 1)/(a.lch*a.wcpp) <= std::max(c->nk, 1);
+    a.wfin = fin ? w.fin : nullptr; a.wsslot = w.sslot; a.wcnt = w.cnt;
+    a.wfence = (fin && c->w_partmem == 2 && exp_env("MIMSEM_WAVE_FIN_FENCE") && atoi(exp_env("MIMSEM_WAVE_FIN_FENCE")) != 0) ? 1 : 0;
+    if (splits) {
+        // the pending BOUNDARY part and its INTERIOR part must match; nothing else can consume or overwrite the partial sums
+        if (k.part == MIMSEM_PART_BOUNDARY) {
+            if (c->split.pending) return MIMSEM_ERR_STATE;
+        } else if (!c->split.pending || c->split.op != k.op || c->split.lev0 != k.lev0 || c->split.nlev != nlev ||
+                   c->split.flags != k.flags || c->split.y != k.y || c->split.ys != k.ys) return MIMSEM_ERR_STATE;
+    }
+    int rc;
+    if ((rc = fin ? c->ensure_wpart(prow*nlev) : (splits ? c->ensure_wsplit(prow*nlev) : c->ensure_ye(prow*nlev)))) return rc;
+    double* const prt = fin ? c->d_wpart : (splits ? c->d_wsplit : c->d_ye);
+    a.y = k.y; a.ys = k.ys; a.out = prt; a.os = prow;
+    basis_by_value(c, a);
+#ifdef MIMSEM_STAMPS
+    const size_t stamp_items = stamps_begin(c, nlev, a);
+#endif
+    rc = a.wgroups > 0 ? launch_apply_wave(c, k.op, a) : MIMSEM_OK;
+#ifdef MIMSEM_STAMPS
+    stamps_report(c, a, stamp_items);
+#endif
+    if (!rc && !fin && !own) rc = launch_wave_perim(c, nlev, prt, prow, a.accum, k.y, k.ys, r0, r1);
+    if (splits && !rc) {
+        if (k.part == MIMSEM_PART_BOUNDARY) { c->split.pending = true; c->split.op = k.op; c->split.lev0 = k.lev0; c->split.nlev = nlev;
+                                              c->split.flags = k.flags; c->split.y = k.y; c->split.ys = k.ys; }
+        else c->split.pending = false;
+    }
+    return rc;
+}
+
+// the plain form: element pass into the workspace, gather-sum pass
+static int apply_two_pass(mimsem_ctx* c, const ApplyCall& k, ElemArgs& a, int outsp) {
+    const long long per = (long long)c->nEl*(outsp == 1 ? 2*c->es.n1e : c->es.n0e);
+    if (int rc = c->ensure_ye(per*k.nlev)) return rc;
+    a.out = c->d_ye; a.os = per;
+    if (c->direct) { a.d0 = c->d_d0; a.d1x = c->d_d1x; a.d1y = c->d_d1y; a.y = k.y; a.ys = k.ys; }
+    const int rc = launch_elem_apply(c, k.op, a);
+    return rc ? rc : launch_gather_sum(c, outsp, k.nlev, c->d_ye, per, a.accum, k.y, k.ys, c->direct);
+}
+
+// validates a call, picks its route and arms the profiling events around it
+static int op_apply_core(mimsem_ctx* c, const ApplyCall& k) {
+    if (!c || k.nlev < 0) return MIMSEM_ERR_ARG;
+    const int op = k.op, nlev = k.nlev;
     // interior / boundary split: only the wave-level form with marked halo slots really splits; everything else runs whole as
     // "the boundary part" and has nothing left for "the interior part", so callers can always issue both
     const bool wave_op = op == MIMSEM_OP_UMAT || op == MIMSEM_OP_UHMAT || op == MIMSEM_OP_ROTMAT || op == MIMSEM_OP_UTMAT || op == MIMSEM_OP_UTMAT_H;
-    const bool splits = part != 0 && c->wave1 && c->w_split && wave_op && !epi &&
-                        (long long)c->n1 < (1LL << 28) && (long long)c->n0 < (1LL << 28) && (long long)c->n2 < (1LL << 28) && (long long)c->nEl*c->es.mp12 < (1LL << 28);
-    if (part == MIMSEM_PART_INTERIOR && !splits) return MIMSEM_OK;
+    const bool fits = fits_32bit(c, true);
+    const bool splits = k.part != 0 && c->wv.on && c->wv.split && wave_op && !k.epi && fits;
+    if (k.part == MIMSEM_PART_INTERIOR && !splits) return MIMSEM_OK;
     int in, cf, outsp;
     if (op_spaces(op, &in, &cf, &outsp)) return MIMSEM_ERR_ARG;
     if (nlev == 0 || c->nEl == 0) return MIMSEM_OK;       // empty batch: nothing to do (pointers of empty arrays may be null)
-    if (!x || !y) return MIMSEM_ERR_ARG;
-    if (cf >= 0 && !f) return MIMSEM_ERR_ARG;
-    if (geom_lev0 < 0 || geom_lev0 + (lev_step ? nlev : 1) > c->nk) return MIMSEM_ERR_ARG;
-    if (op == MIMSEM_OP_UTMAT && geom_lev0 + nlev > c->nk - 1) return MIMSEM_ERR_ARG;   // needs thick[lev+1]
-    if (nlev == 0 || c->nEl == 0) return MIMSEM_OK;
+    if (!k.x || !k.y) return MIMSEM_ERR_ARG;
+    if (cf >= 0 && !k.f) return MIMSEM_ERR_ARG;
+    if (k.lev0 < 0 || k.lev0 + (k.lev_step ? nlev : 1) > c->nk) return MIMSEM_ERR_ARG;
+    if (op == MIMSEM_OP_UTMAT && k.lev0 + nlev > c->nk - 1) return MIMSEM_ERR_ARG;   // needs thick[lev+1]
     if (op == MIMSEM_OP_WMATINV || op == MIMSEM_OP_WHMATINV)
-        return mimsem_colop_block_inverse_apply(c, op, geom_lev0, nlev, scale, flags, f, fs, x, xs, y, ys, alpha);
-
-    const ElemSizes& es = c->es;
-    ElemArgs a;
-    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0; a.wgh = nullptr; a.wgx = nullptr;
-    a.nEl = c->nEl; a.nlev = nlev; a.lev0 = geom_lev0; a.total = c->nEl*nlev;
-    a.flags = flags; a.scale = scale; a.alpha = alpha;
-    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*c->es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;
-    a.i0 = c->d_i0; a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2; a.iq = c->d_iq;
+        return mimsem_colop_block_inverse_apply(c, op, k.lev0, nlev, k.scale, k.flags, k.f, k.fs, k.x, k.xs, k.y, k.ys, k.alpha);
     if (in == 3 && !c->d_iq) return MIMSEM_ERR_STATE;     // projection operators need mimsem_mesh_desc::indsq
-    a.f = f; a.fs = fs; a.x = x; a.xs = xs;
-    a.f2 = f2; a.f2s = f2s; a.param = param; a.xn = c->d_xn;
-    a.lstep = lev_step;                 // 0 (mimsem_op_apply_levels): the forms below that walk consecutive levels are passed over
-    {
-        a.lch = level_chunk(c, nlev);
-        a.swz = 0;   // pass 1: the natural order already keeps all level-chunks of an element on one XCD (profiles/r01_swizzle_ab.txt)
-    }
-    int rc;
-    c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
+
+    ElemArgs a = elem_args(c, k.lev0, nlev, k.flags, k.scale, k.alpha);
+    a.f = k.f; a.fs = k.fs; a.x = k.x; a.xs = k.xs; a.f2 = k.f2; a.f2s = k.f2s; a.param = k.param;
+    a.lstep = k.lev_step;               // 0 (mimsem_op_apply_levels): the forms that walk consecutive levels are passed over
+    const bool walks = k.lev_step == 1;
+    if (outsp != 2) { a.accum = (k.flags & MIMSEM_FLAG_ACCUM) ? 1 : 0; a.flags = k.flags & ~MIMSEM_FLAG_ACCUM; }      // (the scatter passes accumulate, not the element pass)
     if (c->profiling && (c->prof_count++ % c->prof_every) == 0) { c->ev_k1[0] = c->next_event(); c->ev_k1[1] = c->next_event(); c->ev_k2[0] = c->next_event(); c->ev_k2[1] = c->next_event(); c->ev_has2.push_back(0); }
+    int rc;
     if (outsp == 2) {
-        a.out = y; a.os = ys;
+        a.out = k.y; a.os = k.ys;
         // Wmat itself stays on k_elem_apply by default: measured 9.3e9 applies/s there against 8.2e9 on the DPP kernel (its element algebra
         // is four DPP stages for 9 values); Whmat +3 %, WtQUmat +14 % (profiles/r02_wave_ab.txt).  MIMSEM_WAVE2=2 includes Wmat, 0 none.
         const bool wave2_op = (op == MIMSEM_OP_WMAT && c->wave2_mode == 2) || op == MIMSEM_OP_WHMAT || op == MIMSEM_OP_WTQUMAT || op == MIMSEM_OP_WTQDUDZ;
-        const bool fits = (long long)c->n1 < (1LL << 28) && (long long)c->n2 < (1LL << 28) && (long long)c->nEl*es.mp12 < (1LL << 28);
-        if (c->wave1 && es.n == 3 && wave2_op && fits && part == 0 && c->wave2_mode != 0 && lev_step == 1) {
-            // p = 3: the wave-level kernel of the 2-form-valued operators (no scatter: one launch)
-            if ((rc = c->ensure_ye(64))) return rc;
-            a.wlane = c->d_wlane; a.wplan = nullptr; a.wgroups = c->w_ngroups; a.wg0 = 0; a.wdump = 0; a.wsing = nullptr; a.wnode = nullptr;
-            a.wG = c->d_wG; a.wR = c->d_wR; a.wstamps = nullptr;
-            a.lch = wave_level_chunk(c, nlev); a.wcpp = wave_chunks_per_item(c, nlev, a.lch, c->w_ngroups); a.swz = c->wave_order;
-            a.accum = (flags & MIMSEM_FLAG_ACCUM) ? 1 : 0; a.y = c->d_ye;       // a.y: the dump for idle lanes
-            for (size_t k = 0; k < 20; k++) a.Etab[k] = k < c->tab.E.size() ? c->tab.E[k] : 0.0;
-            for (size_t k = 0; k < 5; k++) a.Wq[k] = k < c->tab.quad.w.size() ? c->tab.quad.w[k] : 0.0;
-            rc = launch_apply_wave2(c, op, a);
-            c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
-            return rc;
-        }
-        rc = launch_elem_apply(c, op, a);
-        c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
-        return rc;
+        if (c->wv.on && c->es.n == 3 && wave2_op && fits_32bit(c, false) && k.part == 0 && c->wave2_mode != 0 && walks) rc = apply_wave2(c, k, a);
+        else rc = launch_elem_apply(c, op, a);
     }
-    a.fperm = nullptr; a.accum = (flags & MIMSEM_FLAG_ACCUM) ? 1 : 0;
-    a.d0 = a.d1x = a.d1y = nullptr; a.y = nullptr; a.ys = 0;
-    if (epi) {
-        // Richardson sweep: element pass into the workspace, then the gather with the update epilogue (y is the iterate);
-        // with `blocks` the element-block preconditioner runs in between on the second half of the workspace
-        const long long per = (long long)c->nEl*(outsp == 1 ? 2*es.n1e : es.n0e);
-        if ((rc = c->ensure_ye(per*nlev*(blocks ? 2 : 1)))) return rc;
-        a.out = c->d_ye; a.os = per;
-        a.flags = flags & ~MIMSEM_FLAG_ACCUM;
-        if ((rc = launch_elem_apply(c, op, a))) return rc;
-        const double* src = c->d_ye;
-        if (blocks) {
-            double* ze = c->d_ye + per*nlev;
-            if ((rc = launch_blocks_residual(c, nlev, blocks, c->d_ye, per, epi->b, epi->bs, ze, per, epi->escale, epi->ess))) return rc;
-            src = ze;
-        }
-        return launch_gather_epilogue(c, outsp, nlev, src, per, *epi, y, ys);
-    }
-    if (outsp == 1 && c->fused1 && op < MIMSEM_OP_UMAT_UP && op != MIMSEM_OP_UMAT_RAY && lev_step == 1) {
-        // fused path: group-local sums in LDS, complete slots written straight to y, perimeter partials to the workspace
-        if ((rc = c->ensure_ye((long long)std::max(c->f_npart, 1)*nlev))) return rc;
-        a.fperm = c->d_fperm; a.flid = c->d_flid; a.fslot = c->d_fslot; a.fcnt = c->d_fcnt;
-        a.ngroups = c->f_ngroups; a.lmax = c->f_lmax;
-        a.y = y; a.ys = ys; a.out = c->d_ye; a.os = c->f_npart;
-        a.flags = flags & ~MIMSEM_FLAG_ACCUM;
-        rc = launch_elem_apply(c, op, a);
-        if (!rc) rc = launch_gather_perim(c, nlev, c->d_ye, c->f_npart, a.accum, y, ys);
-        c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
-        return rc;
-    }
-    // the wave kernel addresses its rows with 32-bit byte offsets: vectors / metric beyond 4 GB per level stay on the two-pass form
-    const bool wave_fits = (long long)c->n1 < (1LL << 28) && (long long)c->n0 < (1LL << 28) && (long long)c->n2 < (1LL << 28) &&
-                           (long long)c->nEl*es.mp12 < (1LL << 28);
-    if (c->wave1 && wave_fits && wave_op && lev_step == 1) {
-        // wave-level fused path: complete slots straight into y, one partial per perimeter slot into the workspace, perimeter pass
-        // owner-computes (Umat at p = 3, a whole apply): one launch; the workspace row keeps only its dump tail (a ragged last chunk)
-        const bool own = c->w_own && !splits && op == MIMSEM_OP_UMAT && es.n == 3 && !c->d_tIn && c->w_ntiles == 0;
-        const long long prow = (own ? 0LL : (long long)c->w_npart) + 128;  // partial sums of a level + the dump tail (64 lanes x 16 bytes)
-        int g0 = 0, g1 = c->w_ngroups, r0 = 0, r1 = c->w_nps;
-        if (splits && part == MIMSEM_PART_BOUNDARY) { g1 = c->w_nbgroups; r1 = c->w_nbrec; }
-        if (splits && part == MIMSEM_PART_INTERIOR) { g0 = c->w_nbgroups; r0 = c->w_nbrec; }
-        a.wlane = c->d_wlane; a.wplan = own ? c->d_woplan : c->d_wplan; a.wgroups = g1 - g0; a.wg0 = g0; a.wdump = own ? 0 : c->w_npart;
-        a.wgh = own ? c->d_wgh : nullptr; a.wgx = c->d_wgx;
-        // (the four-level pass adds a pair row to a 32-bit lane offset of the thickInv pair table: half the range of wave_fits)
-        a.wgh4 = (own && (long long)c->nEl*es.mp12 < (1LL << 27)) ? c->d_wgh4 : nullptr;
-        a.wsing = c->w_nsing ? c->d_wsing : nullptr; a.wnode = c->d_wnode; a.wG = c->d_wG; a.wR = c->d_wR;
-        if (c->d_tIn) { a.tIp = c->d_tIn; a.tps = (long long)c->n0*2; a.tnode = 1; }     // (MIMSEM_WAVE_TNODE=1: thickInv per node)
-        a.lch = wave_level_chunk(c, nlev);
-        a.wcpp = wave_chunks_per_item(c, nlev, a.lch, g1 - g0);
-        a.wnp = a.wpb = a.wpr = 0;
-        if (own) {                                                       // level ranges instead of chunks (wave_level_parts)
-            const WaveParts wp = wave_level_parts(c, nlev, g1 - g0);
-            a.wnp = wp.np; a.wpb = wp.pb; a.wpr = wp.pr;
-            a.lch = nlev == 1 ? 1 : 8; a.wcpp = 1;                         // (lch only picks the instantiation: single-level calls have their own)
-        }
-        a.swz = c->wave_order;
-        a.wtfin = nullptr; a.wtile = 0;
-        if (c->w_ntiles > 0) {                                           // tile mode (never together with a halo split: setup_wave)
-            if (splits) return MIMSEM_ERR_STATE;
-            a.wtfin = c->d_wtfin; a.wtile = WTF;
-            a.wcpp = std::min(a.wcpp, MIMSEM_WTLEV/8);                   // the tile's LDS rows hold MIMSEM_WTLEV levels
-            a.swz &= ~2;                                                 // group-minor work items: the four waves of a workgroup = the four groups of a tile
-        }
-        // the whole operator in ONE launch: each side of the perimeter is finished by the group that reaches it second (not for the
-        // parts of a split apply: their partial sums wait for the other part, and the perimeter pass finishes them)
-        const bool fin = !own && c->w_fin && !splits && !a.wtfin && (nlev + a.lch*a.wcpp - 1)/(a.lch*a.wcpp) <= std::max(c->nk, 1);
-        a.wfin = fin ? c->d_wfin : nullptr; a.wsslot = c->d_wsslot; a.wcnt = c->d_wcnt;
-        a.wfence = (fin && c->w_partmem == 2 && exp_env("MIMSEM_WAVE_FIN_FENCE") && atoi(exp_env("MIMSEM_WAVE_FIN_FENCE")) != 0) ? 1 : 0;
-        if (splits) {
-            // the pending BOUNDARY part and its INTERIOR part must match; nothing else can consume or overwrite the partial sums
-            if (part == MIMSEM_PART_BOUNDARY) {
-                if (c->split.pending) return MIMSEM_ERR_STATE;
-            } else if (!c->split.pending || c->split.op != op || c->split.lev0 != geom_lev0 || c->split.nlev != nlev ||
-                       c->split.flags != flags || c->split.y != y || c->split.ys != ys) return MIMSEM_ERR_STATE;
-        }
-        if ((rc = fin ? c->ensure_wpart(prow*nlev) : (splits ? c->ensure_wsplit(prow*nlev) : c->ensure_ye(prow*nlev)))) return rc;
-        double* const prt = fin ? c->d_wpart : (splits ? c->d_wsplit : c->d_ye);
-        a.y = y; a.ys = ys; a.out = prt; a.os = prow;
-        a.flags = flags & ~MIMSEM_FLAG_ACCUM;
-        a.wstamps = nullptr;
-        for (size_t k = 0; k < 20; k++) a.Etab[k] = k < c->tab.E.size() ? c->tab.E[k] : 0.0;
-#ifdef MIMSEM_STAMPS      // diagnostic build: per-phase s_memtime stamps of every work item of this launch, summarised on stderr
-        static long long* d_st = nullptr; static size_t st_items = 0;
-        const size_t items = (size_t)c->w_ngroups*std::max((nlev + a.lch - 1)/a.lch, a.wnp);     // (the kernel stamps item < wgroups x parts: never fewer slots than that)
-        if (exp_env("MIMSEM_WAVE_STAMPS")) {
-            if (items > st_items) { if (d_st) (void)hipFree(d_st); (void)hipMalloc((void**)&d_st, items*16*8); st_items = items; }
-            (void)hipMemsetAsync(d_st, 0, items*16*8, c->stream);
-            a.wstamps = d_st;
-        }
-#endif
-        rc = a.wgroups > 0 ? launch_apply_wave(c, op, a) : MIMSEM_OK;
-#ifdef MIMSEM_STAMPS
-        if (a.wstamps) {
-            (void)hipStreamSynchronize(c->stream);
-            std::vector<long long> h(items*16);
-            (void)hipMemcpy(h.data(), d_st, items*16*8, hipMemcpyDeviceToHost);
-            long long t0 = h[0], t1 = 0;
-            for (size_t i = 0; i < items; i++) { t0 = std::min(t0, h[i*16]); t1 = std::max(t1, h[i*16 + 15]); }
-            fprintf(stderr, "[stamps] items %zu lch %d  first entry -> last done: %lld ticks\n", items, a.lch, t1 - t0);
-            const char* names[16] = {"entry(rel. first)", "barrier", "tables requested", "level loads issued", "batch0", "batch1", "batch2", "batch3",
-                                     "b4", "b5", "b6", "chunks done", "fin: stores acked", "fin: arrival counted", "fin: sides finished", "stores acked"};
-            for (int k = 0; k < 16; k++) {
-                std::vector<long long> v;
-                for (size_t i = 0; i < items; i++) if (h[i*16 + k]) v.push_back(k == 0 ? h[i*16] - t0 : h[i*16 + k] - h[i*16]);
-                if (v.empty()) continue;
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, "[stamps] %-20s min %8lld  p10 %8lld  median %8lld  p90 %8lld  max %8lld   (ticks since the wave's entry)\n", names[k],
-                        v.front(), v[v.size()/10], v[v.size()/2], v[v.size()*9/10], v.back());
-            }
-        }
-#endif
-        if (!rc && !fin && !own) rc = launch_wave_perim(c, nlev, prt, prow, a.accum, y, ys, r0, r1);
-        if (splits && !rc) {
-            if (part == MIMSEM_PART_BOUNDARY) { c->split.pending = true; c->split.op = op; c->split.lev0 = geom_lev0; c->split.nlev = nlev;
-                                                c->split.flags = flags; c->split.y = y; c->split.ys = ys; }
-            else c->split.pending = false;
-        }
-        c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
-        return rc;
-    }
-    const long long per = (long long)c->nEl*(outsp == 1 ? 2*es.n1e : es.n0e);
-    if ((rc = c->ensure_ye(per*nlev))) return rc;
-    a.out = c->d_ye; a.os = per;
-    a.flags = flags & ~MIMSEM_FLAG_ACCUM;
-    if (c->direct) { a.d0 = c->d_d0; a.d1x = c->d_d1x; a.d1y = c->d_d1y; a.y = y; a.ys = ys; a.accum = (flags & MIMSEM_FLAG_ACCUM) ? 1 : 0; }
-    rc = launch_elem_apply(c, op, a);
-    if (!rc) rc = launch_gather_sum(c, outsp, nlev, c->d_ye, per, (flags & MIMSEM_FLAG_ACCUM) ? 1 : 0, y, ys, c->direct);
+    else if (k.epi) rc = apply_epilogue(c, k, a, outsp);
+    else if (outsp == 1 && c->fused1 && op < MIMSEM_OP_UMAT_UP && op != MIMSEM_OP_UMAT_RAY && walks) rc = apply_fused(c, k, a);
+    else if (c->wv.on && fits && wave_op && walks) rc = apply_wave1(c, k, a, splits);
+    else rc = apply_two_pass(c, k, a, outsp);
     c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
     return rc;
 }
@@ -1676,7 +1667,7 @@ int mimsem_op_richardson_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev, d
     if (op_spaces(op, &in, &cf, &outsp) || outsp == 2 || in != outsp) return MIMSEM_ERR_ARG;     // square operators on gathered spaces
     if (is_up_op(op) && !u) return MIMSEM_ERR_ARG;
     GatherEpilogue g{1, b, bs, dinv, ds, upd, upds};
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, u, us, tau, x, xs, x, xs, 1.0, &g);
+    return op_apply_core(c, {op, geom_lev0, nlev, scale, flags, f, fs, x, xs, x, xs, 1.0, u, us, tau, &g});
 }
 
 // the Chebyshev form of mimsem_op_richardson_sweep: z = dinv (b - Op x);  p = z + beta p;  x += alpha p  (two launches)
@@ -1690,7 +1681,7 @@ int mimsem_op_chebyshev_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev, do
     if (is_up_op(op) && !u) return MIMSEM_ERR_ARG;
     GatherEpilogue g{5, b, bs, dinv, ds, upd, upds};
     g.alpha = alpha; g.beta = beta; g.p = p; g.ps = ps;
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, u, us, tau, x, xs, x, xs, 1.0, &g);
+    return op_apply_core(c, {op, geom_lev0, nlev, scale, flags, f, fs, x, xs, x, xs, 1.0, u, us, tau, &g});
 }
 
 int mimsem_block_richardson_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
@@ -1701,7 +1692,7 @@ int mimsem_block_richardson_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev
     if (op_spaces(op, &in, &cf, &outsp) || outsp != 1 || in != 1 || is_up_op(op)) return MIMSEM_ERR_ARG;
     if (c->es.n > 5) return MIMSEM_ERR_UNSUPPORTED;
     GatherEpilogue g{2, b, bs, nullptr, 0, upd, upds};
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, x, xs, 1.0, &g, blocks);
+    return op_apply_core(c, {op, geom_lev0, nlev, scale, flags, f, fs, x, xs, x, xs, 1.0, nullptr, 0, 0.0, &g, blocks});
 }
 
 int mimsem_block_chebyshev_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev, double scale, unsigned flags,
@@ -1714,7 +1705,7 @@ int mimsem_block_chebyshev_sweep(mimsem_ctx* c, int op, int geom_lev0, int nlev,
     if (c->es.n > 5) return MIMSEM_ERR_UNSUPPORTED;
     GatherEpilogue g{3, b, bs, nullptr, 0, upd, upds};
     g.alpha = alpha; g.beta = beta; g.p = p; g.ps = ps; g.escale = elem_scale; g.ess = es_stride;
-    return op_apply_core(c, op, geom_lev0, nlev, scale, flags, f, fs, nullptr, 0, 0.0, x, xs, x, xs, 1.0, &g, blocks);
+    return op_apply_core(c, {op, geom_lev0, nlev, scale, flags, f, fs, x, xs, x, xs, 1.0, nullptr, 0, 0.0, &g, blocks});
 }
 
 // A whole fixed-length Chebyshev solve of  Umat x = b  from x = 0 in ONE call (round 6): the first step has no element pass (Op 0 = 0: the block
@@ -1744,15 +1735,8 @@ static int block_chebyshev_solve_core(mimsem_ctx* c, int op, int eop, int geom_l
     if ((rc = c->ensure_ye(per*nlev*2))) return rc;
     if ((rc = c->ensure_cheb((pend ? 3 : 1)*n1*nlev))) return rc;
     double* ye = c->d_ye; double* ze = c->d_ye + per*nlev;
-    ElemArgs a;
-    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0; a.wgh = nullptr; a.wgx = nullptr;
-    a.nEl = c->nEl; a.nlev = nlev; a.lev0 = geom_lev0; a.total = c->nEl*nlev;
-    a.flags = flags; a.scale = scale; a.alpha = 1.0;
-    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;
-    a.i0 = c->d_i0; a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2; a.iq = c->d_iq;
-    a.f = ef; a.fs = efs; a.f2 = ef2; a.f2s = 0; a.param = tau; a.xn = c->d_xn;
-    a.lch = level_chunk(c, nlev); a.swz = 0;
-    a.fperm = nullptr; a.accum = 0; a.d0 = a.d1x = a.d1y = nullptr; a.y = nullptr; a.ys = 0;
+    ElemArgs a = elem_args(c, geom_lev0, nlev, flags, scale, 1.0);
+    a.f = ef; a.fs = efs; a.f2 = ef2; a.param = tau;
     a.out = ye; a.os = per;
     c->ev_k1[0] = c->ev_k1[1] = c->ev_k2[0] = c->ev_k2[1] = nullptr;
     // step 0: z_0 = P b
@@ -1863,20 +1847,6 @@ int mimsem_sw_chebyshev_flush(mimsem_ctx* c, int nlev, double ca, double cb, dou
     return launch_sw_chebyshev_flush(c, nlev, ca, cb, x, xs, r, d, vs);
 }
 
-// the element-pass arguments of a single-level sweep on the src/ flavour (scale 1, no thickness), as op_apply_core fills them for its epilogue path
-static void sweep_elem_args(mimsem_ctx* c, ElemArgs& a, const double* f, const double* f2, double param, const double* x, double* out, long long os) {
-    a.wfin = nullptr; a.wsslot = nullptr; a.wcnt = nullptr; a.wfence = 0; a.wgh = nullptr; a.wgx = nullptr;
-    a.nEl = c->nEl; a.nlev = 1; a.lev0 = 0; a.total = c->nEl;
-    a.flags = 0; a.scale = 1.0; a.alpha = 1.0;
-    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.th = c->d_th; a.tIp = c->d_tIp; a.tnp = c->nk/2 + 1; a.tps = (long long)c->nEl*c->es.mp12*2; a.tnode = 0; a.E = c->d_E; a.w = c->d_w;
-    a.i0 = c->d_i0; a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2; a.iq = c->d_iq;
-    a.f = f; a.fs = 0; a.x = x; a.xs = 0;
-    a.f2 = f2; a.f2s = 0; a.param = param; a.xn = c->d_xn;
-    a.lch = level_chunk(c, 1); a.swz = 0;
-    a.fperm = nullptr; a.accum = 0; a.d0 = a.d1x = a.d1y = nullptr; a.y = nullptr; a.ys = 0;
-    a.out = out; a.os = os;
-}
-
 // Two independent fixed-length Chebyshev solves of a shallow-water Picard iteration, both from x = 0, in SHARED launches (round 6;
 // csrc/elem_kernels.hip: k_sw_pair): exactly the sequence
 //     for k < nA: mimsem_block_chebyshev_sweep(ctx, MIMSEM_OP_UMAT, 0, 1, 1.0, 0, NULL, 0, blocks1, NULL, 0, b1, 0, coefA[2k], coefA[2k+1], p1, 0, x1, 0, k == nA-1 ? upd1 : (k == 0 ? pb1 : NULL), 0)
@@ -1898,9 +1868,10 @@ int mimsem_sw_dual_chebyshev(mimsem_ctx* c, int nA, const double* coefA, const d
     int rc = c->ensure_ye(2*per1 + per0);
     if (rc) return rc;
     double *yeA = c->d_ye, *zeA = c->d_ye + per1, *yeQ = c->d_ye + 2*per1;
-    ElemArgs ea, eq;
-    sweep_elem_args(c, ea, nullptr, nullptr, 0.0, x1, yeA, per1);
-    sweep_elem_args(c, eq, h, u, tau, x0, yeQ, per0);
+    // the element passes of two single-level sweeps on the src/ flavour (scale 1, no thickness), as apply_epilogue runs them
+    ElemArgs ea = elem_args(c, 0, 1, 0, 1.0, 1.0), eq = ea;
+    ea.x = x1; ea.out = yeA; ea.os = per1;
+    eq.f = h; eq.f2 = u; eq.param = tau; eq.x = x0; eq.out = yeQ; eq.os = per0;
     PairBlocks ba{c->nEl, 1, c->d_i1x, c->d_i1y, c->d_g1, blocks1, yeA, per1, b1, zeA, per1, (const int4*)c->d_bplan};
     PairGather ga{zeA, per1, c->d_g1, c->n1, GatherEpilogue{3, b1, 0, nullptr, 0, nullptr, 0}, x1};
     PairGather gq{yeQ, per0, c->d_g0, c->n0, GatherEpilogue{5, b0, 0, dinv, 0, nullptr, 0}, x0};

@@ -1211,10 +1211,8 @@ int launch_sweep(mimsem_ctx* c, const SweepArgs& a) {
 int ensure_colstat(mimsem_ctx* c) {
     if (c->d_colstat) return MIMSEM_OK;
     if (c->is_capturing()) return MIMSEM_ERR_STATE;
-    MIMSEM_HIP_TRY(hipMalloc((void**)&c->d_colstat, (2*(size_t)c->nEl + 2)*sizeof(int)));
-    MIMSEM_HIP_TRY(hipMalloc((void**)&c->d_colratio, (size_t)std::max(c->nEl, 1)*sizeof(double)));
-    c->bytes += (2*(long long)c->nEl + 2)*4 + (long long)c->nEl*8;
-    return MIMSEM_OK;
+    if (int rc = c->alloc((void**)&c->d_colstat, (2*(size_t)c->nEl + 2)*sizeof(int))) return rc;
+    return c->alloc((void**)&c->d_colratio, (size_t)c->nEl*sizeof(double));
 }
 int launch_thomas_dpp(mimsem_ctx* c, int refine, const double* L, const double* f, double* d, double* G, double* D, double* y, bool counter_zeroed = false) {
     if (int rc = ensure_colstat(c)) return rc;

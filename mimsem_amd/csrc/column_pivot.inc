@@ -384,13 +384,7 @@ int launch_band_lu_flagged(mimsem_ctx* c, int nb, const double* L, bool rowmajor
     int grid = c->pivot_fallback == 2 ? (int)std::max(64LL, std::min<long long>(1024, (256LL << 20)/(per*8))) : 64;
     grid = std::max(1, std::min(grid, c->nEl));
     const long long need = per*grid;
-    if (need > c->lu_doubles) {
-        if (c->is_capturing()) return MIMSEM_ERR_STATE;                  // (hipMalloc is illegal in a capture: warm the solve up outside it)
-        double* nw = nullptr;
-        MIMSEM_HIP_TRY(hipMalloc((void**)&nw, (size_t)need*sizeof(double)));
-        if (c->d_lu) c->retired.push_back(c->d_lu);
-        c->d_lu = nw; c->bytes += (need - c->lu_doubles)*8; c->lu_doubles = need;
-    }
+    if (int rc = c->grow(c->d_lu, c->lu_doubles, need)) return rc;      // (MIMSEM_ERR_STATE in a capture: warm the solve up outside it)
     BandLUArgs a{};
     a.nEl = c->nEl; a.nk = nk; a.rs = rowmajor ? n2 : 1; a.js = rowmajor ? 1 : n2; a.all = c->pivot_fallback == 2;
     a.L = L; a.f = f; a.d = d; a.stat = c->d_colstat; a.ratio = c->d_colratio;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/mimsem_hip.h"
 #include "basis_host.hpp"
@@ -42,6 +43,45 @@ struct ElemSizes {
         : n(order), np1(order + 1), mp1(order + 1), mp12((order + 1)*(order + 1)),
           n0e((order + 1)*(order + 1)), n1e((order + 1)*order), n2e(order*order) {}
 };
+
+// The wave-level plan of a context (k_apply_wave, elem_wave.inc): wave-groups of 64/LPE neighbouring elements.  setup_wave (api.hip) builds
+// a whole new value from build_wave_plan / build_wave_own and assigns it only when every table is on the device; the tables of the plan it
+// replaces stay allocated until the context goes (a captured graph may hold their addresses).
+struct WaveTables {
+    bool on = false;                    // the context has a plan (MIMSEM_WAVE=0, orders > 4 and numberings the plan does not fit: none)
+    int ngroups = 0, nsing = 0, nps = 0, npart = 0, ndirect = 0;
+    int npwritten = 0;                  // partial sums a level really gets (npart is the padded row: nsides x 2 x 16)
+    // in-kernel completion of the perimeter (round 3, elem_wave.inc "finishing phase"): the partial sums are laid out per SIDE (the
+    // slots two wave-groups share), and the group that arrives second at a side's counter finishes its slots -- no second launch
+    bool can_fin = false;               // the plan supports it (MIMSEM_WAVE_FIN=0 keeps the perimeter pass)
+    int nsides = 0;
+    int4* fin = nullptr;                // [ngroups][8] {side, arrivals that complete it (2; 1: a side of the group's own), entries, 0} or {-1, 0, 0, 0}
+    int* sslot = nullptr;               // [nsides][16] y slot of entry j of the side (-1: none)
+    int* cnt = nullptr;                 // [nsides][nk] arrival counters, zero between launches (the finishing wave resets its own)
+    int nbgroups = 0, nbrec = 0; bool split = false;     // interior / boundary split (mimsem_ctx_set_halo_slots): boundary prefix sizes
+    int4* lane = nullptr;               // [ngroups][64] {element of the lane, load pair: even slot b, staging positions of x[b] and of x[b+1]
+                                        //   (two 16-bit positions each; the dump position where nobody wants the value)}
+    // owner-computes form (round 7, build_wave_own; Umat at p = 3, default, MIMSEM_WAVE_OWN=0: off, =1: ghost pass per batch): every store pair written finished by
+    // its one owner group, which computes the neighbour's contribution across its ghost sides -- one launch, no perimeter pass
+    bool own = false;
+    int4* oplan = nullptr;              // [ngroups][64] store pairs of the form (as plan; every destination in y)
+    int4* gh = nullptr;                 // [ngroups][16] packed ghost lanes (side*4 + point; round 9)
+    int* gx = nullptr;                  // [ngroups][64] slot the lane gathers per level (16 per ghost side)
+    int4* gh4 = nullptr;                // [ngroups][64] ghost lanes of the four-level pass (own4::k_apply_wave: DPP row = ghost side), or
+                                        //   null: MIMSEM_WAVE_OWN=1 keeps the pass per batch of two levels for every call
+    int4* tfin = nullptr; int ntiles = 0, ninner = 0;      // tile mode (round 5): [ntiles][64] {slot, LDS position of part A, of part B, 0}
+    int4* plan = nullptr;               // [ngroups][64] store pair {dst, result positions of its first and second slot (2 x 16 bit, the
+                                        //   strip's zero for a missing contributor), 0}: dst >= 0: y[dst], y[dst+1]; dst <= -2: partial sums
+                                        //   -(dst+2), +1 of the workspace row (unused lanes: its dump tail)
+    int2* sing = nullptr;               // [ngroups][64] optional 8-byte store round {slot or -1, positions} (MIMSEM_WAVE_SINGLES=1)
+    int* node = nullptr;                // [ngroups][64] node slot of the lane's quadrature point (RotMat's vorticity)
+    double* G = nullptr;                // [ngroups][64][4] {gaa, gab, gbb, 1/det} of the lane's point: Q/det J^T J, in WAVE-GROUP order
+    double* R = nullptr;                // [ngroups][64]    (-J00 J11 + J01 J10) Q/det: RotMat
+    int4* prec = nullptr;               // [nps] {slot, partial 0, partial 1 (-1: none), 0}: slots finished by k_wave_perim (and slots no element
+                                        //   touches: no partial at all, written as 0)
+};
+
+enum class Mem { Plain, Uncached, FineGrained };      // kinds of device memory mimsem_ctx::alloc hands out
 
 struct mimsem_ctx {
     int device = 0;
@@ -91,54 +131,23 @@ struct mimsem_ctx {
     int* d_fcnt = nullptr;              // [ngroups] local ids in use
     int* d_pslot = nullptr;             // [nps] perimeter slots
     int* d_ppart = nullptr;             // [nps][2] their partial-sum indices (-1 = none)
-    // wave-level fused scatter-add (k_apply_wave, elem_wave.inc): wave-groups of 64/LPE neighbouring elements; tables: build_wave_plan
-    bool wave1 = false;
+    // wave-level fused scatter-add (k_apply_wave, elem_wave.inc): the plan is `wv` (WaveTables above); what follows are the tuning knobs
+    WaveTables wv;
     int wave_order = 3;                 // bit 0: XCD-contiguous block order, bit 1: group-major items (MIMSEM_WAVE_ORDER)
     int wave_lch = 0;                   // MIMSEM_WAVE_LCH override of the levels per chunk
     int wave2_mode = 1;                 // MIMSEM_WAVE2: 2-form-valued operators on k_apply_wave2 (p = 3): 0 none, 1 Whmat / WtQUmat / WtQdUdz, 2 also Wmat
     int wave_cpp = 0;                   // MIMSEM_WAVE_CPP override of the chunks per work item (0: heuristic)
     int wave_part = 0;                  // mimsem_ctx_set_wave_split: levels of a part of the owner form's level ranges (0: the items of the chunk form)
-    int w_ngroups = 0, w_nsing = 0, w_nps = 0, w_npart = 0, w_ndirect = 0;
-    int w_npwritten = 0;                // partial sums a level really gets (w_npart is the padded row: w_nsides x 2 x 16)
-    // in-kernel completion of the perimeter (round 3, elem_wave.inc "finishing phase"): the partial sums are laid out per SIDE (the
-    // slots two wave-groups share), and the group that arrives second at a side's counter finishes its slots -- no second launch
-    bool w_fin = false;                 // the plan supports it (MIMSEM_WAVE_FIN=0 keeps the perimeter pass)
-    int w_nsides = 0; int w_partmem = 0;      // w_partmem: 0 uncached, 1 fine-grained, 2 plain (MIMSEM_WPART_MEM, experiments)
-    int4* d_wfin = nullptr;             // [w_ngroups][8] {side, arrivals that complete it (2; 1: a side of the group's own), entries, 0} or {-1, 0, 0, 0}
-    int* d_wsslot = nullptr;            // [w_nsides][16] y slot of entry j of the side (-1: none)
-    int* d_wcnt = nullptr;              // [w_nsides][nk] arrival counters, zero between launches (the finishing wave resets its own)
-    double* d_wpart = nullptr;          // [nlev][w_npart + 128] partial sums of the finishing phase: UNCACHED device memory (plain stores go
+    int w_partmem = 0;                  // memory kind of d_wpart: 0 uncached, 1 fine-grained, 2 plain (MIMSEM_WPART_MEM, experiments)
+    double* d_wpart = nullptr;          // [nlev][wv.npart + 128] partial sums of the finishing phase: UNCACHED device memory (plain stores go
     long long wpart_doubles = 0;        //   through to the memory side: visible to a finishing wave on another XCD once acknowledged)
-    int ensure_wpart(long long doubles);
     // a split apply (mimsem_op_apply_part): its partial sums live in a buffer no other entry point uses, and the pending BOUNDARY part
     // is remembered so that only the matching INTERIOR part can consume it
     double* d_wsplit = nullptr; long long wsplit_doubles = 0;
-    int ensure_wsplit(long long doubles);
     struct { bool pending = false; int op = 0, lev0 = 0, nlev = 0; unsigned flags = 0; const double* y = nullptr; long long ys = 0; } split;
-    int w_nbgroups = 0, w_nbrec = 0; bool w_split = false;     // interior / boundary split (mimsem_ctx_set_halo_slots): boundary prefix sizes
     std::vector<int> h_i1x, h_i1y, h_i0; std::vector<double> h_J, h_det;      // host copies of the mesh for re-deriving the plan
     std::vector<int> h_e0;              // element -> 0-form slot lists (node multiplicities, likewise)
     std::vector<int> h_e1x, h_e1y;      // element -> 1-form slot lists, kept on EVERY context (edge multiplicities of the PCBJACOBI builders, ksp.hip)
-    int4* d_wlane = nullptr;            // [w_ngroups][64] {element of the lane, load pair: even slot b, staging positions of x[b] and of x[b+1]
-                                        //   (two 16-bit positions each; the dump position where nobody wants the value)}
-    // owner-computes form (round 7, build_wave_own; Umat at p = 3, default, MIMSEM_WAVE_OWN=0: off, =1: ghost pass per batch): every store pair written finished by
-    // its one owner group, which computes the neighbour's contribution across its ghost sides -- one launch, no perimeter pass
-    bool w_own = false;
-    int4* d_woplan = nullptr;           // [w_ngroups][64] store pairs of the form (as d_wplan; every destination in y)
-    int4* d_wgh = nullptr;              // [w_ngroups][16] packed ghost lanes (side*4 + point; round 9)
-    int* d_wgx = nullptr;               // [w_ngroups][64] slot the lane gathers per level (16 per ghost side)
-    int4* d_wgh4 = nullptr;             // [w_ngroups][64] ghost lanes of the four-level pass (own4::k_apply_wave: DPP row = ghost side), or
-                                        //   null: MIMSEM_WAVE_OWN=1 keeps the pass per batch of two levels for every call
-    int4* d_wtfin = nullptr; int w_ntiles = 0, w_ninner = 0;      // tile mode (round 5): [w_ntiles][64] {slot, LDS position of part A, of part B, 0}
-    int4* d_wplan = nullptr;            // [w_ngroups][64] store pair {dst, result positions of its first and second slot (2 x 16 bit, the
-                                        //   strip's zero for a missing contributor), 0}: dst >= 0: y[dst], y[dst+1]; dst <= -2: partial sums
-                                        //   -(dst+2), +1 of the workspace row (unused lanes: its dump tail)
-    int2* d_wsing = nullptr;            // [w_ngroups][64] optional 8-byte store round {slot or -1, positions} (MIMSEM_WAVE_SINGLES=1)
-    int* d_wnode = nullptr;             // [w_ngroups][64] node slot of the lane's quadrature point (RotMat's vorticity)
-    double* d_wG = nullptr;             // [w_ngroups][64][4] {gaa, gab, gbb, 1/det} of the lane's point: Q/det J^T J, in WAVE-GROUP order
-    double* d_wR = nullptr;             // [w_ngroups][64]    (-J00 J11 + J01 J10) Q/det: RotMat
-    int4* d_wprec = nullptr;            // [w_nps] {slot, partial 0, partial 1 (-1: none), 0}: slots finished by k_wave_perim (and slots no element
-                                        //   touches: no partial at all, written as 0)
     // workspace
     double* d_ye = nullptr;     // [nk_ws][nEl][max(2*n1e, n0e)] element-local results
     long long ye_doubles = 0;
@@ -146,7 +155,6 @@ struct mimsem_ctx {
     int4* d_own[3] = {nullptr, nullptr, nullptr}; int own_uncovered[3] = {0, 0, 0};      // slots of the form that no element owns
     double* d_pcw = nullptr;    // [nEl][2 n1e] 1 / edge multiplicity of the element-local 1-form DoFs (mimsem_elem_block_pc_build), made on first use
     double* d_cheb = nullptr; long long cheb_doubles = 0;      // mimsem_block_chebyshev_solve: the second iterate and two direction vectors, [3][nlev][n1]
-    int ensure_cheb(long long doubles);
     int *d_d0 = nullptr, *d_d1x = nullptr, *d_d1y = nullptr;   // direct-write slots (single-contributor DoFs), see ElemArgs
     int *d_sh0 = nullptr, *d_sh1 = nullptr; int nsh0 = 0, nsh1 = 0;   // slots with >= 2 contributors: the only ones pass 2 visits
     bool direct = false;
@@ -167,7 +175,6 @@ struct mimsem_ctx {
     double col_param = 0.0;             // scalar argument of the *_ex column operators (dt_fric / dt)
     const double* col_uh = nullptr;     // horizontal velocity [nk][n1] of the *_up column operators
     long long col_uhs = 0;
-    long long bytes = 0;
     int swz = 1;                   // MIMSEM_NOSWZ=1 disables the XCD-aware block order (tuning)
     int lch_override = 0;          // MIMSEM_LCH environment override (tuning)
     // measurement hook: event triples (start, mid, end) around pass 1 / pass 2 of mimsem_op_apply
@@ -181,15 +188,31 @@ struct mimsem_ctx {
     std::vector<char> ev_has2;                  // per profiled apply: a second kernel recorded its pair (pooled events keep OLD stamps otherwise)
     void mark_k2() { if (ev_k2[0] && !ev_has2.empty()) ev_has2.back() = 1; }
 
-    std::vector<void*> retired;          // outgrown workspaces (still referenced by captured graphs), freed with the context
+    // ---- device memory: ONE owner.  Everything the context allocates comes from alloc() and is freed by mimsem_ctx_destroy from `owned`;
+    // `bytes` (mimsem_ctx_workspace_bytes) is the sum of what is in the list.  A buffer that is outgrown or replaced is RETIRED: the context
+    // stops naming it and nothing else happens -- a hipGraph captured earlier has its address baked into kernel arguments and must keep
+    // working on it.  release() is for the few buffers no recording can hold.
+    std::vector<std::pair<void*, size_t>> owned;
+    long long bytes = 0;
+    int alloc(void** p, size_t nbytes, Mem kind = Mem::Plain);      // at least one byte; *p is written on success only
+    // alloc's book-keeping.  Its one other caller is mimsem_ksp::ensure (ksp.hip), which retires the handle's outgrown workspace to the context
+    void adopt(void* p, size_t nbytes) { owned.emplace_back(p, nbytes); bytes += (long long)nbytes; }
+    void release(void* p);                                          // frees p and drops it from the list (the caller has synchronised)
     bool is_capturing() const;           // the context's stream is inside a hipGraph capture (workspaces must not grow there)
-    int ensure_ye(long long doubles);
-    int ensure_col(long long doubles);
+    // workspaces only ever grow: a new buffer of `doubles` when `have` is less (MIMSEM_ERR_STATE inside a capture), the old one retired
+    int grow(double*& buf, long long& have, long long doubles, Mem kind = Mem::Plain);
+    int ensure_ye(long long n)     { return grow(d_ye, ye_doubles, n); }
+    int ensure_col(long long n)    { return grow(d_col, col_doubles, n); }
+    int ensure_cheb(long long n)   { return grow(d_cheb, cheb_doubles, n); }
+    int ensure_wsplit(long long n) { return n > wsplit_doubles && split.pending ? MIMSEM_ERR_STATE : grow(d_wsplit, wsplit_doubles, n); }
+    // UNCACHED device memory: a plain store is acknowledged by the memory side, not by the storing XCD's L2 (MIMSEM_WPART_MEM=finegrained |
+    // plain select other kinds for experiments; `plain` is NOT coherent across XCDs inside one launch)
+    int ensure_wpart(long long n)  { return grow(d_wpart, wpart_doubles, n, w_partmem == 2 ? Mem::Plain : (w_partmem == 1 ? Mem::FineGrained : Mem::Uncached)); }
+    int ensure_kry(long long n);         // ... and, once, the arrival counters of the one-launch rowdot
     int gs_fused = -1;                  // second Gram-Schmidt pass + normalisation in two launches (mimsem_krylov_gs_control; -1: from the environment)
     int* gs_flag = nullptr;             // caller's word (device or pinned host), set to 1 when that form's Pythagorean norm would cancel
     double* d_kry = nullptr;            // partial sums of the Krylov multi-dot
     long long kry_doubles = 0;
-    int ensure_kry(long long doubles);
 };
 
 // tile mode of the wave-level kernel (round 5): finishing entries per tile, doubles of a tile's LDS row, levels the LDS rows hold

@@ -133,7 +133,7 @@ struct mimsem_ksp {
             if (c->is_capturing()) return MIMSEM_ERR_STATE;
             double* nw = nullptr;                                    // the new buffer first: on failure `ws` still names a live allocation
             MIMSEM_HIP_TRY(hipMalloc((void**)&nw, (size_t)doubles*sizeof(double)));
-            if (ws) c->retired.push_back(ws);                        // (a captured graph may still hold its address: retired, not freed)
+            if (ws) c->adopt(ws, (size_t)ws_doubles*sizeof(double));  // (a captured graph may still hold its address: retired to the context, not freed)
             ws = nw; ws_doubles = doubles;
         }
         if (hostd > host_doubles) {
@@ -660,8 +660,8 @@ int mimsem_pc_edge_weights(mimsem_ctx* c, const double** dw) {
         int rc = edge_weights(c, nd, d);
         if (rc) return rc;
         double* p = nullptr;
-        MIMSEM_HIP_TRY(hipMalloc((void**)&p, std::max<size_t>(d.size(), 1)*8));
-        if (hipMemcpy(p, d.data(), d.size()*8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(p); return MIMSEM_ERR_HIP; }
+        if ((rc = c->alloc((void**)&p, d.size()*8))) return rc;
+        if (hipMemcpy(p, d.data(), d.size()*8, hipMemcpyHostToDevice) != hipSuccess) { c->release(p); return MIMSEM_ERR_HIP; }
         c->d_pcw = p;
     }
     *dw = c->d_pcw;

@@ -258,12 +258,11 @@ int owned_tables(mimsem_ctx* c, int form) {
     for (int o : owner) uncovered += o < 0;
     int4* d = nullptr;
     if (!tab.empty()) {
-        MIMSEM_HIP_TRY(hipMalloc((void**)&d, tab.size()*sizeof(int4)));
+        if (int rc = c->alloc((void**)&d, tab.size()*sizeof(int4))) return rc;
         if (hipMemcpyAsync(d, tab.data(), tab.size()*sizeof(int4), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipFree(d); return MIMSEM_ERR_HIP; }
+            hipStreamSynchronize(c->stream) != hipSuccess) { c->release(d); return MIMSEM_ERR_HIP; }
     }
     c->d_own[form] = d; c->own_uncovered[form] = uncovered;
-    c->bytes += (long long)tab.size()*sizeof(int4);
     return MIMSEM_OK;
 }
 

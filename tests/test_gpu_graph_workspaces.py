@@ -1,8 +1,9 @@
 """Regression test for the GPU fault recorded in DESIGN.md 9.0 (round 1): a hipGraph captured around engine calls has the
 addresses of the context's workspaces (d_ye: element-local results, d_col: column workspace, d_kry: Krylov partial sums) baked
 into its kernel arguments; a later call that needs a LARGER workspace used to free the old buffer, and the next replay of the
-graph faulted (MEMORY_APERTURE_VIOLATION).  Outgrown workspaces are now retired until mimsem_ctx_destroy
-(mimsem_amd/csrc/api.hip ensure_ye / ensure_col / ensure_kry), and a workspace refuses to grow while its stream is capturing.
+graph faulted (MEMORY_APERTURE_VIOLATION).  Outgrown workspaces are now retired until mimsem_ctx_destroy: the context stops naming
+them and its list of allocations keeps them (mimsem_amd/csrc/api.hip mimsem_ctx::grow, behind ensure_ye / ensure_col / ensure_kry of
+ctx.hpp), and a workspace refuses to grow while its stream is capturing.
 
 Run once per suite: capture -> grow every workspace through larger requests -> scribble -> replay -> compare with eager."""
 import numpy as np
