@@ -147,6 +147,21 @@ int  mimsem_op_wave_stats(const mimsem_ctx* ctx, int nlev, int out[5]);
  * requested parts for that form while the two-launch form of the same context (MIMSEM_WAVE_OWN=0, split applies) keeps its chunks, so the
  * two can report different numbers until part_levels is set back to 0.  Applies to the launches that follow; not inside a stream capture. */
 int  mimsem_ctx_set_wave_split(mimsem_ctx* ctx, int part_levels, int order);
+/* Balanced level ranges of the one-launch Umat form (p = 3, calls of >= 2 levels, no requested split): where the default rule's workgroups
+ * would all be resident at once (at most 3 per CU) without being a multiple of the CU count, a host planner deals wgs_per_cu x ncu
+ * workgroups whose level-pair totals differ by at most 2 pairs instead, so that every CU carries the same work.  OPT-IN: a context starts with the
+ * default rule (ncu < 0; wgs_per_cu is ignored) unless MIMSEM_WAVE_BALANCE=k, k = 1 .. 3, is set at its creation, which is ncu = 0 with
+ * wgs_per_cu = k; MIMSEM_WAVE_BALANCE=0 or unset: off.  ncu = 0: the device's multiProcessorCount, ncu > 0: a
+ * pretended chip of that many CUs, which lets a test engage the planner on a small mesh.  wgs_per_cu: 1 .. 3.  The list of a level count is
+ * planned and uploaded by the first call with that count outside a stream capture (a captured call that finds none keeps the default rule);
+ * from then on mimsem_op_wave_stats out[4] reports the longest planned item for that count.  A workgroup count the call cannot fill
+ * keeps the default rule.  Results do not depend on any of it (tests/test_gpu_wave_balance.py).  A list (16 bytes per item) is kept per
+ * (levels, groups, workgroups) for the context's life -- mimsem_ctx_set_levels, a re-plan and this call keep the lists made so far, so
+ * the context's memory grows only with the number of distinct triples.  Applies to the launches that follow; not inside a stream
+ * capture.  MIMSEM_ERR_ARG changes nothing. */
+int  mimsem_ctx_set_wave_balance(mimsem_ctx* ctx, int ncu, int wgs_per_cu);
+/* Launches on this context so far that ran from a planned list (own4::k_apply_wave_list), counted where the kernel is launched. */
+long long mimsem_ctx_wave_balance_launches(const mimsem_ctx* ctx);
 /* Interior / boundary split of a 1-form operator apply, so that a halo exchange overlaps the interior work (the
  * reference's MatMult + VecScatterBegin/End, eul/Assembly.cpp:2194-2195): tell the context once which 1-form slots take part in an
  * exchange (ghosts and mirrors of mimsem_halo_create's lists) -- the element groups touching them are moved to the front of the

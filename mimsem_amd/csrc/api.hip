@@ -6,6 +6,7 @@
 #include <climits>
 #include <cstring>
 #include "ctx.hpp"
+#include "wave_balance.hpp"
 
 namespace mimsem {
 thread_local std::string g_last_hip_error;
@@ -663,6 +664,45 @@ WaveParts wave_level_parts(const mimsem_ctx* c, int nlev, int ngroups) {
     return w;
 }
 
+// BALANCED level ranges (wave_balance.hpp): the default rule deals whole parts, wnw to a workgroup, and the workgroups land 1 or 2 to a CU
+// (864 groups x 30 levels: 432 on 256 CUs, the launch ending with the CUs that hold 120 wave-levels of a mean of 101).  Where the
+// default rule's workgroups are all resident at once (at most 3 per CU: the register bound) and are no multiple of the CU count, the
+// planner deals bal_k x CUs workgroups of equal level-pair totals instead.  Not for a requested split, single-level calls or a call
+// that does not cover all the groups of the plan (the parts of a boundary / interior apply).  Returns the number of workgroups to plan,
+// 0: the default rule.
+int wave_balance_workgroups(const mimsem_ctx* c, int nlev, int ngroups, const WaveParts& wp) {
+    if (!c->wv.own || ngroups != c->wv.ngroups) return 0;
+    const int ncu = c->bal_ncu > 0 ? c->bal_ncu : (c->bal_ncu == 0 ? c->dev_ncu : 0);
+    if (ncu < 1 || nlev < 2 || c->wave_part > 0 || c->wave_lch > 0 || c->wave_cpp > 0) return 0;
+    const int wnw = wave_workgroup_waves();
+    const long long wgs = ((long long)ngroups*wp.np + wnw - 1)/wnw;
+    if (wgs > 3LL*ncu || wgs%ncu == 0 || (long long)c->bal_k*ncu >= (1LL << 24)) return 0;
+    return c->bal_k*ncu;
+}
+// the context's list for that call, or null: none yet.  A list depends on (levels, groups, workgroups) alone -- its items name groups by
+// index -- so it outlives mimsem_ctx_set_levels, a re-plan and the setter, and the cache holds one list per triple ever asked for.
+const mimsem_ctx::BalList* wave_balance_find(const mimsem_ctx* c, int nlev, int ngroups, int nwg) {
+    for (const mimsem_ctx::BalList& b : c->bal) if (b.nlev == nlev && b.ngroups == ngroups && b.nwg == nwg) return &b;
+    return nullptr;
+}
+// ... planned and uploaded (never inside a capture: the caller has looked).  A count the planner refuses is remembered as an empty list.
+int wave_balance_make(mimsem_ctx* c, int nlev, int ngroups, int nwg, const WaveParts& wp) {
+    std::vector<mimsem::WaveItem> items;
+    mimsem_ctx::BalList b{nlev, ngroups, nwg, nullptr, 0, 0};
+    if (mimsem::plan_wave_balance(ngroups, nlev, wave_workgroup_waves(), nwg, wp.longest, items) == mimsem::WAVE_BALANCE_OK) {
+        std::vector<int4> rec(items.size());
+        for (size_t i = 0; i < items.size(); i++) {
+            rec[i] = int4{items[i].group, items[i].lev0, items[i].lev0 + items[i].nlev, 0};
+            b.longest = std::max(b.longest, items[i].nlev);
+        }
+        int4* d = nullptr;
+        if (int rc = upload(&d, rec.data(), rec.size(), c)) return rc;
+        b.items = d; b.nitems = (int)rec.size();
+    }
+    c->bal.push_back(b);
+    return MIMSEM_OK;
+}
+
 int op_spaces(int op, int* in, int* cf, int* out) {
     switch (op) {
     case MIMSEM_OP_UMAT: case MIMSEM_OP_UTMAT:   *in = 1; *cf = -1; *out = 1; return 0;
@@ -894,6 +934,14 @@ int mimsem_ctx_create(const mimsem_mesh_desc* d, int device, mimsem_ctx** out) {
 
     mimsem_ctx* c = new mimsem_ctx();
     c->device = device;
+    {   // the CUs the balanced level ranges are dealt over (wave_balance_workgroups).  The form is OPT-IN (it did not separate from the
+        // default rule on the headline step: DESIGN 4.8): MIMSEM_WAVE_BALANCE=k, k = 1 .. 3 workgroups per CU, or mimsem_ctx_set_wave_balance
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->dev_ncu = prop.multiProcessorCount;
+        const char* ev = getenv("MIMSEM_WAVE_BALANCE");
+        const int k = ev ? atoi(ev) : 0;
+        if (k >= 1 && k <= 3) { c->bal_ncu = 0; c->bal_k = k; }
+    }
     if (const char* ev = exp_env("MIMSEM_LCH")) c->lch_override = atoi(ev);
     if (const char* ev = exp_env("MIMSEM_NOSWZ")) c->swz = atoi(ev) ? 0 : 1;
     c->es = ElemSizes(d->elOrd);
@@ -1142,7 +1190,13 @@ int mimsem_op_wave_stats(const mimsem_ctx* c, int nlev, int out[5]) {
     if (!c->wv.on) return 0;
     out[0] = c->wv.ngroups; out[1] = c->wv.ndirect; out[2] = c->wv.npwritten; out[3] = c->wv.nps;
     if (c->wv.own) { out[1] = c->n1; out[2] = 0; out[3] = 0; }     // the headline operator's form: every slot written once, no partial sums
-    if (c->wv.own && c->es.n == 3 && c->wv.ntiles == 0 && !c->d_tIn) out[4] = wave_level_parts(c, nlev, c->wv.ngroups).longest;     // the longest item's levels
+    if (c->wv.own && c->es.n == 3 && c->wv.ntiles == 0 && !c->d_tIn) {
+        const WaveParts wp = wave_level_parts(c, nlev, c->wv.ngroups);
+        out[4] = wp.longest;                              // the longest item's levels: of the default rule, or of the planned list once a call has made it
+        const int nwg = c->wv.gh4 ? wave_balance_workgroups(c, nlev, c->wv.ngroups, wp) : 0;
+        const mimsem_ctx::BalList* b = nwg > 0 ? wave_balance_find(c, nlev, c->wv.ngroups, nwg) : nullptr;
+        if (b && b->items) out[4] = b->longest;
+    }
     else { const int lch = wave_level_chunk(c, nlev); out[4] = lch*wave_chunks_per_item(c, nlev, lch, c->wv.ngroups); }
     return 1;
 }
@@ -1154,6 +1208,15 @@ int mimsem_ctx_set_wave_split(mimsem_ctx* c, int part_levels, int order) {
     if (order >= 0) c->wave_order = order;
     return MIMSEM_OK;
 }
+
+int mimsem_ctx_set_wave_balance(mimsem_ctx* c, int ncu, int wgs_per_cu) {
+    if (!c || ncu > (1 << 20) || (ncu >= 0 && (wgs_per_cu < 1 || wgs_per_cu > 3))) return MIMSEM_ERR_ARG;
+    if (c->is_capturing()) return MIMSEM_ERR_STATE;
+    c->bal_ncu = ncu < 0 ? -1 : ncu;
+    if (ncu >= 0) c->bal_k = wgs_per_cu;
+    return MIMSEM_OK;                                     // (the lists made so far stay: they are kept by workgroup count)
+}
+long long mimsem_ctx_wave_balance_launches(const mimsem_ctx* c) { return c ? c->bal_launches : MIMSEM_ERR_ARG; }
 
 int mimsem_ctx_set_levels(mimsem_ctx* c, const double* thick, const double* thickInv) {
     if (!c) return MIMSEM_ERR_ARG;
@@ -1456,6 +1519,14 @@ static int apply_wave1(mimsem_ctx* c, const ApplyCall& k, ElemArgs& a, bool spli
         const WaveParts wp = wave_level_parts(c, nlev, g1 - g0);
         a.wnp = wp.np; a.wpb = wp.pb; a.wpr = wp.pr;
         a.lch = nlev == 1 ? 1 : 8; a.wcpp = 1;                         // (lch only picks the instantiation: single-level calls have their own)
+        if (const int nwg = a.wgh4 ? wave_balance_workgroups(c, nlev, g1 - g0, wp) : 0) {      // balanced ranges: a planned list instead
+            const mimsem_ctx::BalList* b = wave_balance_find(c, nlev, g1 - g0, nwg);
+            if (!b && !c->is_capturing()) {               // (no upload inside a capture: such a call keeps the default rule)
+                if (int rc = wave_balance_make(c, nlev, g1 - g0, nwg, wp)) return rc;
+                b = &c->bal.back();
+            }
+            if (b && b->items) { a.witems = b->items; a.wnitems = b->nitems; }
+        }
     }
     a.swz = c->wave_order;
     if (w.ntiles > 0) {                                              // tile mode (never together with a halo split: setup_wave)

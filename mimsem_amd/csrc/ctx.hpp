@@ -138,6 +138,13 @@ struct mimsem_ctx {
     int wave2_mode = 1;                 // MIMSEM_WAVE2: 2-form-valued operators on k_apply_wave2 (p = 3): 0 none, 1 Whmat / WtQUmat / WtQdUdz, 2 also Wmat
     int wave_cpp = 0;                   // MIMSEM_WAVE_CPP override of the chunks per work item (0: heuristic)
     int wave_part = 0;                  // mimsem_ctx_set_wave_split: levels of a part of the owner form's level ranges (0: the items of the chunk form)
+    // balanced level ranges of the owner form's four-level kernel (wave_balance.hpp): one planned item list per (levels, groups,
+    // workgroups), made on the first such call outside a capture and kept for the context's life
+    int dev_ncu = 0;                    // hipDeviceProp_t::multiProcessorCount of the context's device
+    int bal_ncu = -1, bal_k = 2;        // CUs the planner deals over (< 0: off, the default; 0: the device's -- MIMSEM_WAVE_BALANCE=k) and workgroups per CU
+    struct BalList { int nlev, ngroups, nwg; const int4* items; int nitems, longest; };      // items {group, first level, end level, 0}; null: the planner refused
+    std::vector<BalList> bal;
+    long long bal_launches = 0;         // launches of own4::k_apply_wave_list so far (mimsem_ctx_wave_balance_launches)
     int w_partmem = 0;                  // memory kind of d_wpart: 0 uncached, 1 fine-grained, 2 plain (MIMSEM_WPART_MEM, experiments)
     double* d_wpart = nullptr;          // [nlev][wv.npart + 128] partial sums of the finishing phase: UNCACHED device memory (plain stores go
     long long wpart_doubles = 0;        //   through to the memory side: visible to a finishing wave on another XCD once acknowledged)
@@ -258,6 +265,12 @@ struct ElemArgs {
     const int *d0, *d1x, *d1y;       // [nEl][n0e|n1e]: the slot when the element is its only contributor, else -1 (null = off)
     int lstep = 1;                   // geometry level of row r: lev0 + r lstep; 0 = every row at lev0 (mimsem_op_apply_levels, k_elem_apply only)
     const int4* wgh4 = nullptr;      // owner-computes form: ghost lanes of the four-level pass (build_wave_own), or null: the pass per batch
+    // ... its planned items (wave_balance.hpp), four consecutive ones a workgroup: {group, first level, end level, 0}; null: wnp, wpb, wpr
+    const int4* witems = nullptr; int wnitems = 0;
+    // KNOWN SENSITIVITY: the wave kernels' prologues wait for a handful of these fields by scalar loads, and how the compiler groups those
+    // loads depends on the fields' offsets -- adding the two above moved the headline step by -0.27 us, a prologue with the loads behind
+    // a branch by +0.5 us.  After a change to this struct, look at the first waits of own4::k_apply_wave in the assembly
+    // (one s_waitcnt before the exit test) and measure the loop of profiles/umat_balance_ab.txt.
 };
 
 // The vector update a Chebyshev step still owes (mimsem_block_chebyshev_solve: the gather epilogue of step k folded into the element pass of
@@ -302,6 +315,7 @@ int launch_elem_apply_pending(mimsem_ctx* c, const ElemArgs& a, const ElemPendin
 int launch_gather_perim(mimsem_ctx* c, int nlev, const double* yp, long long yps, int accum, double* y, long long ys,
                         const int* pslot = nullptr, const int* ppart = nullptr, int nps = -1);
 int launch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a);
+int wave_workgroup_waves();          // wavefronts per workgroup of the wave-level kernels
 int launch_apply_wave2(mimsem_ctx* c, int op, const ElemArgs& a);
 int launch_wave_perim(mimsem_ctx* c, int nlev, const double* yp, long long yps, int accum, double* y, long long ys, int r0 = 0, int r1 = -1);
 int launch_gather_sum(mimsem_ctx* c, int form, int nlev, const double* ye, long long ye_stride, int accum,

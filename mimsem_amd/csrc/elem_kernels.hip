@@ -1675,12 +1675,16 @@ int launch_gather_perim(mimsem_ctx* c, int nlev, const double* yp, long long yps
     return MIMSEM_OK;
 }
 
+int wave_workgroup_waves() { return WNW; }
 // the wave-level fused form of the 1-form -> 1-form operators (elem_wave.inc): one wavefront per (wave-group, level chunk)
 template <int N>
 static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     const int nch = (a.nlev + a.lch - 1)/a.lch;
-    if (a.wnp > 0 && (a.wtfin || a.wfin || a.wpb < 1 || a.wpr < 0 || a.wpr >= a.wnp || 2*(a.wnp*a.wpb + a.wpr) < a.nlev)) return MIMSEM_ERR_ARG;   // level ranges cover the call; not for the tile / finishing forms
-    const long long items = (long long)a.wgroups*(a.wnp > 0 ? a.wnp : (nch + a.wcpp - 1)/a.wcpp);
+    if (a.wnp > 0 && !a.witems && (a.wtfin || a.wfin || a.wpb < 1 || a.wpr < 0 || a.wpr >= a.wnp || 2*(a.wnp*a.wpb + a.wpr) < a.nlev)) return MIMSEM_ERR_ARG;   // level ranges cover the call; not for the tile / finishing forms
+    // a planned item list (wave_balance.hpp; the four-level owner kernel alone) sizes the grid itself: the planner has proved its coverage
+    const bool listed = a.witems != nullptr;
+    if (listed && (a.wnitems < 1 || !a.wgh || !a.wgh4 || a.lch != WLC || a.wg0 != 0 || N != 3 || MIMSEM_WLB != 2 || MIMSEM_WAHEAD != 2)) return MIMSEM_ERR_ARG;
+    const long long items = listed ? (long long)a.wnitems : (long long)a.wgroups*(a.wnp > 0 ? a.wnp : (nch + a.wcpp - 1)/a.wcpp);
     if (items >= (1LL << 31)) return MIMSEM_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)((items + WNW - 1)/WNW);
     if (grid == 0) return MIMSEM_OK;
@@ -1691,10 +1695,12 @@ static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     if (own && (N != 3 || op != MIMSEM_OP_UMAT || tile || a.wnp < 1)) return MIMSEM_ERR_STATE;
     if constexpr (N == 3 && MIMSEM_WLB == 2 && MIMSEM_WAHEAD == 2) {      // (the A/B builds of those two knobs keep the form below)
         if (own && a.wgh4 && a.lch == WLC) {             // the ghost pass per four levels (single-level calls keep the form below)
-#define MIMSEM_WL4(ACC) \
-            if (c->ev_k1[0]) hipExtLaunchKernelGGL((own4::k_apply_wave<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
-            else hipLaunchKernelGGL((own4::k_apply_wave<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, a)
-            if (a.accum) { MIMSEM_WL4(true); } else { MIMSEM_WL4(false); }
+#define MIMSEM_WL4(K, ACC) \
+            if (c->ev_k1[0]) hipExtLaunchKernelGGL((own4::K<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
+            else hipLaunchKernelGGL((own4::K<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, a)
+            if (listed) c->bal_launches++;
+            if (listed) { if (a.accum) { MIMSEM_WL4(k_apply_wave_list, true); } else { MIMSEM_WL4(k_apply_wave_list, false); } }
+            else        { if (a.accum) { MIMSEM_WL4(k_apply_wave, true); } else { MIMSEM_WL4(k_apply_wave, false); } }
 #undef MIMSEM_WL4
             MIMSEM_HIP_TRY(hipGetLastError());
             return MIMSEM_OK;

@@ -590,8 +590,10 @@ levels_done: ;
 // item with an odd number of batches runs its last pass half empty, on the clamped loads of the batch it does not have.  Everything
 // else -- the element's algebra, the level pipeline, the stores, the exits -- is the kernel above, written out for its one case.
 namespace own4 {
-template <int N, int OP, int LCT, bool ACCUM>
-__global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_apply_wave(ElemArgs a) {
+// LIST: the item is read from the planned list a.witems (wave_balance.hpp: balanced level ranges) -- its own entry point,
+// k_apply_wave_list, so that the kernel of the default rule keeps its prologue of one wait for the kernel arguments.
+template <int N, int OP, int LCT, bool ACCUM, bool LIST>
+__device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
     using D = Dims<N>;
     static_assert(N == 3 && OP == MIMSEM_OP_UMAT && LCT == 8 && MIMSEM_WLB == 2 && MIMSEM_WAHEAD == 2, "owner-computes Umat at p = 3, rings of four batches of two levels");
     constexpr int LPE = D::LPE, EPW = 64/LPE, ND = 2*D::n1e, NW = WNW;
@@ -610,16 +612,27 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) 
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & 63, el = lane/LPE, q = lane%LPE;
     const unsigned nchunk = (unsigned)a.wnp;
-    const unsigned nitems = (unsigned)a.wgroups*nchunk;
+    const unsigned nitems = LIST ? (unsigned)a.wnitems : (unsigned)a.wgroups*nchunk;
     const unsigned bid = xcd_swizzle(blockIdx.x, gridDim.x, a.swz & 1);
     const unsigned item = bid*NW + (unsigned)wv;
+    const int4* const wit = a.witems;
+    if constexpr (LIST) asm volatile("" :: "s"(wit));    // (the list's address arrives with the other kernel arguments, not behind the exit below)
     if (item >= nitems) return;                          // wave-uniform
-    unsigned g, ch;
-    if (a.swz & 2) { g = item/nchunk; ch = item%nchunk; }
-    else           { g = item%(unsigned)a.wgroups; ch = item/(unsigned)a.wgroups; }
-    g += (unsigned)a.wg0;
-    int lbeg = 2*((int)ch*a.wpb + min((int)ch, a.wpr));
-    const int lend = min(a.nlev, lbeg + 2*(a.wpb + ((int)ch < a.wpr ? 1 : 0)));
+    unsigned g;
+    int lbeg, lend_;
+    if constexpr (LIST) {                                // a planned item {group, first level, end level, 0}: its first three ints, by scalar loads
+        typedef const __attribute__((address_space(4))) int cint;        // (constant address space: a scalar load whatever stands before it)
+        cint* const it = (cint*)(unsigned long long)(wit + item);
+        g = (unsigned)it[0]; lbeg = it[1]; lend_ = it[2];
+    } else {
+        unsigned ch;
+        if (a.swz & 2) { g = item/nchunk; ch = item%nchunk; }
+        else           { g = item%(unsigned)a.wgroups; ch = item/(unsigned)a.wgroups; }
+        g += (unsigned)a.wg0;
+        lbeg = 2*((int)ch*a.wpb + min((int)ch, a.wpr));
+        lend_ = min(a.nlev, lbeg + 2*(a.wpb + ((int)ch < a.wpr ? 1 : 0)));
+    }
+    const int lend = lend_;
     const int4 wl = a.wlane[(size_t)g*64 + lane];
     const int4 wp = a.wplan[(size_t)g*64 + lane];
     const int4 gh = a.wgh4[(size_t)g*64 + lane];
@@ -779,6 +792,10 @@ __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) 
     }
     }
 }
+template <int N, int OP, int LCT, bool ACCUM>
+__global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_apply_wave(ElemArgs a) { apply_wave_body<N, OP, LCT, ACCUM, false>(a); }
+template <int N, int OP, int LCT, bool ACCUM>
+__global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_apply_wave_list(ElemArgs a) { apply_wave_body<N, OP, LCT, ACCUM, true>(a); }
 }  // namespace own4
 
 // k_apply_wave2<OP, LCT, ACCUM>: the 2-form-valued operators at p = 3 -- Wmat, Whmat (2-form in), WtQUmat, WtQdUdz_mat (1-form in, 1-form

@@ -188,6 +188,12 @@ class Engine:
         """0 = off; n > 0 = time every n-th op_apply with hipExtLaunchKernelGGL start/stop events"""
         check(self.L.mimsem_ctx_set_profiling(self.ctx, int(every)), "set_profiling")
 
+    def set_wave_balance(self, ncu=0, wgs_per_cu=2):
+        """balanced level ranges of the one-launch Umat form: deal wgs_per_cu x ncu workgroups of equal work (ncu = 0: the device's CUs,
+        < 0: off, > 0: a pretended chip); mimsem_ctx_set_wave_balance"""
+        _need(int(ncu) < 0 or 1 <= int(wgs_per_cu) <= 3, "set_wave_balance: 1 .. 3 workgroups per CU")
+        check(self.L.mimsem_ctx_set_wave_balance(self.ctx, int(ncu), int(wgs_per_cu)), "set_wave_balance")
+
     def profile_read(self):
         """(ms in element kernels, ms in gather-sum kernels, launches) since the last read"""
         a, b, n = C.c_double(), C.c_double(), C.c_longlong()
