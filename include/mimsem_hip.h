@@ -15,6 +15,17 @@
  * "dev" pointers are device (HBM) addresses (hipMalloc / torch tensor data_ptr / mimsem_malloc);
  * "host" pointers are ordinary memory.  Vectors follow the PETSc layout the reference reads through
  * VecGetArray: contiguous doubles; a multi-level field is addressed as base + k*lev_stride.
+ * Strides: every operand of a call has a stride argument of its own (named *_stride or ld*, in doubles) and the strides of one call
+ * are independent of each other: each may be any value >= the operand's row length, or 0 where the entry says that one row serves
+ * every level (f0_stride of the shallow-water operator, blocks_level_stride, u_stride of exner_s, ...).  Two operands share a stride
+ * only where the signature has one argument for both (ldu of velx1 / velx2, v_stride of the Chebyshev chain).  Alignment: a base
+ * address and a stride need be multiples of 8 bytes (one double) only -- bases and strides that are not multiples of 16 bytes are
+ * supported by every entry, the wave-level kernels with their paired loads and stores included (ordinary global accesses; an odd
+ * stride may cost bandwidth, not correctness).  The result of a call depends on its sizes, levels and plan alone: rows placed at
+ * other strides or bases give the same bits.  tests/test_gpu_abi_strides.py holds every strided entry to this -- distinct even and
+ * distinct odd strides per operand against the contiguous call, bit for bit, with guarded padding around every row -- and
+ * tests/test_abi_stride_coverage.py fails when an entry with a stride argument has no case there.  Operands must not overlap unless
+ * an entry allows it.
  * Every function returns 0 on success or a negative MIMSEM_ERR_* code (the reference itself has no
  * error convention: PETSc codes are ignored and Inv's error int is dropped, eul/VertOps.cpp:434).
  * Launches are asynchronous on the context's stream; nothing here synchronises unless it says so.
