@@ -771,7 +771,8 @@ typedef struct mimsem_ksp mimsem_ksp;
 enum mimsem_ksp_type { MIMSEM_KSP_CG = 0, MIMSEM_KSP_GMRES = 1 };
 enum mimsem_ksp_reason {                        /* KSPConvergedReason, the values PETSc uses */
     MIMSEM_KSP_CONVERGED_RTOL = 2, MIMSEM_KSP_CONVERGED_ATOL = 3, MIMSEM_KSP_CONVERGED_ITS = 4,
-    MIMSEM_KSP_DIVERGED_ITS = -3, MIMSEM_KSP_DIVERGED_BREAKDOWN = -5, MIMSEM_KSP_DIVERGED_NANORINF = -9 };
+    MIMSEM_KSP_DIVERGED_ITS = -3, MIMSEM_KSP_DIVERGED_BREAKDOWN = -5, MIMSEM_KSP_DIVERGED_NANORINF = -9,
+    MIMSEM_KSP_FIXED_ITS = 100 };               /* not PETSc's: a fixed-length solve (mimsem_ksp_set_fixed_iterations), not monitored */
 typedef int (*mimsem_ksp_apply_fn)(void* user, int nlev, const double* x, long long x_stride, double* y, long long y_stride);
 int  mimsem_ksp_create(mimsem_ctx* ctx, int type, mimsem_ksp** out);                       /* KSPCreate + KSPSetType            */
 void mimsem_ksp_destroy(mimsem_ksp* ksp);                                                  /* KSPDestroy                        */
@@ -831,6 +832,20 @@ int  mimsem_ksp_set_initial_guess_nonzero(mimsem_ksp* ksp, int flag);           
 int  mimsem_ksp_solve(mimsem_ksp* ksp, const double* b, long long b_stride, double* x, long long x_stride);
 /* KSPGetIterationNumber / KSPGetResidualNorm / KSPGetConvergedReason of the last solve (rnorm: relative, worst row)                 */
 int  mimsem_ksp_get_info(const mimsem_ksp* ksp, int* iterations, double* rnorm, int* reason);
+/* A FIXED-length mode for the batched CG: what mimsem_amd/krylov.py pcg_engine(fixed_its = m) and the residual log of VortDiag._solve
+ * (mimsem_amd/vortdiag.py) are in Python -- the density-dependent interface solves of Euler::HorizPotVort and HorizSolve::diagVertVort
+ * (eul/Euler_2.cpp:1079-1092, eul/HorizSolve.cpp:843-855) without a host read.  its > 0: mimsem_ksp_solve runs exactly `its` iterations of
+ * the adaptive loop (the same calls in the same order: the bits of an adaptive solve that stops after `its` iterations) with no copy to
+ * the host, no stream synchronisation and no early exit -- an all-zero right-hand side gives x = 0 through the guarded divisions of
+ * cg_update / cg_direction --, then forms the true residual b - A x and folds |b - A x|^2 / |b|^2 of every row into `log` with
+ * mimsem_krylov_ratio_max.  log: nlev contiguous doubles on the device, owned by the caller, valid until the mode is left; NULL: no log.
+ * mimsem_ksp_get_info then reports iterations = its, rnorm = 0 and MIMSEM_KSP_FIXED_ITS.  The first solve of an object still allocates its
+ * workspace; later solves of the same shape can be recorded (mimsem_graph_begin).  its == 0: the adaptive solve again, as before.
+ * its < 0: MIMSEM_ERR_ARG; a GMRES object: MIMSEM_ERR_UNSUPPORTED.                                                                    */
+int  mimsem_ksp_set_fixed_iterations(mimsem_ksp* ksp, int its, double* log);
+/* log[i] = max(log[i], num[i] / max(den[i], 1e-300)) for nrows contiguous doubles each; a NaN on either side is kept (a NaN ratio makes
+ * log[i] NaN, a NaN log[i] stays): the check log of a fixed-length solve, read once by the host.  One launch, nothing read on the host. */
+int  mimsem_krylov_ratio_max(mimsem_ctx* ctx, int nrows, const double* num, const double* den, double* log);
 /* Eigenvalues of a real upper Hessenberg matrix H [n][n] (host, row-major, entries below the first subdiagonal ignored; n <= 400) -- the
  * host-side step of a Ritz estimate (what KSPComputeEigenvalues gets from LAPACK's hseqr in PETSc): a host that runs its own Arnoldi
  * process (a SHARDED mesh, where the inner products are all-reduced by the host: mimsem_amd/host/mimsem_sweqn.hpp) hands the small

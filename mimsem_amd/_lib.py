@@ -112,6 +112,8 @@ _SIGS = {
     "mimsem_ksp_set_initial_guess_nonzero": (C.c_int, [C.c_void_p, C.c_int]),
     "mimsem_ksp_solve": (C.c_int, [C.c_void_p, c_dp, c_ll, c_dp, c_ll]),
     "mimsem_ksp_get_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "mimsem_ksp_set_fixed_iterations": (C.c_int, [C.c_void_p, C.c_int, c_dp]),
+    "mimsem_krylov_ratio_max": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp]),
     "mimsem_colop_apply_blocks": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_dp, c_dp]),
     "mimsem_l2_transpose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_dp, c_ll, c_dp]),
     "mimsem_colop_nblocks": (C.c_int, [C.c_void_p, C.c_int]),

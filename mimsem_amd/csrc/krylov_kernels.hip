@@ -498,6 +498,26 @@ int mimsem_krylov_cg_direction(mimsem_ctx* c, int nrows, long long n, const doub
     return MIMSEM_OK;
 }
 
+// the check log of a fixed-length solve: log[i] = max(log[i], num[i] / max(den[i], 1e-300)), a NaN on either side kept (what VortDiag._solve
+// of mimsem_amd/vortdiag.py does with clamp_min, a division and torch.maximum)
+namespace {
+__global__ __launch_bounds__(256) void k_ratio_max(int nrows, const double* __restrict__ num, const double* __restrict__ den, double* __restrict__ log) {
+    const int i = blockIdx.x*256 + threadIdx.x;
+    if (i >= nrows) return;
+    const double d = den[i];
+    const double q = num[i]/(d < 1.0e-300 ? 1.0e-300 : d);           // (a NaN denominator compares false and stays)
+    const double l = log[i];
+    log[i] = (q > l || q != q) ? q : l;                               // (a NaN ratio wins, a NaN log stays)
+}
+}  // namespace
+int mimsem_krylov_ratio_max(mimsem_ctx* c, int nrows, const double* num, const double* den, double* log) {
+    if (!c || !num || !den || !log || nrows < 0 || log == num || log == den) return MIMSEM_ERR_ARG;
+    if (nrows == 0) return MIMSEM_OK;
+    hipLaunchKernelGGL(k_ratio_max, dim3((unsigned)((nrows + 255)/256)), dim3(256), 0, c->stream, nrows, num, den, log);
+    MIMSEM_HIP_TRY(hipGetLastError());
+    return MIMSEM_OK;
+}
+
 
 int mimsem_krylov_rowdot(mimsem_ctx* c, int nrows, long long n, const double* A, long long lda, const double* B, long long ldb, double* out);
 

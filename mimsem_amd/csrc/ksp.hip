@@ -5,7 +5,8 @@
 // Rounds 1-3 had these loops in Python only (mimsem_amd/krylov.py); a C++ host could reach the operator applies but nothing above
 // them.  Here the loops are library code on the context's stream, composed from the ABI's own entry points:
 //   CG     batched over the rows (one independent SPD system per level): mimsem_krylov_rowdot / cg_update / cg_direction keep the
-//          per-row scalars on the device; the host looks at |r|^2 every `check_every` iterations (one small copy);
+//          per-row scalars on the device; the host looks at |r|^2 every `check_every` iterations (one small copy) -- or, at a FIXED length
+//          (mimsem_ksp_set_fixed_iterations), never: the true residual of every row goes into a device log of the caller's;
 //   GMRES  restarted, left-preconditioned, classical Gram-Schmidt with re-orthogonalisation (mimsem_krylov_orthogonalize +
 //          mimsem_krylov_reorthonormalize_ex: four launches; MIMSEM_GS_CGS2=1: the three-launch mimsem_krylov_cgs2, measured slower),
 //          Hessenberg column through pinned host memory, Givens rotations on the host.
@@ -119,6 +120,7 @@ struct mimsem_ksp {
     mimsem_ksp_apply_fn pfn = nullptr; void* puser = nullptr;
     // controls
     double rtol = 1.0e-16, atol = 1.0e-50; int maxit = 1000, restart = 30, check_every = 2; bool guess_nonzero = false;
+    int fixed_its = 0; double* fixed_log = nullptr;          // mimsem_ksp_set_fixed_iterations (CG): > 0: that many iterations, nothing read back; the caller's log [nlev] or null
     // workspace
     double* ws = nullptr; long long ws_doubles = 0;
     double* host = nullptr; long long host_doubles = 0;      // pinned
@@ -230,6 +232,37 @@ int solve_cg(mimsem_ksp* k, const double* b, long long bs, double* x, long long 
         std::swap(rz, rz2);
     }
     return MIMSEM_OK;
+}
+
+// ---- the same loop at a FIXED length (mimsem_ksp_set_fixed_iterations): the calls of solve_cg in its order without the looks at the residual --
+// no copy to the host, no synchronisation, no early exit (a zero row: the guarded divisions of k_cg_update / k_cg_direction leave x = 0) --,
+// then the true residual of every row folded into the caller's log: pcg_engine(fixed_its = m) and the log of VortDiag._solve in Python
+int solve_cg_fixed(mimsem_ksp* k, const double* b, long long bs, double* x, long long xs) {
+    mimsem_ctx* c = k->c; const int nr = k->nlev; const long long n = k->n;
+    KTRY(k->ensure(4*nr*n + 6*(long long)nr, 2*(long long)nr));
+    double *r = k->ws, *z = r + nr*n, *p = z + nr*n, *Ap = p + nr*n, *sc = Ap + nr*n;
+    double *rz = sc, *rz2 = sc + nr, *pAp = sc + 2*nr, *rr = sc + 3*nr, *bb = sc + 4*nr;
+    if (k->guess_nonzero) { KTRY(k->A(x, xs, Ap, n)); KTRY(combine(c, nr, n, 1.0, b, bs, -1.0, Ap, n, r, n)); }
+    else { MIMSEM_HIP_TRY(hipMemset2DAsync(x, (size_t)xs*8, 0, (size_t)n*8, (size_t)nr, c->stream)); KTRY(combine(c, nr, n, 1.0, b, bs, 0.0, nullptr, 0, r, n)); }
+    k->its = k->fixed_its; k->rnorm = 0.0; k->reason = MIMSEM_KSP_FIXED_ITS;
+    KTRY(k->P(r, n, z, n));
+    KTRY(combine(c, nr, n, 1.0, z, n, 0.0, nullptr, 0, p, n));
+    KTRY(mimsem_krylov_rowdot(c, nr, n, r, n, z, n, rz));
+    for (int it = 0; it < k->fixed_its; it++) {
+        KTRY(k->A(p, n, Ap, n));
+        KTRY(mimsem_krylov_rowdot(c, nr, n, p, n, Ap, n, pAp));
+        KTRY(mimsem_krylov_cg_update(c, nr, n, rz, pAp, p, n, Ap, n, x, xs, r, n));
+        KTRY(k->P(r, n, z, n));
+        KTRY(mimsem_krylov_rowdot(c, nr, n, r, n, z, n, rz2));
+        KTRY(mimsem_krylov_cg_direction(c, nr, n, rz2, rz, z, n, p, n));
+        std::swap(rz, rz2);
+    }
+    if (!k->fixed_log) return MIMSEM_OK;
+    KTRY(k->A(x, xs, Ap, n));
+    KTRY(combine(c, nr, n, 1.0, b, bs, -1.0, Ap, n, r, n));
+    KTRY(mimsem_krylov_rowdot(c, nr, n, r, n, r, n, rr));
+    KTRY(mimsem_krylov_rowdot(c, nr, n, b, bs, b, bs, bb));
+    return mimsem_krylov_ratio_max(c, nr, rr, bb, k->fixed_log);
 }
 
 // ---- restarted left-preconditioned GMRES on the rows taken as ONE vector ---------------------------------------------------------------
@@ -570,7 +603,14 @@ int mimsem_ksp_solve(mimsem_ksp* k, const double* b, long long bs, double* x, lo
         const long long want = k->bform == 0 ? k->c->n0 : (k->bform == 1 ? k->c->n1 : k->c->n2);
         if (want != k->n) return MIMSEM_ERR_ARG;
     }
+    if (k->type == MIMSEM_KSP_CG && k->fixed_its > 0) return solve_cg_fixed(k, b, bs, x, xs);
     return k->type == MIMSEM_KSP_CG ? solve_cg(k, b, bs, x, xs) : solve_gmres(k, b, bs, x, xs);
+}
+int mimsem_ksp_set_fixed_iterations(mimsem_ksp* k, int its, double* log) {
+    if (!k || its < 0) return MIMSEM_ERR_ARG;
+    if (k->type != MIMSEM_KSP_CG) return MIMSEM_ERR_UNSUPPORTED;
+    k->fixed_its = its; k->fixed_log = its > 0 ? log : nullptr;
+    return MIMSEM_OK;
 }
 // ---- round 5: what a host needs to run FIXED-LENGTH (Chebyshev) solves itself: the blocks PCSetUp built, and the region of the spectrum ----
 int mimsem_ksp_get_pc_blocks(const mimsem_ksp* k, const double** blocks, const double** elem_scale, int* nd) {

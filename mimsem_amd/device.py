@@ -1077,6 +1077,14 @@ class Engine:
         check(self.L.mimsem_krylov_cg_direction(self.ctx, nrows, n, self._vec(num, nrows, "num", atleast=True), self._vec(den, nrows, "den", atleast=True),
                                                 *pz, *pp), "cg_direction")
 
+    def ratio_max(self, num, den, log):
+        """log[i] = max(log[i], num[i] / max(den[i], 1e-300)), a NaN on either side kept: the check log of a fixed-length solve, in place
+        (one launch: mimsem_krylov_ratio_max)"""
+        nrows = log.numel()
+        check(self.L.mimsem_krylov_ratio_max(self.ctx, nrows, self._vec(num, nrows, "num"), self._vec(den, nrows, "den"), self._vec(log, nrows, "log")),
+              "ratio_max")
+        return log
+
     def combine(self, a, alpha=1.0, op=None, b=None, beta=0.0, c=None, out=None):
         """out = alpha * (a, a*b or a/b) + beta * c, row by row ([nrows, n] tensors whose rows are contiguous; slices along the first
         dimension are fine); out may be a or c (mimsem_vec_combine)"""

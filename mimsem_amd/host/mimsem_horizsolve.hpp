@@ -81,6 +81,11 @@ public:
         log.rewind(); fixed_length = true;
     }
     void shorten_for_test(int steps) { m1.shorten(steps); }      // (tests: a solve that must miss its check)
+    // for a host that solves with a matrix close to M1 on the same blocks and logs into the same checks (mimsem_euler.hpp: HorizMomentum's
+    // M1 + M1ray under Held-Suarez forcing): the object PCSetUp built, the fixed-length solver with its blocks and pair arrays, the log
+    mimsem_ksp* mass_ksp() const { return ksp1; }
+    FixedMassSolve& mass_solver() { return m1; }
+    CheckLog& check_log() { return log; }
     // after mimsem_ctx_set_levels (new layer thicknesses): the element blocks and the per-(level, element) factors of the preconditioner and
     // the spectral interval belong to the old ones
     void levels_changed() {

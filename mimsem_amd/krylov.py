@@ -19,7 +19,7 @@ class KSP:
     """mimsem_ksp_* of the C ABI (round 4, csrc/ksp.hip): the solve loops as library code -- the object a C++ host uses in place of
     PETSc's KSP (mimsem_amd/host/mimsem_shim.hpp: KSP).  Python callers reach the same loops through this wrapper: one code path.
     type "cg" (batched over the rows: one SPD system per level) | "gmres" (restarted, left-preconditioned, the rows as one vector)."""
-    REASONS = {2: "rtol", 3: "atol", 4: "its", -3: "diverged_its", -5: "breakdown", -9: "nan_or_inf", 0: "none"}
+    REASONS = {2: "rtol", 3: "atol", 4: "its", -3: "diverged_its", -5: "breakdown", -9: "nan_or_inf", 0: "none", 100: "fixed_its"}
 
     def __init__(self, eng, ksp_type="gmres"):
         import ctypes as C
@@ -42,6 +42,7 @@ class KSP:
     def set_operator(self, op, nlev, lev0=0, scale=1.0, flags=0, f=None):
         from .device import OPS, _ptr
         self._keep.append(f)
+        self._nlev = nlev
         self._check(self.eng.L.mimsem_ksp_set_operator(self.h, OPS[op], lev0, nlev, scale, flags, _ptr(f), f.stride(0) if f is not None else 0),
                     "ksp_set_operator")
         return self
@@ -49,6 +50,7 @@ class KSP:
     def set_operator_sw(self, nlev, a, grav, H, f0):
         from .device import _ptr
         self._keep.append(f0)
+        self._nlev = nlev
         self._check(self.eng.L.mimsem_ksp_set_operator_sw(self.h, nlev, a, grav, H, _ptr(f0), f0.stride(0) if f0.dim() > 1 and f0.shape[0] > 1 else 0),
                     "ksp_set_operator_sw")
         return self
@@ -78,6 +80,14 @@ class KSP:
 
     def set_tolerances(self, rtol=1e-16, atol=1e-50, maxit=1000, restart=30, check_every=2):
         self._check(self.eng.L.mimsem_ksp_set_tolerances(self.h, rtol, atol, maxit, restart, check_every), "ksp_set_tolerances")
+        return self
+
+    def set_fixed_iterations(self, its, log=None):
+        """mimsem_ksp_set_fixed_iterations ("cg" only): its > 0: every solve runs exactly `its` iterations and reads nothing back; log
+        (optional): [nlev] float64 on the device that collects max |b - A x|^2 / |b|^2 per row.  its = 0: the adaptive solve again"""
+        self._log = log
+        self._check(self.eng.L.mimsem_ksp_set_fixed_iterations(self.h, its, None if log is None else self.eng._vec(log, getattr(self, "_nlev", None), "log")),
+                    "ksp_set_fixed_iterations")
         return self
 
     def solve(self, b, x=None, guess_nonzero=False):

@@ -39,6 +39,8 @@ def parse(argv):
     ap.add_argument("--hs-forcing", action="store_true", help="Held-Suarez friction and temperature forcing (Euler's hs_forcing)")
     ap.add_argument("--patches", type=int, default=0, help="patches of the mesh (default: 24 for an even ne >= 8, else 6)")
     ap.add_argument("--profile", default=None, help="write the summary to this file as well")
+    ap.add_argument("--write-case", default=None, metavar="PATH",
+                    help="write the initial state as a case for the C++ host (mimsem_amd/host/euler_call.cpp, workloads.write_euler_case) and stop")
     ap.add_argument("--time-limit", type=float, default=1200.0)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
@@ -78,6 +80,12 @@ def work(a):
     torch.cuda.synchronize()
     t_init = time.perf_counter() - t0
     print("mesh, engine and %s: %.1f s (init1 solves redone: %d)" % ("restart" if a.start_step else "initial state", t_init, eu.init1_redone), flush=True)
+
+    if a.write_case:
+        from mimsem_amd.workloads import write_euler_case
+        write_euler_case(a.write_case, eng.mesh, um.levels(a.nk, xq), xq, state, a.dt, a.nsteps, hs_lat=hs_lat, newton_maxit=a.newton_maxit, eng=eng)
+        print("case for the C++ host written to %s" % a.write_case, flush=True)
+        return 0
 
     ms, dump_ms, newton, lines = [], [], [], []
 
