@@ -8,11 +8,38 @@ on the device: no host synchronisation inside the iteration).  Mat-vecs are the 
 import math
 import os
 
+import numpy as np
 import torch
 
 from ._switches import experiment
 
+from .checks import CheckLog, accepted, interval_rate, interval_steps, rate_steps
 from .device import no_gc
+
+
+def seeded_randn(shape, seed, device):
+    """the random right-hand side of a spectral estimate: drawn by the CPU generator (the same numbers whatever the device), then moved"""
+    g = torch.Generator(device="cpu"); g.manual_seed(seed)
+    return torch.randn(shape, generator=g, dtype=torch.float64).to(device)
+
+
+def edge_sharing_weights(eng):
+    """D_e = 1 / (number of elements sharing the edge) for the 2 n1e edges of every element, [nEl, 2 n1e]; sharded: sharers on other ranks count too"""
+    idx = torch.cat([torch.as_tensor(eng.mesh.inds1x, device=eng.device), torch.as_tensor(eng.mesh.inds1y, device=eng.device)], dim=1).long()
+    mult = torch.zeros(1, eng.sizes[1], dtype=torch.float64, device=eng.device)
+    mult[0].index_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.float64, device=eng.device))
+    return 1.0 / eng.complete(1, mult)[0][idx]
+
+
+def element_block_preconditioner(eng, em, d=None):
+    """element-block preconditioner of a 1-form mass matrix (the reference: PCBJACOBI with one block per element, src/SWEqn_Picard.cpp:88-90):
+    P^-1 = sum_e R_e^T D_e (M_e)^-1 D_e R_e -- cond(P^-1 M1) ~ 1.2.  em: the operator's element matrices ([nEl, 4 n1e^2], the four quadrants in
+    turn); d: edge_sharing_weights(eng) when the caller keeps them (an operator whose blocks are rebuilt per solve)"""
+    n1e = eng.n1e
+    B = em.view(eng.nEl, 2, 2, n1e, n1e).permute(0, 1, 3, 2, 4).reshape(eng.nEl, 2 * n1e, 2 * n1e)        # [[UtQU, UtQV], [VtQU, VtQV]]
+    d = edge_sharing_weights(eng) if d is None else d
+    Binv = getattr(eng, "eng", eng).block_inverse(B)          # the library's batched Gauss-Jordan
+    return (d[:, :, None] * Binv * d[:, None, :]).contiguous()
 
 
 class KSP:
@@ -118,35 +145,30 @@ class KSP:
         return b.value, e.value, nd.value
 
 
-def pcg(apply_A, b, minv=None, x0=None, rtol=1e-14, maxit=300, check_every=10, allreduce=None, precond=None):
-    """Solve A x = b for a batch of systems (rows of b).  apply_A(x)->A x on [nlev, n] tensors.
-    minv: elementwise preconditioner (Jacobi) of the same shape, or precond(r)->z (symmetric positive definite).
-    allreduce(t): sums per-level scalars over ranks (multi-GPU: each rank holds ghost copies, the caller's dot
-    weights handle ownership)."""
-    if precond is not None:
-        return _pcg_general(apply_A, b, precond, x0, rtol, maxit, check_every, allreduce)
-    x = torch.zeros_like(b) if x0 is None else x0.clone()
-    r = b - apply_A(x) if x0 is not None else b.clone()
-    z = r * minv if minv is not None else r
+def pcg(apply_A, b, precond, rtol=1e-14, maxit=300, check_every=10):
+    """Solve A x = b for a batch of SPD systems (rows of b) in torch ops.  apply_A(x)->A x on [nlev, n] tensors; precond(r)->z, symmetric
+    positive definite (a Jacobi scaling: lambda r: r * minv).  The adaptive fall-back of MassSolver where the engine loops do not apply;
+    the only host synchronisation is the convergence test every `check_every` iterations."""
+    x = torch.zeros_like(b)
+    r = b.clone()
+    z = precond(r)
     p = z.clone()
-    dot = (lambda u, v: (u * v).sum(dim=1)) if allreduce is None else (lambda u, v: allreduce((u * v).sum(dim=1)))
+    dot = lambda u, v: torch.linalg.vecdot(u, v, dim=1)
     rz = dot(r, z)
     bnorm = torch.sqrt(dot(b, b)).clamp_min(1e-300)
     its = 0
     for it in range(maxit):
         Ap = apply_A(p)
         alpha = rz / dot(p, Ap).clamp_min(1e-300)
-        x += alpha[:, None] * p
-        r -= alpha[:, None] * Ap
-        z = r * minv if minv is not None else r
-        rz_new = dot(r, z)
-        beta = rz_new / rz.clamp_min(1e-300)
-        p = z + beta[:, None] * p
-        rz = rz_new
+        torch.addcmul(x, alpha[:, None], p, out=x)
+        torch.addcmul(r, alpha[:, None], Ap, value=-1.0, out=r)
         its = it + 1
-        if its % check_every == 0:                    # the only host synchronisation
-            if bool((torch.sqrt(dot(r, r)) / bnorm).max() < rtol):
-                break
+        if its % check_every == 0 and bool((torch.sqrt(dot(r, r)) / bnorm).max() < rtol):
+            break
+        z = precond(r)
+        rz_new = dot(r, z)
+        p = torch.addcmul(z, (rz_new / rz.clamp_min(1e-300))[:, None], p)
+        rz = rz_new
     return x, its
 
 
@@ -179,53 +201,6 @@ def pcg_engine(eng, apply_A, b, precond, rtol=1e-14, maxit=300, check_every=2, f
     return x, its
 
 
-def pcg_fixed(apply_A, b, precond, iterations):
-    """PCG with a FIXED iteration count and no host synchronisation: capturable in a hipGraph.  For the element-block
-    preconditioned mass systems (condition ~1.2, error contraction ~0.05 per iteration) 14 iterations reach round-off."""
-    x = torch.zeros_like(b)
-    r = b.clone()
-    z = precond(r)
-    p = z.clone()
-    dot = lambda u, v: torch.linalg.vecdot(u, v, dim=1)
-    rz = dot(r, z)
-    tiny = 1e-300
-    for _ in range(iterations):
-        Ap = apply_A(p)
-        alpha = rz / dot(p, Ap).clamp_min(tiny)
-        torch.addcmul(x, alpha[:, None], p, out=x)
-        torch.addcmul(r, alpha[:, None], Ap, value=-1.0, out=r)
-        z = precond(r)
-        rz_new = dot(r, z)
-        p = torch.addcmul(z, (rz_new / rz.clamp_min(tiny))[:, None], p)
-        rz = rz_new
-    return x
-
-
-def _pcg_general(apply_A, b, precond, x0, rtol, maxit, check_every, allreduce):
-    x = torch.zeros_like(b) if x0 is None else x0.clone()
-    r = b - apply_A(x) if x0 is not None else b.clone()
-    z = precond(r)
-    p = z.clone()
-    vd = lambda u, v: torch.linalg.vecdot(u, v, dim=1)
-    dot = vd if allreduce is None else (lambda u, v: allreduce(vd(u, v)))
-    rz = dot(r, z)
-    bnorm = torch.sqrt(dot(b, b)).clamp_min(1e-300)
-    its = 0
-    for it in range(maxit):
-        Ap = apply_A(p)
-        alpha = rz / dot(p, Ap).clamp_min(1e-300)
-        torch.addcmul(x, alpha[:, None], p, out=x)
-        torch.addcmul(r, alpha[:, None], Ap, value=-1.0, out=r)
-        its = it + 1
-        if its % check_every == 0 and bool((torch.sqrt(dot(r, r)) / bnorm).max() < rtol):
-            break
-        z = precond(r)
-        rz_new = dot(r, z)
-        p = torch.addcmul(z, (rz_new / rz.clamp_min(1e-300))[:, None], p)
-        rz = rz_new
-    return x, its
-
-
 K_F = 1.1574074074074073e-05       # the largest Held-Suarez friction rate k_v can take (1/day; compute_k_v, eul/Assembly.cpp:1846-1856)
 
 
@@ -250,25 +225,28 @@ class MassSolver:
         self.eng, self.scale, self.flags = eng, scale, 1 if vert_scale else 0
         n1e = eng.n1e
         dm = eng.mesh
-        ix = torch.as_tensor(dm.inds1x, device=eng.device).long()
-        iy = torch.as_tensor(dm.inds1y, device=eng.device).long()
         self.kind = precond
         self.fixed_its = 0          # > 0: run exactly that many PCG iterations (hipGraph capture)
         self._cheb = None
         self._cheb_fric = {}        # tau -> the fixed-length solver of M1 + M1ray(tau) (solve_fric)
         self._cheb_checked = False
+        self._cheb_cal = None       # what the calibrated step count was calibrated on
+        self._bt = None
+        self._ksp_key = None
         # every fixed-length solve logs {|P r_last|^2, |P b|^2} per level into a slot of this device log (round 6: round 5 verified the first
-        # solve only; a later, rougher right-hand side could lose accuracy unseen): verify() reads it once per evaluation / step
-        self.MAXLOG = 16
-        self._log = None
-        self._slot = 0
+        # solve only; a later, rougher right-hand side could lose accuracy unseen): verify() reads it once per evaluation / step.  Made on
+        # the first such solve (one slot holds the levels of a solve); solves past its 16 slots share the last one
+        self.check_log = None
         self.solves_checked = self.solves_missed = 0
+        self.solves_unchecked = 0   # solves whose check norms a later solve overwrote in the full log before verify() read them
         self.worst_check = 0.0
         # default solver for the block preconditioner on one rank: fixed-length Chebyshev on the fused sweep (no inner products)
         # (round 6: also over a halo -- a DistEngine has the sweep with its two exchanges inside, no inner product: no all-reduce in the solve)
         self.dist = hasattr(eng, "halo")
         self.chebyshev = (precond != "jacobi" and os.environ.get("MIMSEM_MASS_SOLVER", "chebyshev") == "chebyshev" and eng.mesh.n <= 5)
         if precond == "jacobi":
+            ix = torch.as_tensor(dm.inds1x, device=eng.device).long()
+            iy = torch.as_tensor(dm.inds1y, device=eng.device).long()
             diag = eng.zeros(eng.nk, dm.n1)
             for k in range(eng.nk):
                 em = eng.element_matrices("UMAT", lev=k, scale=scale, flags=self.flags).view(eng.nEl, 4, n1e, n1e)
@@ -284,17 +262,11 @@ class MassSolver:
             ob = eng.owned_blocks("UMAT", lev0=0, nlev=eng.nk if vert_scale else 1, scale=scale, flags=self.flags, invert=True)
             self.blocks_owned = ob if vert_scale else ob[0]
         else:
-            idx = torch.cat([ix, iy], dim=1)
-            mult = torch.zeros(1, dm.n1, dtype=torch.float64, device=eng.device)
-            mult[0].index_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.float64, device=eng.device))
-            mult = eng.complete(1, mult)[0]                  # sharded: sharers on other ranks count too
-            d = 1.0 / mult[idx]
             # M1_e(k) = U^T diag(c_q thickInv_k(q)) U ~ tau_{k,e} * U^T diag(c_q) U with tau = the element's mean thickInv (exact when
             # the layer thickness is horizontally uniform over the element): ONE thickness-free inverse per element, resident in
             # LDS while the kernel sweeps the levels, times 1/tau per (level, element)
-            em = eng.element_matrices("UMAT", lev=0, scale=scale, flags=0).view(eng.nEl, 2, 2, n1e, n1e)
-            B = em.permute(0, 1, 3, 2, 4).reshape(eng.nEl, 2 * n1e, 2 * n1e)
-            self.blocks = (d[:, :, None] * getattr(eng, "eng", eng).block_inverse(B) * d[:, None, :]).contiguous()
+            d = edge_sharing_weights(eng)
+            self.blocks = element_block_preconditioner(eng, eng.element_matrices("UMAT", lev=0, scale=scale, flags=0), d)
             tau = torch.as_tensor(dm.thickInv, device=eng.device).mean(dim=2) if vert_scale else \
                 torch.ones(eng.nk, eng.nEl, dtype=torch.float64, device=eng.device)
             self.escale = (1.0 / tau).contiguous()
@@ -311,7 +283,7 @@ class MassSolver:
     def _blocks_t(self):
         """the blocks as mimsem_ksp_set_pc_elem_blocks applies them (no transpose flag): B^T, contiguous -- the same products as
         precond()'s transposed read of B"""
-        if getattr(self, "_bt", None) is None:
+        if self._bt is None:
             self._bt = self.blocks.transpose(1, 2).contiguous()
         return self._bt
 
@@ -329,8 +301,7 @@ class MassSolver:
                 lmin, lmax, elo, ehi = lanczos_bounds(lambda v: self.apply(v, 0), lambda r: self.precond(r, 0), b, its=40, errors=True,
                                                       dot=lambda u, v: eng.allreduce(torch.linalg.vecdot(u * w1, v, dim=1)))
             else:
-                g = torch.Generator(device="cpu"); g.manual_seed(1234)
-                b = torch.randn(eng.nk, eng.sizes[1], generator=g, dtype=torch.float64).to(eng.device)
+                b = seeded_randn((eng.nk, eng.sizes[1]), 1234, eng.device)
                 lmin, lmax, elo, ehi = lanczos_bounds(lambda v: self.apply(v, 0), lambda r: self.precond(r, 0), b, its=40, errors=True)
             self.ritz_errors = (elo / lmin, ehi / lmax)
             self.ritz = (lmin, lmax)
@@ -350,49 +321,37 @@ class MassSolver:
         """the fixed-length solve with its check norms written to the device log (two extra stores in two sweeps + one two-row-block dot:
         recordable, no host synchronisation)"""
         nlev, n = b.shape
-        if self._log is None or self._log.shape[1] != 2 * nlev:
-            self._log = torch.zeros(self.MAXLOG, 2 * nlev, dtype=torch.float64, device=b.device)
+        if self.check_log is None or self.check_log.width != nlev:
+            self.check_log = CheckLog(self.eng, 16, width=nlev, reuse_last=True)
             self._pair = torch.zeros(2 * nlev, n, dtype=torch.float64, device=b.device)
-            self._slot = 0
         ch.upd = self._pair[:nlev]
         x = ch.solve(b, want_residual=True, pb=self._pair[nlev:])
-        k = min(self._slot, self.MAXLOG - 1); self._slot += 1
-        self.eng.rowdot_local(self._pair, self._pair, out=self._log[k], space=1)       # (sharded: this rank's ownership-weighted part; verify() reduces the log once)
+        self.check_log.pair(self._pair, space=1)       # (sharded: this rank's ownership-weighted part; verify() reduces the log once)
         return x
 
-    def verify(self, rtol=1e-14, host_log=None):
+    def verify(self, rtol=1e-14, host=None):
         """the checks of every fixed-length solve since the last call in ONE read: True = every level of every solve had its last
         preconditioned residual below 30 rtol |P b| (one more contraction lies between that residual and the result).  False: the
         Chebyshev mode is switched off (PCG from here on) and the caller redoes its evaluation.  Synchronises -- unless the caller read
-        the log itself together with checks of its own (host_log: log().cpu() of that read, single rank)."""
-        if self._log is None or self._slot == 0:
+        check_log itself together with checks of its own (host: its array of that CheckLog.read)."""
+        log = self.check_log
+        if log is None or log.size == 0:
             return True
-        if self.dist:
-            self.eng.allreduce_checked(self._log)               # ONE all-reduce for every solve since the last call (+ the halo time-outs: HaloTimeout)
-        import numpy as np
-        v = self._log.cpu().numpy() if host_log is None else np.asarray(host_log).reshape(self._log.shape)
-        self._log.zero_(); self._slot = 0
-        nlev = v.shape[1] // 2
-        ok = True
-        for row in v:
-            r2, ref2 = row[:nlev], row[nlev:]
-            if not (r2.any() or ref2.any()):
-                continue
-            import numpy as np
-            with np.errstate(divide="ignore", invalid="ignore"):
-                rel = np.where(ref2 > 0.0, np.sqrt(r2 / np.where(ref2 > 0.0, ref2, 1.0)), np.where(r2 > 0.0, np.inf, 0.0))
-            self.solves_checked += 1
-            worst = float(np.nanmax(rel)) if np.isfinite(rel).any() else float("inf")
-            self.worst_check = max(self.worst_check, worst)
-            if not bool((rel <= 30.0 * rtol).all()):
-                ok = False; self.solves_missed += 1
-        if not ok:
+        v = CheckLog.read(log)[0] if host is None else host
+        self.solves_unchecked += log.shared
+        log.clear()
+        v = v[v.any(axis=1)]                                   # (a row of zeros: nothing was logged there)
+        if not len(v):
+            return True
+        good, rel = accepted(v[:, :log.width], v[:, log.width:], 30.0 * rtol)
+        fin = np.isfinite(rel)
+        missed = int((~good.all(axis=1)).sum())
+        self.solves_checked += len(v)
+        self.solves_missed += missed
+        self.worst_check = max(self.worst_check, float(np.nanmax(rel)) if fin.any(axis=1).all() else float("inf"))
+        if missed:
             self.chebyshev = False
-        return ok
-
-    def log(self):
-        """the device log verify() reads (None before the first fixed-length solve)"""
-        return self._log
+        return not missed
 
     def solve(self, b, lev0=0, rtol=1e-14, maxit=300):
         nlev = b.shape[0]
@@ -415,7 +374,7 @@ class MassSolver:
                     "UMAT", self._blocks_cm, rhs, coef, elem_scale=es, lev0=lev0, scale=self.scale, flags=self.flags, pb=pb, upd=upd)
             # the calibrated step count holds for the tolerance and the level range it was calibrated on (advisor, round 3): a call that asks
             # for a tighter rtol, or covers levels the calibration did not see, goes back to the bound-based count and re-calibrates
-            cal = getattr(self, "_cheb_cal", None)
+            cal = self._cheb_cal
             if cal is not None and not torch.cuda.is_current_stream_capturing() and \
                     (rtol < cal["rtol"] or lev0 < cal["lev0"] or lev0 + nlev > cal["lev0"] + cal["nlev"]):
                 ch.set_steps(cal["bound_steps"])
@@ -440,8 +399,7 @@ class MassSolver:
                 # path of this class) or is within a factor 2 of the round-off floor, plus one step; MIMSEM_CHEB_CALIBRATE=0 keeps the bound.
                 if os.environ.get("MIMSEM_CHEB_CALIBRATE", "1") != "0":
                     full = ch.steps
-                    g = torch.Generator(device="cpu"); g.manual_seed(4321)
-                    rnd = torch.randn(b.shape, generator=g, dtype=b.dtype).to(b.device) * bn[:, None] / math.sqrt(b.shape[1])
+                    rnd = seeded_randn(b.shape, 4321, b.device) * bn[:, None] / math.sqrt(b.shape[1])
                     rn = torch.linalg.vector_norm(rnd, dim=1).clamp_min(1e-300)
                     rnd_res = lambda y: float((torch.linalg.vector_norm(rnd - self.apply(y, lev0), dim=1) / rn).max())
                     floor_rnd = rnd_res(ch.solve(rnd))             # a random right-hand side excites every eigenmode: the count must hold for it too
@@ -462,7 +420,7 @@ class MassSolver:
             if not hasattr(self.eng, "halo") and not self.fixed_its and os.environ.get("MIMSEM_PCG", "c") == "c":
                 # the batched PCG loop of the C ABI (mimsem_ksp_*, csrc/ksp.hip) with this object's blocks: what a C++ host runs
                 key = (lev0, nlev)
-                if getattr(self, "_ksp_key", None) != key:
+                if self._ksp_key != key:
                     self._ksp = KSP(self.eng, "cg").set_operator("UMAT", nlev, lev0=lev0, scale=self.scale, flags=self.flags)
                     self._ksp.set_pc("elem_blocks", blocks=self._blocks_t(), elem_scale=self.escale[lev0:lev0 + nlev])
                     self._ksp_key = key
@@ -472,9 +430,8 @@ class MassSolver:
             with self.eng.space(1):
                 return pcg_engine(self.eng, lambda v: self.apply(v, lev0), b, lambda r: self.precond(r, lev0), rtol=rtol, maxit=maxit,
                                   fixed_its=self.fixed_its)
-        if self.kind == "jacobi":
-            return pcg(lambda v: self.apply(v, lev0), b, minv=self.minv[lev0:lev0 + nlev], rtol=rtol, maxit=maxit)
-        return pcg(lambda v: self.apply(v, lev0), b, precond=lambda r: self.precond(r, lev0), rtol=rtol, maxit=maxit, check_every=2)
+        minv = self.minv[lev0:lev0 + nlev]                 # (jacobi: the other two kinds have returned)
+        return pcg(lambda v: self.apply(v, lev0), b, precond=lambda r: r * minv, rtol=rtol, maxit=maxit)
 
     def apply_fric(self, x, tau, exner, exner_s, lev0=0):
         """(M1 + M1ray(tau)) x in one element pass; exner: the rows of levels lev0.., exner_s: the row of level 0"""
@@ -505,7 +462,8 @@ class MassSolver:
             return self._logged_solve(ch, b), ch.steps
         A = lambda v: self.apply_fric(v, tau, exner, exner_s, lev0)
         if self.kind == "jacobi":
-            return pcg(A, b, minv=self.minv[lev0:lev0 + nlev], rtol=rtol, maxit=maxit)
+            minv = self.minv[lev0:lev0 + nlev]
+            return pcg(A, b, precond=lambda r: r * minv, rtol=rtol, maxit=maxit)
         return pcg(A, b, precond=lambda r: self.precond(r, lev0), rtol=rtol, maxit=maxit, check_every=2)
 
 
@@ -806,7 +764,6 @@ def arnoldi_ritz(body, n, m, device, seed=1, eng=None, space=None, earlier=None)
     (same seed, same generator -> the same Krylov space), inner products are ownership-weighted and all-reduced -- every rank arrives at
     the same Hessenberg matrix, hence at the same spectral interval and the same fixed step counts.
     earlier = m0 < m: returns (values of m steps, values of the first m0 steps) -- how far the ends still move tells how well they are known."""
-    import numpy as np
     dist = eng is not None and hasattr(eng, "halo")
     if dist:
         v = eng.randn_global(space, seed).reshape(-1)
@@ -859,7 +816,6 @@ def chebyshev_ellipse_coefs(d, c2, steps):
 
 def chebyshev_ellipse_rate(d, a_re, a_im):
     """asymptotic convergence factor for an ellipse with centre d > 0 and semi-axes a_re (real direction), a_im (imaginary direction)"""
-    import math
     c2 = a_re * a_re - a_im * a_im
     return (a_re + a_im) / (d + math.sqrt(max(d * d - c2, 0.0)))
 
@@ -877,14 +833,11 @@ class GraphedChebyshev:
         operator has one: mimsem_sw_operator_precond_chebyshev, three launches) instead of body(d) + the update kernel (four).
         space: the vector space of the two check norms (a DistEngine weights them by ownership; they stay LOCAL partial sums -- _run() holds no
         all-reduce, the caller reduces its whole check vector once)"""
-        import math
         self.eng, self.body, self.precond, self.step, self.space = eng, body, precond, step, space
         self.lmin, self.lmax = margin[0] * lmin, margin[1] * lmax
         self.theta, self.delta = 0.5 * (self.lmax + self.lmin), 0.5 * (self.lmax - self.lmin)
-        kap = self.lmax / self.lmin
-        q = (math.sqrt(kap) - 1.0) / (math.sqrt(kap) + 1.0)
-        self.rate = q
-        self.steps = max(2, int(math.ceil(math.log(0.5 * rtol) / math.log(q))) + 1)
+        self.rate = interval_rate(self.lmin, self.lmax)
+        self.steps = rate_steps(self.rate, rtol)
         self.rtol = rtol
         self.b = torch.zeros(shape, dtype=dtype, device=eng.device)       # the raw right-hand side (un-preconditioned)
         self.x = torch.zeros(shape, dtype=dtype, device=eng.device)
@@ -932,13 +885,12 @@ class GraphedChebyshev:
                 self.graph_steps = self.steps
             self.b.copy_(b)
             self.graph.replay()
-        r2, c2 = self.nrm.tolist()
+        r2, c2 = CheckLog.read(self.nrm)[0].tolist()
         if c2 == 0.0:
             return self.x.clone(), self.steps, 0.0
         rel = (r2 / c2) ** 0.5
         if not (rel <= self.rtol):                        # (NaN fails too)
             if rel == rel and rel < 1e3 * self.rtol and self.steps < 200:
-                import math
                 self.steps += max(1, int(math.ceil(math.log(self.rtol / rel) / math.log(self.rate))) + 1)     # the bound was a little short: longer next time
             return None if not (rel == rel) else (self.x.clone(), -self.steps, rel)
         return self.x.clone(), self.steps, rel
@@ -950,7 +902,6 @@ def lanczos_bounds(apply_A, precond, b, its=25, dot=None, errors=False):
     the spectrum first.  Returns (lmin, lmax) over all rows.  Setup-time helper (host synchronisation per step).
     errors: also the residual bounds of the two extreme Ritz values, |beta_k s_ki| (s_ki: last component of the Ritz vector in the Lanczos
     basis) -- an eigenvalue of P A lies within that distance of each; (lmin, lmax, err_min, err_max), the errors the largest over the rows."""
-    import numpy as np
     x = torch.zeros_like(b); r = b.clone(); z = precond(r); p = z.clone()
     if dot is None:                                          # (sharded meshes pass the ownership-weighted, all-reduced row dot)
         dot = lambda u, v: torch.linalg.vecdot(u, v, dim=1)
@@ -997,9 +948,7 @@ class ChebyshevMass:
         """sweep(x, b, p, alpha, beta, upd): one fused step (closure over op, blocks, elem_scale, lev0, scale, flags)"""
         self.eng, self.sweep = eng, sweep
         self.lmin, self.lmax = margin[0] * lmin, margin[1] * lmax
-        kappa = self.lmax / self.lmin
-        sg = (math.sqrt(kappa) - 1.0) / (math.sqrt(kappa) + 1.0)
-        self.set_steps(max(2, int(math.ceil(math.log(2.0 / rtol) / math.log(1.0 / sg)))))
+        self.set_steps(interval_steps(self.lmin, self.lmax, rtol))
         self.p = None
         self.upd = None
         self.whole = None          # whole(b, coef, pb, upd) -> x: the solve from x = 0 as ONE engine call (Engine.block_chebyshev_solve: no operator pass in the first step, nothing cleared)

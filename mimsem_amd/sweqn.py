@@ -12,8 +12,10 @@ import torch
 
 from ._switches import experiment
 
+from .checks import CheckLog, accepted, rate_steps
 from .geom import gll_weights
-from .krylov import GraphedGMRES, GraphedRichardson, gmres, pcg_engine
+from .krylov import (ChebyshevMass, GraphedChebyshev, GraphedGMRES, GraphedRichardson, arnoldi_ritz, chebyshev_ellipse_coefs, chebyshev_ellipse_rate,
+                     edge_sharing_weights, element_block_preconditioner, gmres, lanczos_bounds, pcg_engine, ritz_margins, seeded_randn)
 
 RAD_EARTH = 6371220.0          # src/SWEqn_Picard.cpp:22-23
 RAD_SPHERE = 6371220.0
@@ -35,7 +37,7 @@ class SWEqn:
         xq = torch.as_tensor(quad_coords, dtype=torch.float64, device=eng.device)
         self.lat = torch.asin(xq[:, 2] / RAD_SPHERE)
         self.m0 = eng.pvec(0, 1, 1.0)                            # M0 is diagonal (collocated 0-forms): Pmat as a vector
-        self.m1_pre = self._m1_element_blocks()
+        self.m1_pre = element_block_preconditioner(eng, eng.element_matrices("UMAT"))     # of M1 (the reference: PCBJACOBI, one block per element, :88-90)
         self.m2_inv = eng.element_matrices("WMATINV").view(eng.nEl, eng.n2e, eng.n2e)            # M2 is element-block diagonal: its exact inverse, built once
         self.coriolis()
         self.A_dt = None
@@ -127,21 +129,6 @@ class SWEqn:
     def R_up(self, q, ul, dt, u): return self.eng.apply_up("ROTMAT_UP", u, q, ul, fac=UP_TAU, dt=dt)
     def E(self, name, x): return self.eng.incidence(name, x)
 
-    def _m1_element_blocks(self):
-        """element-block preconditioner of M1 (the reference: PCBJACOBI with one block per element, :88-90):
-        P^-1 = sum_e R_e^T D_e (M1_e)^-1 D_e R_e, D_e = 1/(number of elements sharing the edge) -- cond(P^-1 M1) ~ 1.2"""
-        eng = self.eng
-        n1e = eng.n1e
-        em = eng.element_matrices("UMAT").view(eng.nEl, 2, 2, n1e, n1e)
-        B = em.permute(0, 1, 3, 2, 4).reshape(eng.nEl, 2 * n1e, 2 * n1e)        # [[UtQU, UtQV], [VtQU, VtQV]]
-        idx = torch.cat([torch.as_tensor(eng.mesh.inds1x, device=eng.device), torch.as_tensor(eng.mesh.inds1y, device=eng.device)], dim=1).long()
-        mult = torch.zeros(1, eng.sizes[1], dtype=torch.float64, device=eng.device)
-        mult[0].index_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.float64, device=eng.device))
-        mult = eng.complete(1, mult)[0]                                          # sharded: count the sharers on other ranks too
-        d = 1.0 / mult[idx]                                                      # [nEl, 2 n1e]
-        Binv = getattr(eng, "eng", eng).block_inverse(B)      # the library's batched Gauss-Jordan (24 x 24 SPD blocks)
-        return (d[:, :, None] * Binv * d[:, None, :]).contiguous()
-
     def precond_M1(self, r, out=None):
         return self.eng.blocks_apply(1, self.m1_pre, r, transpose=True, out=out)        # symmetric blocks: the coalesced read order
 
@@ -185,12 +172,10 @@ class SWEqn:
         return x
 
     def _solve_M1_chebyshev(self, b):
-        from .krylov import ChebyshevMass, lanczos_bounds
         st = getattr(self, "_cM1", None)
         if st is None or st["b"].shape != b.shape:
             cm = self.m1_pre.transpose(1, 2).contiguous()
-            g = torch.Generator(device="cpu"); g.manual_seed(4321)
-            rb = torch.randn(b.shape, generator=g, dtype=torch.float64).to(self.eng.device)
+            rb = seeded_randn(b.shape, 4321, self.eng.device)
             lmin, lmax = lanczos_bounds(self.M1, self.precond_M1, rb, its=25)
             ch = ChebyshevMass(self.eng, lambda x, rhs, p, al, be, upd: self.eng.block_chebyshev_sweep("UMAT", cm, x, rhs, p, al, be, upd=upd),
                                lmin, lmax, rtol=self.rtol)
@@ -210,9 +195,9 @@ class SWEqn:
         if st["graph"] is None:
             st["graph"], _ = self.eng.capture(st["run"])
         st["graph"].replay()
-        z2, c2 = st["nrm"].tolist()
+        z2, c2 = CheckLog.read(st["nrm"])[0].tolist()
         # (the residual the last sweep saw belongs to the iterate BEFORE its update: one more contraction lies between it and the result)
-        if c2 > 0.0 and not (z2 ** 0.5 <= 30.0 * self.rtol * c2 ** 0.5):
+        if not accepted(z2, c2, 30.0 * self.rtol)[0]:
             st["bad"] += 1
             return None
         return st["x"].clone(), st["ch"].steps
@@ -394,11 +379,7 @@ class SWEqn:
         Ae[:, :2 * n1e, 2 * n1e:] = (a * self.grav) * (-E21.T) @ M2e
         Ae[:, 2 * n1e:, :2 * n1e] = (a * H_MEAN) * M2e @ E21
         Ae[:, 2 * n1e:, 2 * n1e:] = M2e
-        idx = torch.cat([torch.as_tensor(eng.mesh.inds1x, device=dev), torch.as_tensor(eng.mesh.inds1y, device=dev)], dim=1).long()
-        mult = torch.zeros(1, eng.sizes[1], dtype=torch.float64, device=dev)
-        mult[0].index_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.float64, device=dev))
-        mult = eng.complete(1, mult)[0]
-        d = torch.cat([1.0 / mult[idx], torch.ones(nEl, n2e, dtype=torch.float64, device=dev)], dim=1)
+        d = torch.cat([edge_sharing_weights(eng), torch.ones(nEl, n2e, dtype=torch.float64, device=dev)], dim=1)
         C = d[:, :, None] * getattr(self.eng, "eng", self.eng).block_inverse(Ae) * d[:, None, :]
         return C.transpose(1, 2).contiguous()                     # column-major per element
 
@@ -480,7 +461,6 @@ class SWEqn:
                 cheb_done = False
                 if self.cheb and self.eng.mesh.n <= 4 and self.coupled_pc:
                     if self._cA is None or self._cA[0] != dt:
-                        from .krylov import GraphedChebyshev, arnoldi_ritz
                         body1 = self._krylov_body1(dt)
                         ev = arnoldi_ritz(body1, self.n1 + self.n2, 40, self.eng.device)
                         lmin, lmax, imax = float(ev.real.min()), float(ev.real.max()), float(abs(ev.imag).max())
@@ -685,11 +665,10 @@ class _PicardGraph:
     vector ONCE, checks every solve against its tolerance and takes |dx| / |x| for the Picard loop.  Two graphs: the first iteration of a step
     (also diagnoses q of the start-of-step state; uj = ui) and the later ones."""
     NSLOT = 16
-    SPACE = {"M1": 1, "q": 0, "A": "uh", "picard": "uh"}          # the vector space of each check (a DistEngine weights the norms by ownership)
+    SPACE = {"M1": 1, "q": 0, "A": "uh", "picard": "uh"}          # the vector space of each kind of check (a DistEngine weights the norms by ownership)
 
     def __init__(self, S, dt, q_exact, un, hn, has_bot=False, widen=1.0):
         """widen >= 1: the safety margins around the estimated spectral regions, times widen (a re-estimate after a missed check asks for more)"""
-        from .krylov import ChebyshevMass, GraphedChebyshev, arnoldi_ritz, chebyshev_ellipse_coefs, chebyshev_ellipse_rate, lanczos_bounds, ritz_margins
         self.S, self.dt, self.q_exact = S, dt, q_exact
         self.dist = S.dist                   # sharded: local (ownership-weighted) check norms, one all-reduce per Picard iteration (replay)
         # ... recorded as a hipGraph all the same when the exchanges are kernels only (the one-sided transport of csrc/halo.hip: pack into the
@@ -705,7 +684,7 @@ class _PicardGraph:
         self.ui, self.hi = torch.zeros_like(un), torch.zeros_like(hn)
         self.x = torch.zeros(un.shape[0], n1 + n2, dtype=torch.float64, device=dev)
         self.qi = torch.zeros(un.shape[0], n0, dtype=torch.float64, device=dev)
-        self.chk = torch.zeros(2 * self.NSLOT, dtype=torch.float64, device=dev)
+        self.log = CheckLog(eng, self.NSLOT)          # kinds: the keys of SPACE
         self.graphs = {}
         self.its = {}
         # ---- [u|h]: real interval of P A
@@ -732,8 +711,7 @@ class _PicardGraph:
             w1 = eng.weights(1)
             l1, l2, e1, e2 = lanczos_bounds(S.M1, S.precond_M1, rb, its=40, errors=True, dot=lambda a, b: eng.allreduce(torch.linalg.vecdot(a * w1, b, dim=1)))
         else:
-            g = torch.Generator(device="cpu"); g.manual_seed(4321)
-            rb = torch.randn(un.shape, generator=g, dtype=torch.float64).to(dev)
+            rb = seeded_randn(un.shape, 4321, dev)
             l1, l2, e1, e2 = lanczos_bounds(S.M1, S.precond_M1, rb, its=40, errors=True)
         self.regions["M1"] = (l1, l2)
         self.margins = {"A": mgA, "M1": ritz_margins(l1, l2, 2.0 * e1 / l1, 2.0 * e2 / l2, widen)}
@@ -758,15 +736,13 @@ class _PicardGraph:
             rate = chebyshev_ellipse_rate(d0, a_re, a_im)
             if not (d0 > 0.2 and rate < 0.6):
                 raise _NoGraph()
-            nq = max(2, int(math.ceil(math.log(0.5 * S.rtol) / math.log(rate))) + 1)
+            nq = rate_steps(rate, S.rtol)
             self.qcoef = chebyshev_ellipse_coefs(d0, a_re * a_re - a_im * a_im, nq)
             self.qtau = tau
             self.qp = torch.zeros(un.shape[0], n0, dtype=torch.float64, device=dev)
             self.pair0 = torch.zeros(2, n0, dtype=torch.float64, device=dev) if un.shape[0] == 1 else None
             self.qupd = self.pair0[0:1] if self.pair0 is not None else torch.zeros_like(self.qp)
             self.its["q"] = nq
-        self.slot = 0
-        self.names = {}
         # MIMSEM_SW_FORK=1: the q solve as a parallel branch of the recorded iteration (second stream + second context of the same mesh)
         self.fork = (not q_exact) and not self.dist and experiment("MIMSEM_SW_FORK", "0") == "1"
         # round 6: the mass-flux solve (15 sweeps x 3 launches) and the potential-vorticity solve (20 x 2) of an iteration read nothing of each
@@ -781,34 +757,19 @@ class _PicardGraph:
             self.qj = torch.zeros_like(self.qi)
 
     # -- the inline solves (called from SWEqn.solve_M1 / diagnose_q while this object records or warms up)
-    def _log(self, name, res, ref):
-        k = self.slot; self.slot += 1
-        assert k < self.NSLOT
-        self.names[k] = name
-        eng = self.S.eng
-        sp = self.SPACE[name]
-        eng.rowdot_local(res.reshape(1, -1), res.reshape(1, -1), out=self.chk[2 * k:2 * k + 1], space=sp)
-        eng.rowdot_local(ref.reshape(1, -1), ref.reshape(1, -1), out=self.chk[2 * k + 1:2 * k + 2], space=sp)
-
-    def _log_pair(self, name, pair):
-        k = self.slot; self.slot += 1
-        assert k < self.NSLOT
-        self.names[k] = name
-        self.S.eng.rowdot_local(pair, pair, out=self.chk[2 * k:2 * k + 2], space=self.SPACE[name])
-
     def m1(self, b):
         if self.pairM is not None and not self.dist and hasattr(self.S.eng, "block_chebyshev_solve") and self.S.eng.n1e <= 30 and len(self.chM.coef) > 1:
             # one context: the whole solve from x = 0 as ONE call (no operator pass in the first step, nothing cleared); P b, the check's reference
             # vector, is the first step's update -- 5 launches fewer than the sweeps + the extra preconditioner application (config 2: no dual solves)
             x = self.S.eng.block_chebyshev_solve("UMAT", self.cm, b, self.chM.coef, pb=self.pairM[1:2], upd=self.pairM[0:1])
-            self._log_pair("M1", self.pairM)
+            self.log.pair(self.pairM, "M1", self.SPACE["M1"])
             return x
         x = self.chM.solve(b, want_residual=True)
         if self.pairM is not None and self.chM.upd.data_ptr() == self.pairM.data_ptr():
             self.S.precond_M1(b, out=self.pairM[1:2])
-            self._log_pair("M1", self.pairM)
+            self.log.pair(self.pairM, "M1", self.SPACE["M1"])
         else:
-            self._log("M1", self.chM.upd, self.S.precond_M1(b))
+            self.log.two(self.chM.upd, self.S.precond_M1(b), "M1", self.SPACE["M1"])
         return x
 
     def q(self, rhs, m0h, h, u, dt):
@@ -821,9 +782,9 @@ class _PicardGraph:
             eng.chebyshev_sweep("PHMAT_UP", x, rhs, dinv, self.qp, al, be, f=h, u=u, tau=self.qtau, upd=self.qupd if k == last else None)
         if self.pair0 is not None:
             torch.mul(rhs, dinv, out=self.pair0[1:2])
-            self._log_pair("q", self.pair0)
+            self.log.pair(self.pair0, "q", self.SPACE["q"])
         else:
-            self._log("q", self.qupd, rhs * dinv)
+            self.log.two(self.qupd, rhs * dinv, "q", self.SPACE["q"])
         return x
 
     def solve_F_and_q(self, hu, rhs0, m0h, h, u):
@@ -833,8 +794,8 @@ class _PicardGraph:
         F = torch.empty_like(hu); q = torch.empty_like(rhs0)          # (outputs of solves from x = 0: written, not updated -- nothing to clear)
         eng.sw_dual_chebyshev(self.chM.coef, self.cm, hu, self.chM.p, F, self.pairM[0:1], self.qcoef, self.qtau, h, u, rhs0, dinv, self.qp, q, self.pair0[0:1],
                               pb1=self.pairM[1:2], pb0=self.pair0[1:2])      # P hu and dinv rhs0, the checks' reference vectors, are the first steps' updates
-        self._log_pair("M1", self.pairM)
-        self._log_pair("q", self.pair0)
+        self.log.pair(self.pairM, "M1", self.SPACE["M1"])
+        self.log.pair(self.pair0, "q", self.SPACE["q"])
         return F, q
 
     def _q_on_a_branch(self, first, uj, hj):
@@ -857,7 +818,7 @@ class _PicardGraph:
 
     def _body(self, first):
         S, n1 = self.S, self.S.n1
-        self.slot = 0
+        self.log.rewind()                                # (a slot claimed while recording is part of the graph: every body fills the same ones)
         uj, hj = self.x[:, :n1].contiguous(), self.x[:, n1:].contiguous()
         join = None
         F = None
@@ -880,67 +841,52 @@ class _PicardGraph:
         f = S.assemble_residual(self.ui, self.hi, uj, hj, self.dt, self.q_exact, self.bot, qi=None if self.q_exact else self.qi,
                                 qj=qj, it=0 if first else 1, before_q=join, F=F)
         ch = self.chA
-        k = self.slot; self.slot += 1
-        self.names[k] = "A"
-        ch._run(neg_of=f, nrm=self.chk[2 * k:2 * k + 2])          # A dx = -f: the sign rides in the start kernel, the check norms go straight into the log
-        k = self.slot; self.slot += 1
-        self.names[k] = "picard"
+        ch._run(neg_of=f, nrm=self.log.claim("A"))              # A dx = -f: the sign rides in the start kernel, the check norms go straight into the log
         if not self.dist and hasattr(S.eng, "axpy_dots") and self.x.is_contiguous() and ch.x.is_contiguous():
-            S.eng.axpy_dots(ch.x, self.x, self.chk[2 * k:2 * k + 2])      # x += dx, |dx|^2, |x|^2: one launch
+            S.eng.axpy_dots(ch.x, self.x, self.log.claim("picard"))      # x += dx, |dx|^2, |x|^2: one launch
         else:
             self.x.add_(ch.x)
-            S.eng.rowdot_local(ch.x.reshape(1, -1), ch.x.reshape(1, -1), out=self.chk[2 * k:2 * k + 1], space="uh")
-            S.eng.rowdot_local(self.x.reshape(1, -1), self.x.reshape(1, -1), out=self.chk[2 * k + 1:2 * k + 2], space="uh")
-        self.nslots = self.slot
+            self.log.two(ch.x, self.x, "picard", self.SPACE["picard"])
 
     def replay(self, first):
+        """one Picard iteration; returns the host copy of the log, [NSLOT, 2].  Sharded with a library or host transport: the same sequence of
+        launches eagerly, with the halo exchanges where the element-local sums need completing.  Every check norm is a local (ownership-weighted)
+        partial sum: CheckLog.read holds the ONE all-reduce of a Picard iteration (this rank's count of one-sided halo plans whose exchange gave up
+        waiting folded in, so every rank raises HaloTimeout after the same collective); there is none inside any solve"""
         S = self.S
-        if self.dist and not self.record:
-            # the same sequence of launches, eagerly, with the halo exchanges where the element-local sums need completing; every check norm is a
-            # local (ownership-weighted) partial sum: ONE all-reduce of 2 x nslots doubles per Picard iteration, none inside any solve
+        eager = self.dist and not self.record
+        if eager or first not in self.graphs:
+            keep = None if eager else self.x.clone()
             S._inline = self
             try:
-                self._body(first)
+                g = self._body(first) if eager else S.eng.capture(lambda: self._body(first))[0]
             finally:
                 S._inline = None
-            self.graphs[first] = (None, dict(self.names), self.nslots)
-            return self._reduce()
-        if first not in self.graphs:
-            keep = self.x.clone()
-            S._inline = self
-            try:
-                self.graphs[first] = (S.eng.capture(lambda: self._body(first))[0], dict(self.names), self.nslots)
-            finally:
-                S._inline = None
-            self.x.copy_(keep)
-        g, _, _ = self.graphs[first]
-        g.replay()
-        if self.dist:
-            return self._reduce()
-        return self.chk.tolist()
-
-    def _reduce(self):
-        """the ONE all-reduce of a sharded Picard iteration: the check norms, with this rank's count of one-sided halo plans whose exchange gave
-        up waiting folded in (DistEngine.allreduce_checked) -- every rank sees any rank's time-out after the same collective and raises HaloTimeout"""
-        self.S.eng.allreduce_checked(self.chk)
-        return self.chk.tolist()
+            self.graphs[first] = (g, self.log.kinds[:self.log.size], self.log.size)
+            if not eager:
+                self.x.copy_(keep)
+        if not eager:
+            self.graphs[first][0].replay()
+        return CheckLog.read(self.log)[0]
 
     def verify(self, vals, first):
-        _, names, nslots = self.graphs[first]
+        """vals: the host copy of the log, {|r|^2, |ref|^2} per slot.  (every check passed, |dx| / |x| of the picard slot)"""
+        _, kinds, nslots = self.graphs[first]
+        vals = np.asarray(vals, dtype=np.float64).reshape(-1).tolist()
         ok, norm = True, float("nan")
         for k in range(nslots):
             res2, ref2 = vals[2 * k], vals[2 * k + 1]
-            if names[k] == "picard":
+            if kinds[k] == "picard":
                 norm = (res2 / ref2) ** 0.5 if ref2 > 0.0 else 0.0
                 ok = ok and norm == norm
                 continue
             # M1 / q log the residual the LAST sweep saw (one more contraction lies between it and the result): a factor 30 of slack; the
             # [u|h] system logs the recurrence residual of the result itself
-            tol = self.S.rtol * (30.0 if names[k] in ("M1", "q") else 3.0)
-            rel = (res2 / ref2) ** 0.5 if ref2 > 0.0 else 0.0
-            if not (rel <= tol):
+            tol = self.S.rtol * (30.0 if kinds[k] in ("M1", "q") else 3.0)
+            good, rel = accepted(res2, ref2, tol)
+            if not good:
                 ok = False
-                self.last_miss = (names[k], rel, tol)
+                self.last_miss = (kinds[k], rel, tol)
         return ok, norm
 
 

@@ -16,8 +16,9 @@ import math
 import numpy as np
 import torch
 
+from .checks import CheckLog, accepted, log_true_residual
 from .geom import gll_weights
-from .krylov import MassSolver, pcg_engine
+from .krylov import MassSolver, edge_sharing_weights, element_block_preconditioner, pcg_engine
 from .sweqn import RAD_SPHERE, galewsky
 
 RK3 = ((0.0, 1.0), (0.75, 0.25), (1.0 / 3.0, 2.0 / 3.0))      # (alpha, beta) of the three stages, :894-1000
@@ -57,15 +58,11 @@ class ThermalSW:
         w = gll_weights(n)
         self.Qw = torch.as_tensor(np.outer(w, w).reshape(-1), device=eng.device)      # point q = qy (n+1) + qx
         self.det = torch.as_tensor(eng.mesh.det, device=eng.device)
-        idx = torch.cat([torch.as_tensor(eng.mesh.inds1x, device=eng.device), torch.as_tensor(eng.mesh.inds1y, device=eng.device)], dim=1).long()
-        mult = torch.zeros(eng.sizes[1], dtype=torch.float64, device=eng.device)
-        mult.index_add_(0, idx.reshape(-1), torch.ones(idx.numel(), dtype=torch.float64, device=eng.device))
-        self._idx1, self._d1 = idx, 1.0 / mult[idx]
+        self._d1 = edge_sharing_weights(eng)
         if not torch.all(torch.as_tensor(eng.mesh.thickInv) == 1.0):
             raise ValueError("ThermalSW needs unit thickness (the src flavour: levels 0 and 1)")
         self.m1h_its = 16                   # fixed length of the M1h(h) PCG (12 reach rtol 1e-14 on the Galewsky state at ne 2 ... 24)
-        self._log1h = torch.zeros(3, 2, dtype=torch.float64, device=eng.device)     # per stage {|b - M1h x|^2, |b|^2}, read with the step's check
-        self._stage = 0
+        self._log1h = torch.zeros(1, dtype=torch.float64, device=eng.device)        # worst |b - M1h x|^2 / |b|^2 of the step's stages, read with the step's check
         self.steps = 0
         self.redone = 0                     # steps redone by the adaptive solvers after a missed check
         self.its = {}
@@ -88,17 +85,12 @@ class ThermalSW:
         synchronisation); the true residual is logged on the device and read with the step's single check (solve_rk).  After a missed
         check: the adaptive PCG to rtol."""
         eng = self.eng
-        n1e = eng.n1e
-        em = eng.element_matrices("UHMAT", f=h[0]).view(eng.nEl, 2, 2, n1e, n1e)
-        B = em.permute(0, 1, 3, 2, 4).reshape(eng.nEl, 2 * n1e, 2 * n1e)
-        P = (self._d1[:, :, None] * eng.block_inverse(B) * self._d1[:, None, :]).contiguous()
+        P = element_block_preconditioner(eng, eng.element_matrices("UHMAT", f=h[0]), self._d1)
         A = lambda v: eng.apply("UHMAT", v, f=h)
         pre = lambda r: eng.blocks_apply(1, P, r, transpose=True)
         if self.m1h_its > 0:
             x, its = pcg_engine(eng, A, b, pre, fixed_its=self.m1h_its)
-            r = b - A(x)
-            k = min(self._stage, self._log1h.shape[0] - 1)
-            eng.rowdot(torch.cat([r, b]), torch.cat([r, b]), out=self._log1h[k])
+            log_true_residual(eng, A, x, b, self._log1h)
         else:
             x, its = pcg_engine(eng, A, b, pre, rtol=self.rtol, maxit=1000, check_every=4)
         self.its["M1h"] = its
@@ -107,12 +99,10 @@ class ThermalSW:
     def check(self):
         """the step's ONE read: MassSolver's log of the fixed-length M1 solves and the M1h residuals, in one transfer.  False: a solve
         missed its tolerance -- the mass solver has switched to PCG and the M1h solve to the adaptive PCG; the caller redoes the step"""
-        ml = self.mass.log()
-        v = torch.cat([self._log1h.reshape(-1)] + ([ml.reshape(-1)] if ml is not None else [])).cpu().numpy()
+        ratio, ml = CheckLog.read(self._log1h, self.mass.check_log)
         self._log1h.zero_()
-        r2, b2 = v[0:6:2], v[1:6:2]
-        ok1h = bool(np.all(r2 <= (30.0 * self.rtol) ** 2 * b2))            # (NaN compares False: a miss)
-        okm = self.mass.verify(self.rtol, host_log=v[6:] if ml is not None else None)
+        ok1h = bool(accepted(ratio, 1.0, 30.0 * self.rtol)[0].all())
+        okm = self.mass.verify(self.rtol, host=ml)
         if not ok1h:
             self.m1h_its = 0
         return ok1h and okm
@@ -174,8 +164,7 @@ class ThermalSW:
         the step with the adaptive solvers."""
         for attempt in range(2):
             uj, hj, Sj = u.clone(), h.clone(), S.clone()
-            for k, (alpha, beta) in enumerate(RK3):
-                self._stage = k
+            for alpha, beta in RK3:
                 uj = self.stage(u, h, S, uj, hj, Sj, dt, alpha, beta)
             if self.check():
                 break

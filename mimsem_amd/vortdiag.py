@@ -15,6 +15,7 @@ logged on the device, one check() reading the log; after a miss the solves run t
 runs adaptively to find its count.  Single GPU, global numbering; vectors as in HorizSolve ([nk, n] levels, [nk - 1, n] interfaces)."""
 import torch
 
+from .checks import CheckLog, accepted, log_true_residual
 from .horizsolve import SCALE, VERT
 from .krylov import pcg_engine
 
@@ -58,10 +59,7 @@ class VortDiag:
         m = self._its[kind]
         if m:
             x, its = pcg_engine(eng, A, b, pre, fixed_its=m)
-            r = eng.combine(A(x), -1.0, beta=1.0, c=b)
-            ratio = eng.rowdot(r, r) / eng.rowdot(b, b).clamp_min(1e-300)
-            k = 0 if kind == "uz" else 1
-            torch.maximum(self._log[k], ratio, out=self._log[k])                 # (NaN propagates: a miss)
+            log_true_residual(eng, A, x, b, self._log[0 if kind == "uz" else 1])      # (NaN propagates: a miss)
             self.logged += 1
         else:
             x, its = pcg_engine(eng, A, b, pre, rtol=self.rtol, maxit=1000, check_every=2)
@@ -73,10 +71,10 @@ class VortDiag:
     def check(self):
         """the ONE read of the fixed-length solves since the last call.  False: some interface missed 30 rtol -- both solves have switched
         to the adaptive PCG; the caller redoes the diagnoses"""
-        v = self._log.cpu().numpy()
+        v, = CheckLog.read(self._log)
         self._log.zero_()
         self.logged = 0
-        ok = bool((v <= (30.0 * self.rtol) ** 2).all())                          # (NaN compares False)
+        ok = bool(accepted(v, 1.0, 30.0 * self.rtol)[0].all())
         if not ok:
             self.missed += 1
             self.m_its = 0

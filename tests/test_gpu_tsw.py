@@ -85,6 +85,26 @@ def test_fused_matches_composed(ne2):
     assert max(errs) < 1e-13
 
 
+def test_missed_m1h_check_redoes_the_step_adaptively(ne2):
+    """an M1h PCG forced to ONE iteration misses its true-residual check: the step is redone with the adaptive PCG and equals the step of an
+    object that was adaptive from the start.  Tolerance: after the miss both objects run the same solvers (adaptive M1h PCG, the mass solver in
+    its fixed-length mode) on the same state, so the 1e-13 this file asks between two device evaluations of one step is asked here too"""
+    from mimsem_amd.thermalsw import ThermalSW
+    eng, O, xq, T, (u, h, S) = ne2
+    A, B = ThermalSW(eng, xq), ThermalSW(eng, xq)
+    for t in (A, B):
+        t.solve_M1(eng.apply("UTQ", eng.zeros(1, eng.sizes["q2"]) + 1.0))           # (the mass solver's one-time calibration, as init() triggers it)
+        assert t.mass.verify(t.rtol) and t.mass.chebyshev
+    A.m1h_its = 1
+    B.m1h_its = 0
+    a, b = A.solve_rk(u, h, S, 30.0), B.solve_rk(u, h, S, 30.0)
+    assert A.redone == 1 and A.m1h_its == 0 and A.mass.chebyshev and A.mass.solves_missed == 0
+    assert B.redone == 0 and B.mass.chebyshev
+    errs = [rel_l2(x.cpu().numpy(), y.cpu().numpy()) for x, y in zip(a, b)]
+    print("redone after a missed M1h check vs adaptive from the start: u %.1e  h %.1e  S %.1e" % tuple(errs))
+    assert max(errs) < 1e-13
+
+
 def test_step_matches_dense_oracle(ne2):
     eng, O, xq, T, (u, h, S) = ne2
     uo, ho, So = galewsky_state(O)
