@@ -111,6 +111,7 @@ __device__ __forceinline__ double2 load_pair_agent(const double* p) {
 #define MIMSEM_WAVE_NT 0
 #endif
 typedef double wave_d2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) wave_d2 gwave_d2;
 #if MIMSEM_WAVE_NT
 __device__ __forceinline__ double2 wload2(const void* p) { const wave_d2 v = __builtin_nontemporal_load((const wave_d2*)p); double2 r; r.x = v.x; r.y = v.y; return r; }
 #else
@@ -784,7 +785,11 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
             val.x = sacc[wp00] + sacc[wp01]; val.y = sacc[wp10] + sacc[wp11];
             gdouble* o = (gdouble*)(l < nl ? wo : dumpp);
             if constexpr (ACCUM) { double o0 = o[0], o1 = o[1]; if (!wy) { o0 = 0.0; o1 = 0.0; } val.x += o0; val.y += o1; }
-            o[0] = val.x; o[1] = val.y;
+            // y is the one stream nobody in the launch reads back (ACCUM reads a pair before it stores it, with the default policy): its
+            // 16-byte store is NON-TEMPORAL -- still ONE global_store_dwordx4 per level.  Measured (profiles/umat_store_policy_ab.txt,
+            // _pmc.txt): the launch's trace 12.5 -> 11.9 us, 8 spheres out of cache 87 -> 78 us, FETCH_SIZE -5 %, WRITE_SIZE +10 %.  x, the
+            // gathers and thickInv keep the default policy: thickInv as `nt` costs 3 us per launch.
+            { wave_d2 vv; vv.x = val.x; vv.y = val.y; __builtin_nontemporal_store(vv, (gwave_d2*)o); }
             wo += wst;
         }
         wave_fence();
