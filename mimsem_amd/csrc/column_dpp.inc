@@ -1,4 +1,4 @@
-// column_dpp.inc -- included by column_kernels.hip (same translation unit: shares CG, WS, VSCALE, RD, CV, ...).
+// column_dpp.inc -- included by column_kernels.hip (same translation unit: shares CG, plan_col, for_order, VSCALE, RD, CV, ...).
 //
 // Round 2: the column Schur path on an LDS-FREE block algebra.
 //
@@ -1175,32 +1175,11 @@ template <class A> void fill_geo(const mimsem_ctx* c, A& a, int waves_per_simd =
 
 bool sweep_supported(const mimsem_ctx* c) { return c->es.n >= 1 && c->es.n <= 4 && c->nk >= 2; }
 
-// workspace of the fused path: L, the Thomas factors, three interface / level vectors
-long long sweep_ws_doubles(const mimsem_ctx* c) {
-    const long long nEl = c->nEl, nk = c->nk, n2 = c->es.n2e, nn = n2*n2;
-    return nEl*nk*(3*nn + 2*nn + 2*n2) + 3*nEl*nk*n2;
-}
-
-struct SweepWS { double *L, *G, *D, *y, *rl, *geta, *fu2; };
-int sweep_carve(mimsem_ctx* c, SweepWS& w) {
-    const long long nEl = c->nEl, nk = c->nk, n2 = c->es.n2e, nn = n2*n2;
-    int rc = c->ensure_col(sweep_ws_doubles(c));
-    if (rc) return rc;
-    double* p = c->d_col;
-    w.L = p; p += nEl*nk*3*nn; w.G = p; p += nEl*nk*nn; w.D = p; p += nEl*nk*nn; w.y = p; p += nEl*nk*n2;
-    w.rl = p; p += nEl*nk*n2; w.geta = p; p += nEl*nk*n2; w.fu2 = p; p += nEl*nk*n2;
-    return MIMSEM_OK;
-}
+using mimsem::SweepWS;
 
 int launch_sweep(mimsem_ctx* c, const SweepArgs& a) {
     const unsigned grid = walk_task_grid(a.nEl, a.nchunk);
-    switch (c->es.n) {
-    case 1: hipLaunchKernelGGL((k_schur_sweep<1>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL((k_schur_sweep<2>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL((k_schur_sweep<3>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL((k_schur_sweep<4>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_schur_sweep<N()>), dim3(grid), dim3(64), 0, c->stream, a); })) return rc;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
@@ -1224,7 +1203,6 @@ int launch_thomas_dpp(mimsem_ctx* c, int refine, const double* L, const double* 
         // fallback kernel as before)
         if (refine > 0xff) refine = 0xff;
         if (c->pivot_fallback == 1 && !(exp_env("MIMSEM_THOMAS_TRIAGE") && atoi(exp_env("MIMSEM_THOMAS_TRIAGE")) == 0)) refine |= 0x100;
-#define MIMSEM_TD2(N) case N: hipLaunchKernelGGL((k_thomas_dpp2<N>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, refine, L, f, d, G, D, y, c->d_colstat, c->d_colratio); break;
         // A/B forms (round 5, profiles/r05_thomas_wps_ab.txt): order 3 at TWO wavefronts per SIMD (one slot of look-ahead less: 252 VGPRs, no
         // spill, all 1 728 wavefronts of 3 456 columns resident at once) -- 229 us against 205 us: the kernel moves 887 MB per launch and is
         // bound by that traffic (4.2-4.3 TB/s; a plain copy reaches 4.9), not by residency; order 4 with two slots instead of three (no spill)
@@ -1235,33 +1213,20 @@ int launch_thomas_dpp(mimsem_ctx* c, int refine, const double* L, const double* 
         else if (c->es.n2e == 16 && depth == 2) hipLaunchKernelGGL((k_thomas_dpp2<16, 2, 1>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, refine, L, f, d, G, D, y, c->d_colstat, c->d_colratio);
         else
 #endif
-        switch (c->es.n2e) {
-        MIMSEM_TD2(1) MIMSEM_TD2(4) MIMSEM_TD2(9) MIMSEM_TD2(16)
-        default: return MIMSEM_ERR_UNSUPPORTED;
-        }
-#undef MIMSEM_TD2
+        if (int rc = for_order<1, 4, 9, 16>(c->es.n2e, [&](auto N) {
+                hipLaunchKernelGGL((k_thomas_dpp2<N()>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, refine, L, f, d, G, D, y, c->d_colstat, c->d_colratio); })) return rc;
         MIMSEM_HIP_TRY(hipGetLastError());
         return MIMSEM_OK;
     }
     const unsigned grid = (unsigned)((c->nEl + 3)/4);
-#define MIMSEM_TD(N) case N: hipLaunchKernelGGL((k_thomas_dpp<N>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, refine, L, f, d, G, D, y, c->d_colstat, c->d_colratio); break;
-    switch (c->es.n2e) {
-    MIMSEM_TD(1) MIMSEM_TD(4) MIMSEM_TD(9) MIMSEM_TD(16)
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
-#undef MIMSEM_TD
+    if (int rc = for_order<1, 4, 9, 16>(c->es.n2e, [&](auto N) {
+            hipLaunchKernelGGL((k_thomas_dpp<N()>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, refine, L, f, d, G, D, y, c->d_colstat, c->d_colratio); })) return rc;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
 int launch_backsub(mimsem_ctx* c, const BacksubArgs& a) {
     const unsigned grid = walk_task_grid(a.nEl, a.nchunk);
-    switch (c->es.n) {
-    case 1: hipLaunchKernelGGL((k_schur_backsub<1>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    case 2: hipLaunchKernelGGL((k_schur_backsub<2>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    case 3: hipLaunchKernelGGL((k_schur_backsub<3>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    case 4: hipLaunchKernelGGL((k_schur_backsub<4>), dim3(grid), dim3(64), 0, c->stream, a); break;
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_schur_backsub<N()>), dim3(grid), dim3(64), 0, c->stream, a); })) return rc;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
@@ -1269,7 +1234,7 @@ int launch_backsub(mimsem_ctx* c, const BacksubArgs& a) {
 // the Helmholtz operator alone (mimsem_column_helmholtz_blocks)
 int sweep_helmholtz(mimsem_ctx* c, double dt, const double* theta, const double* rho, const double* eta, const double* pi, double* out) {
     SweepWS w;
-    int rc = sweep_carve(c, w);
+    int rc = plan_col(c, w);
     if (rc) return rc;
     SweepArgs a{};
     fill_geo(c, a);
@@ -1283,7 +1248,7 @@ int sweep_helmholtz(mimsem_ctx* c, double dt, const double* theta, const double*
 int sweep_solve_eta(mimsem_ctx* c, double dt, const double* theta, const double* rho, const double* eta, const double* pi,
                     double* F_u, double* F_rho, double* F_eta, double* F_pi, double* d_u, double* d_rho, double* d_eta, double* d_pi) {
     SweepWS w;
-    int rc = sweep_carve(c, w);
+    int rc = plan_col(c, w);
     if (rc) return rc;
     SweepArgs a{};
     fill_geo(c, a);
@@ -1296,10 +1261,7 @@ int sweep_solve_eta(mimsem_ctx* c, double dt, const double* theta, const double*
     // up to four refinement steps, each column stops once its correction is below 1e-10 of its solution (most stop after the first): the
     // sweep eliminates block by block without pivoting across blocks; on 3 456 rough random columns the worst relative residual is
     // 1e-5 after the sweep and at LAPACK's level (eps |L| |d| / |f|) after one or two steps -- scripts/diag_thomas_residual.py
-    int nref = 4;
-    if (const char* ev = getenv("MIMSEM_REFINE")) nref = std::max(0, atoi(ev));
-    if (getenv("MIMSEM_NO_REFINE")) nref = 0;
-    if ((rc = launch_thomas_dpp(c, nref, w.L, F_pi, d_pi, w.G, w.D, w.y, true))) return rc;
+    if ((rc = launch_thomas_dpp(c, refine_steps(), w.L, F_pi, d_pi, w.G, w.D, w.y, true))) return rc;
     if ((rc = launch_band_lu_flagged(c, 1, w.L, false, F_pi, d_pi))) return rc;       // (opt-in: flagged columns by a pivoted band LU, column_pivot.inc)
     BacksubArgs b{};
     fill_geo(c, b, exp_env("MIMSEM_BACKSUB_WPS") ? std::max(1, atoi(exp_env("MIMSEM_BACKSUB_WPS"))) : 2);      // 192 VGPRs: two waves per SIMD, the second hides the first one's memory waits (A/B knob)

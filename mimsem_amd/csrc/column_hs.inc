@@ -1,4 +1,4 @@
-// column_hs.inc -- included at the end of column_kernels.hip (same translation unit: shares CG, BA, WS, bmm, ...).
+// column_hs.inc -- included at the end of column_kernels.hip (same translation unit: shares CG, BA, Band, plan_col, for_order, bmm, ...).
 //
 // The column rows of the Strang / Held-Suarez path (SURVEY 8(a) C2-C6 remainder):
 //   * AssembleLinearWithRho2_up / AssembleLinCon2_up   eul/VertOps.cpp:1415-1561  (test functions at departure points)
@@ -116,7 +116,6 @@ int up_blocks_into(mimsem_ctx* c, int colop, const double* rho, double* M, doubl
 }
 
 // ---- block-banded matrices: blocks [e][r][b] (n2 x n2 each), block column = r + lo + b, b in [0, nb) ----
-struct Band { double* p; int nr, nc, lo, nb; };
 
 // one workgroup per block row (e, r) of C: the A.nb blocks of A's row and the A.nb x B.nb blocks of B they meet are staged in LDS
 // (coalesced 648-B reads at p = 3), every output entry is formed from LDS in the same order as the entry-per-thread version below
@@ -300,45 +299,38 @@ __global__ __launch_bounds__(256) void k_penta_to_tri(int nEl, int nk, int n2, i
     T[x] = v;
 }
 
-struct Schur3 { Band Muinv, Mrhoinv, Mrt, Npiinv, GG, Drho, Nrt, QM, GN, DDM, L; double *tA, *tB, *tC; double* Tm = nullptr; bool Tm_done = false; };
+// the plan of the chain (col_workspace.hpp) and what its launches have done; `dpp`: the path the plan was carved for
+struct Schur3 : mimsem::Schur3WS { bool dpp = false; bool Tm_done = false; };
+
+// the launch of the three product kernels on the DPP row algebra (column_schur3_dpp.inc)
+int launch_s3_chain(mimsem_ctx* c, Schur3& S, double hdt) {
+    S3Args a{};
+    a.nEl = c->nEl; a.nk = c->nk; a.hdt = hdt; a.gam = RD/CV;
+    a.B = S.B.p; a.Binv = S.Mrhoinv.p; a.Npiinv = S.Npiinv.p; a.Ainv = S.Ainv.p; a.Muinv = S.Muinv.p; a.Cg = S.VBA.p; a.Cv = S.Cv.p;
+    a.Brinv = S.Brinv.p; a.T = S.T.p; a.Rr = S.Rr.p; a.Brt = S.Brt.p; a.Brtinv = S.Brtinv.p; a.Bth = S.Bth.p;
+    a.X = S.X.p; a.Nrt = S.Nrt.p; a.GN = S.GN.p; a.GG = S.GG.p; a.QM = S.QM.p; a.Drho = S.Drho.p; a.DDM = S.DDM.p; a.L = S.L.p;
+    a.Tm = S.Tm; a.K = (c->nk + 1)/2; S.Tm_done = S.Tm != nullptr;
+    return for_order<1, 4, 9, 16>(c->es.n2e, [&](auto N) { return launch_s3<N()>(c, a); });
+}
 
 int schur3_operator(mimsem_ctx* c, double dt, unsigned flags, const double* theta, const double* velz, const double* rho,
-                    const double* rt, const double* pi, Schur3& S, WS& w) {
-    const int nk = c->nk, nm = nk - 1, n2 = c->es.n2e, nn = n2*n2, nEl = c->nEl, mp12 = c->es.mp12;
+                    const double* rt, const double* pi, Schur3& S) {
     const double hdt = 0.5*dt;
     int rc;
-    double* cq = w.take((long long)nEl*(nk + 1)*2*mp12);
-    double* tmpM = w.take((long long)nEl*(nk + 1)*2*nn*2);
-    auto band = [&](int nr, int nc, int lo, int nb) { Band b; b.nr = nr; b.nc = nc; b.lo = lo; b.nb = nb; b.p = w.take((long long)nEl*nr*nb*nn); return b; };
-    Band B = band(nk, nk, 0, 1), Ainv = band(nm, nm, 0, 1), V01 = band(nm, nk, 0, 2), V10 = band(nk, nm, -1, 2);
-    S.Muinv = band(nm, nm, 0, 1); S.Mrhoinv = band(nk, nk, 0, 1); S.Mrt = B; S.Npiinv = band(nk, nk, 0, 1);
-    S.tA = w.take((long long)nEl*nk*n2); S.tB = w.take((long long)nEl*nk*n2); S.tC = w.take((long long)nEl*nk*n2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
-    const bool s3_dpp = (n2 == 1 || n2 == 4 || n2 == 9 || n2 == 16) && !exp_env("MIMSEM_SCHUR3_BANDS");
+    double *cq = S.cq, *tmpM = S.tmpM;
+    const Band &B = S.B, &Ainv = S.Ainv, &V01 = S.V01, &V10 = S.V10, &VBA = S.VBA;
+    const bool s3_dpp = S.dpp;
     if (s3_dpp && c->es.n <= 4 && !exp_env("MIMSEM_SCHUR3_WIDE_FACTORS")) {
         // orders 1..3: every diagonal factor block assembled / inverted on the row algebra (two launches), then the three product launches
-        Band VBA = band(nk, nm, -1, 2), Brinv = band(nk, nk, 0, 1), T = band(nm, nm, 0, 1), Rr = band(nm, nm, 0, 1), Brt = band(nk, nk, 0, 1),
-             Brtinv = band(nk, nk, 0, 1), Bth = band(nk, nk, 0, 1), X = band(nm, nm, 0, 1);
-        Band Cv = VBA;
-        if (!(flags & MIMSEM_SCHUR3_BOX_Q)) Cv = band(nk, nm, -1, 2);
-        S.Drho = band(nk, nm, -1, 2); S.Nrt = band(nk, nk, 0, 1); S.QM = band(nk, nk, -1, 3); S.GN = band(nm, nk, 0, 2); S.GG = band(nm, nk, 0, 2);
-        S.DDM = band(nk, nm, -2, 4); S.L = band(nk, nk, -2, 5);
-        if (w.used > w.cap) return MIMSEM_ERR_STATE;
         S3FactorArgs fa{};
         fill_newton_geo(c, fa.g);
         fa.rayleigh = (flags & MIMSEM_SCHUR3_NO_RAYLEIGH) ? 0 : 1; fa.ray_param = 0.5*dt*(4.0/120.0);     // RAYLEIGH, eul/VertSolve.cpp:32, :520
         fa.cv_from_velz = (flags & MIMSEM_SCHUR3_BOX_Q) ? 0 : 1;
         fa.theta = theta; fa.velz = velz; fa.rho = rho; fa.rt = rt; fa.pi = pi;
-        fa.B = B.p; fa.Binv = S.Mrhoinv.p; fa.Npiinv = S.Npiinv.p; fa.Brinv = Brinv.p; fa.Brt = Brt.p; fa.Brtinv = Brtinv.p; fa.Bth = Bth.p;
-        fa.Ainv = Ainv.p; fa.Muinv = S.Muinv.p; fa.T = T.p; fa.Rr = Rr.p; fa.Cg = VBA.p; fa.Cv = Cv.p;
+        fa.B = B.p; fa.Binv = S.Mrhoinv.p; fa.Npiinv = S.Npiinv.p; fa.Brinv = S.Brinv.p; fa.Brt = S.Brt.p; fa.Brtinv = S.Brtinv.p; fa.Bth = S.Bth.p;
+        fa.Ainv = Ainv.p; fa.Muinv = S.Muinv.p; fa.T = S.T.p; fa.Rr = S.Rr.p; fa.Cg = VBA.p; fa.Cv = S.Cv.p;
         if ((rc = launch_s3_factors(c, fa))) return rc;
-        S3Args a{};
-        a.nEl = nEl; a.nk = nk; a.hdt = hdt; a.gam = RD/CV;
-        a.B = B.p; a.Binv = S.Mrhoinv.p; a.Npiinv = S.Npiinv.p; a.Ainv = Ainv.p; a.Muinv = S.Muinv.p; a.Cg = VBA.p; a.Cv = Cv.p;
-        a.Brinv = Brinv.p; a.T = T.p; a.Rr = Rr.p; a.Brt = Brt.p; a.Brtinv = Brtinv.p; a.Bth = Bth.p;
-        a.X = X.p; a.Nrt = S.Nrt.p; a.GN = S.GN.p; a.GG = S.GG.p; a.QM = S.QM.p; a.Drho = S.Drho.p; a.DDM = S.DDM.p; a.L = S.L.p;
-        a.Tm = S.Tm; a.K = (nk + 1)/2; S.Tm_done = S.Tm != nullptr;
-        return n2 == 1 ? launch_s3<1>(c, a) : (n2 == 4 ? launch_s3<4>(c, a) : (n2 == 9 ? launch_s3<9>(c, a) : launch_s3<16>(c, a)));
+        return launch_s3_chain(c, S, hdt);
     }
     if ((rc = band_fill_incidence(c, V01, 1))) return rc;              // (V01 also carries the pressure gradient below)
     if (!s3_dpp && (rc = band_fill_incidence(c, V10, 0))) return rc;
@@ -361,71 +353,46 @@ int schur3_operator(mimsem_ctx* c, double dt, unsigned flags, const double* thet
     if ((rc = band_mv(c, V01, S.tA, S.tB, 1.0, 0.0))) return rc;
     if ((rc = band_mv(c, Ainv, S.tB, S.tC, 1.0, 0.0))) return rc;
     // G_rt = 0.5dt VBA(grad)^T VB_inv(rho) VB   (:532-541)
-    Band VBA = band(nk, nm, -1, 2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = colop_blocks_into(c, MIMSEM_V_CONLIN_W, 0, S.tC, nullptr, VBA.p, cq, tmpM))) return rc;
     if (s3_dpp) {
         // round 2: the whole MatMatMult chain (:532-627) in three launches on the DPP row algebra (column_schur3_dpp.inc); the
         // banded products below (20 launches, each reading and writing whole bands) stay selectable with MIMSEM_SCHUR3_BANDS=1
-        Band Brinv = band(nk, nk, 0, 1), T = band(nm, nm, 0, 1), Rr = band(nm, nm, 0, 1), Brt = band(nk, nk, 0, 1), Brtinv = band(nk, nk, 0, 1),
-             Bth = band(nk, nk, 0, 1), X = band(nm, nm, 0, 1);
-        Band Cv = VBA;
-        if (!(flags & MIMSEM_SCHUR3_BOX_Q)) Cv = band(nk, nm, -1, 2);
-        S.Drho = band(nk, nm, -1, 2); S.Nrt = band(nk, nk, 0, 1); S.QM = band(nk, nk, -1, 3); S.GN = band(nm, nk, 0, 2); S.GG = band(nm, nk, 0, 2);
-        S.DDM = band(nk, nm, -2, 4); S.L = band(nk, nk, -2, 5);
-        if (w.used > w.cap) return MIMSEM_ERR_STATE;
-        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO_INV, 0, rho, nullptr, Brinv.p, cq, tmpM))) return rc;
-        if ((rc = colop_blocks_into(c, MIMSEM_V_LINEAR_THETA, 0, theta, nullptr, T.p, cq, tmpM))) return rc;
-        if ((rc = colop_blocks_into(c, MIMSEM_V_LINEAR_RT, MIMSEM_FLAG_VERT, rho, nullptr, Rr.p, cq, tmpM))) return rc;
-        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO, 0, rt, nullptr, Brt.p, cq, tmpM))) return rc;
-        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO_INV, 0, rt, nullptr, Brtinv.p, cq, tmpM))) return rc;
-        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_THETA, 0, theta, nullptr, Bth.p, cq, tmpM))) return rc;
+        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO_INV, 0, rho, nullptr, S.Brinv.p, cq, tmpM))) return rc;
+        if ((rc = colop_blocks_into(c, MIMSEM_V_LINEAR_THETA, 0, theta, nullptr, S.T.p, cq, tmpM))) return rc;
+        if ((rc = colop_blocks_into(c, MIMSEM_V_LINEAR_RT, MIMSEM_FLAG_VERT, rho, nullptr, S.Rr.p, cq, tmpM))) return rc;
+        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO, 0, rt, nullptr, S.Brt.p, cq, tmpM))) return rc;
+        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO_INV, 0, rt, nullptr, S.Brtinv.p, cq, tmpM))) return rc;
+        if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_THETA, 0, theta, nullptr, S.Bth.p, cq, tmpM))) return rc;
         if (!(flags & MIMSEM_SCHUR3_BOX_Q))
-            if ((rc = colop_blocks_into(c, MIMSEM_V_CONLIN_W, 0, velz, nullptr, Cv.p, cq, tmpM))) return rc;
-        S3Args a{};
-        a.nEl = nEl; a.nk = nk; a.hdt = hdt; a.gam = RD/CV;
-        a.B = B.p; a.Binv = S.Mrhoinv.p; a.Npiinv = S.Npiinv.p; a.Ainv = Ainv.p; a.Muinv = S.Muinv.p; a.Cg = VBA.p; a.Cv = Cv.p;
-        a.Brinv = Brinv.p; a.T = T.p; a.Rr = Rr.p; a.Brt = Brt.p; a.Brtinv = Brtinv.p; a.Bth = Bth.p;
-        a.X = X.p; a.Nrt = S.Nrt.p; a.GN = S.GN.p; a.GG = S.GG.p; a.QM = S.QM.p; a.Drho = S.Drho.p; a.DDM = S.DDM.p; a.L = S.L.p;
-        a.Tm = S.Tm; a.K = (nk + 1)/2; S.Tm_done = S.Tm != nullptr;
-        return n2 == 1 ? launch_s3<1>(c, a) : (n2 == 4 ? launch_s3<4>(c, a) : (n2 == 9 ? launch_s3<9>(c, a) : launch_s3<16>(c, a)));
+            if ((rc = colop_blocks_into(c, MIMSEM_V_CONLIN_W, 0, velz, nullptr, S.Cv.p, cq, tmpM))) return rc;
+        return launch_s3_chain(c, S, hdt);
     }
-    Band VAB = band(nm, nk, 0, 2), Brinv = band(nk, nk, 0, 1), t_a = band(nm, nk, 0, 2), G_rt = band(nm, nk, 0, 2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
+    // the banded products: their intermediates are the plan's wide-path members
+    const Band &VAB = S.VAB, &Brinv = S.Brinv, &t_a = S.t_a, &G_rt = S.G_rt, &DTV1 = S.DTV1, &AinvDTV1 = S.AinvDTV1, &T = S.T, &G_pi = S.G_pi,
+               &Rr = S.Rr, &X = S.X, &DX = S.DX, &Brt = S.Brt, &D_rt = S.D_rt, &t_d = S.t_d, &Bth = S.Bth, &Q = S.Q, &GNN = S.GNN, &QMD = S.QMD,
+               &DD = S.DD, &DGG = S.DGG;
     if ((rc = band_transpose(c, VAB, VBA))) return rc;
     if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO_INV, 0, rho, nullptr, Brinv.p, cq, tmpM))) return rc;
     if ((rc = band_mul(c, t_a, VAB, Brinv, 1.0))) return rc;
     if ((rc = band_mul(c, G_rt, t_a, B, hdt))) return rc;
     // G_pi = 0.5dt VA(theta) VA_inv V01 VB      (:543-555)
-    Band DTV1 = band(nm, nk, 0, 2), AinvDTV1 = band(nm, nk, 0, 2), T = band(nm, nm, 0, 1), G_pi = band(nm, nk, 0, 2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = band_mul(c, DTV1, V01, B, 1.0))) return rc;
     if ((rc = band_mul(c, AinvDTV1, Ainv, DTV1, 1.0))) return rc;
     if ((rc = colop_blocks_into(c, MIMSEM_V_LINEAR_THETA, 0, theta, nullptr, T.p, cq, tmpM))) return rc;
     if ((rc = band_mul(c, G_pi, T, AinvDTV1, hdt))) return rc;
     // D_rho = 0.5dt VB V10 VA_inv VA(rho)       (:557-569)
-    Band Rr = band(nm, nm, 0, 1), X = band(nm, nm, 0, 1), DX = band(nk, nm, -1, 2);
-    S.Drho = band(nk, nm, -1, 2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = colop_blocks_into(c, MIMSEM_V_LINEAR_RT, MIMSEM_FLAG_VERT, rho, nullptr, Rr.p, cq, tmpM))) return rc;
     if ((rc = band_mul(c, X, Ainv, Rr, 1.0))) return rc;
     if ((rc = band_mul(c, DX, V10, X, 1.0))) return rc;
     if ((rc = band_mul(c, S.Drho, B, DX, hdt))) return rc;
     // D_rt = 0.5dt VB(rt) V10                   (:571-575)
-    Band Brt = band(nk, nk, 0, 1), D_rt = band(nk, nm, -1, 2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO, 0, rt, nullptr, Brt.p, cq, tmpM))) return rc;
     if ((rc = band_mul(c, D_rt, Brt, V10, hdt))) return rc;
     // N_rt = -R/cv VB VB_inv(rt) VB             (:577-585)
-    Band t_d = band(nk, nk, 0, 1);
-    S.Nrt = band(nk, nk, 0, 1);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_RHO_INV, 0, rt, nullptr, Brt.p, cq, tmpM))) return rc;   // Brt now holds the inverse
     if ((rc = band_mul(c, t_d, Brt, B, 1.0))) return rc;
     if ((rc = band_mul(c, S.Nrt, B, t_d, -1.0*RD/CV))) return rc;
     // Q_rt_rho = 0.5dt VBA(velz) VA_inv V01 VB(theta)   (:587-599)
-    Band Bth = band(nk, nk, 0, 1), Q = band(nk, nk, -1, 3);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = colop_blocks_into(c, MIMSEM_V_CONST_THETA, 0, theta, nullptr, Bth.p, cq, tmpM))) return rc;
     if ((rc = band_mul(c, DTV1, V01, Bth, 1.0))) return rc;
     if ((rc = band_mul(c, AinvDTV1, Ainv, DTV1, 1.0))) return rc;
@@ -434,10 +401,6 @@ int schur3_operator(mimsem_ctx* c, double dt, unsigned flags, const double* thet
         if ((rc = colop_blocks_into(c, MIMSEM_V_CONLIN_W, 0, velz, nullptr, VBA.p, cq, tmpM))) return rc;
     if ((rc = band_mul(c, Q, VBA, AinvDTV1, hdt))) return rc;
     // products of the Schur complement           (:601-627)
-    S.QM = band(nk, nk, -1, 3); S.GN = band(nm, nk, 0, 2); S.GG = band(nm, nk, 0, 2);
-    Band GNN = band(nm, nk, 0, 2), QMD = band(nk, nm, -2, 4), DD = band(nk, nm, -2, 4), DGG = band(nk, nk, -2, 5);
-    S.DDM = band(nk, nm, -2, 4); S.L = band(nk, nk, -2, 5);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
     if ((rc = band_mul(c, S.QM, Q, S.Mrhoinv, 1.0))) return rc;
     if ((rc = band_mul(c, S.GN, G_pi, S.Npiinv, 1.0))) return rc;
     if ((rc = band_mul(c, GNN, S.GN, S.Nrt, 1.0))) return rc;
@@ -448,12 +411,6 @@ int schur3_operator(mimsem_ctx* c, double dt, unsigned flags, const double* thet
     if ((rc = band_mul(c, DGG, S.DDM, S.GG, 1.0))) return rc;
     if ((rc = band_lincomb(c, S.L, -1.0, DGG, 1.0, S.Mrt))) return rc;
     return MIMSEM_OK;
-}
-
-long long schur3_ws_doubles(const mimsem_ctx* c) {
-    const long long nEl = c->nEl, nk = c->nk + 1, nn = (long long)c->es.n2e*c->es.n2e, n2 = c->es.n2e, mp12 = c->es.mp12;
-    // bands: ~ (1+1+2+2 +1+1+1 +2+2+1+2+2 +2+2+1+2 +1+1+2+2 +1+2 +1+1 +1+3 +3+2+2+2+4+4+5+4+5) = 72 block-diagonals of nk
-    return nEl*nk*(80*nn + 2*mp12 + 4*nn + 16*n2) + nEl*((nk + 2)/2)*(4LL*4*nn + 2*2*n2 + 4*nn + 4*nn /* D^-1 of the super-blocks */);
 }
 
 }  // namespace
@@ -500,11 +457,10 @@ int mimsem_column_diag_theta_up(mimsem_ctx* c, double dt, const double* rho, con
                                 const double* uh, long long uhs, double* theta) {
     if (!c || !rho || !rt || !uh || !theta) return MIMSEM_ERR_ARG;
     const int nk = c->nk, n2 = c->es.n2e, nn = n2*n2, nEl = c->nEl;
-    int rc = c->ensure_col(colop_ws_doubles(c) + (long long)nEl*(nk + 1)*(3LL*nn + 2LL*n2));
+    mimsem::ColopWS w;
+    int rc = plan_col(c, w, true);
     if (rc) return rc;
-    const long long nbmax = (long long)nEl*(nk + 1)*2;
-    double* cq = c->d_col; double* tmpM = cq + nbmax*c->es.mp12; double* M = tmpM + 2*nbmax*nn;
-    double* frt = M + (long long)nEl*(nk + 1)*2*nn;
+    double *cq = w.cq, *tmpM = w.tmpM, *M = w.M, *frt = w.frt;
     c->col_param = dt; c->col_uh = uh; c->col_uhs = uhs;
     rc = colop_blocks_into(c, MIMSEM_V_LINCON2_UP, 0, nullptr, nullptr, M, cq, tmpM);
     if (!rc) rc = stored_apply(c, MIMSEM_V_LINCON2_UP, 0, M, rt, frt);
@@ -521,9 +477,10 @@ int mimsem_column_temp_forcing_hs(mimsem_ctx* c, const double* lat, const double
     if (!c || !lat || !exner || !theta || !rho || !out) return MIMSEM_ERR_ARG;
     const CG g = make_cg(c);
     const int nk = c->nk;
-    int rc = c->ensure_col((long long)c->nEl*nk*g.mp12);
+    mimsem::QuadWS w;
+    int rc = plan_col(c, w);
     if (rc) return rc;
-    double* rq = c->d_col;
+    double* rq = w.q;
     if ((rc = each(c, (long long)c->nEl*nk*g.mp12, [=] __device__(long long i) {
         const int q = (int)(i%g.mp12); long long t = i/g.mp12;
         const int k = (int)(t%nk), e = (int)(t/nk);
@@ -568,27 +525,26 @@ int mimsem_column_solve_schur_3(mimsem_ctx* c, double dt, unsigned flags,
     const int nk = c->nk, n2 = c->es.n2e, nn = n2*n2, nEl = c->nEl;
     const int m = 2*n2, K = (nk + 1)/2;
     if ((size_t)(3*m*m + 2*m)*sizeof(double) > 160*1024) return MIMSEM_ERR_UNSUPPORTED;     // p = 7
-    int rc = c->ensure_col(schur3_ws_doubles(c));
-    if (rc) return rc;
-    WS w{c, c->d_col, 0, c->col_doubles};
+    // the path of the call, known on entry: the bands on the DPP row algebra or by banded products; the five bands eliminated directly or
+    // through the 2x2 super-blocks, whose row-per-lane sweep (2x2 / 3x3 faces, m = 8 / 18) keeps its factors
+    const bool dpp_sizes = n2 == 1 || n2 == 4 || n2 == 9 || n2 == 16;
+    const bool penta = dpp_sizes && !getenv("MIMSEM_SCHUR3_SUPERBLOCKS");
+    const bool rows = (m == 8 || m == 18) && !exp_env("MIMSEM_THOMAS_WG");
     Schur3 S;
-    S.Tm = w.take((long long)nEl*K*3*m*m);            // the super-block form of L: written by k_s3_row itself on the DPP path
-    if ((rc = schur3_operator(c, dt, flags, theta, velz, rho, rt, pi, S, w))) return rc;
+    S.dpp = dpp_sizes && !exp_env("MIMSEM_SCHUR3_BANDS");
+    int rc = plan_col(c, S, S.dpp, !(flags & MIMSEM_SCHUR3_BOX_Q), penta, rows);
+    if (rc) return rc;
+    if ((rc = schur3_operator(c, dt, flags, theta, velz, rho, rt, pi, S))) return rc;
     if (L_out) MIMSEM_HIP_TRY(hipMemcpyAsync(L_out, S.L.p, (size_t)nEl*nk*5*nn*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     // residual updates (:632-639)
     if ((rc = band_mv(c, S.QM, F_rho, F_rt, -1.0, 1.0))) return rc;
     if ((rc = band_mv(c, S.GN, F_pi, F_u, -1.0, 1.0))) return rc;
     if ((rc = band_mv(c, S.DDM, F_u, F_rt, -1.0, 1.0))) return rc;
     // F_rt = -F_rt ; L d_rt = F_rt   (:652-653)
-    if ((n2 == 1 || n2 == 4 || n2 == 9 || n2 == 16) && !getenv("MIMSEM_SCHUR3_SUPERBLOCKS")) {
+    if (penta) {
         // round 4: the five bands eliminated directly on the DPP rows (column_penta.inc), refinement and status in the same launch
-        double* Fac = w.take((long long)nEl*nk*4*nn); double* yws = w.take((long long)nEl*nk*n2);
-        if (w.used > w.cap) return MIMSEM_ERR_STATE;
         if ((rc = each(c, (long long)nEl*nk*n2, [=] __device__(long long i) { F_rt[i] *= -1.0; }))) return rc;
-        int nref = 4;
-        if (const char* ev = getenv("MIMSEM_REFINE")) nref = std::max(0, atoi(ev));
-        if (getenv("MIMSEM_NO_REFINE")) nref = 0;
-        if ((rc = launch_penta_dpp(c, nref, S.L.p, true, F_rt, d_rt, Fac, yws))) return rc;
+        if ((rc = launch_penta_dpp(c, refine_steps(), S.L.p, true, F_rt, d_rt, S.Fac, S.yws))) return rc;
         if ((rc = launch_band_lu_flagged(c, 2, S.L.p, true, F_rt, d_rt))) return rc;
         c->colstat_valid = true;
         if ((rc = band_mv(c, S.GG, d_rt, F_u, -1.0, -1.0))) return rc;
@@ -599,14 +555,9 @@ int mimsem_column_solve_schur_3(mimsem_ctx* c, double dt, unsigned flags,
         return band_mv(c, S.Mrhoinv, F_rho, d_rho, 1.0, 0.0);
     }
     // (rounds 1-3, kept for orders >= 5 and as the A/B: MIMSEM_SCHUR3_SUPERBLOCKS=1) through the 2x2 super-block tridiagonal form
-    double* Tm = S.Tm;
-    double* fpad = w.take((long long)nEl*K*m); double* dpad = w.take((long long)nEl*K*m);
-    double* Gws = w.take((long long)nEl*K*m*m); double* yws = w.take((long long)nEl*K*m);
     // 2x2 / 3x3 faces (m = 8 / 18): the row-per-lane sweep of k_block_thomas_rows (16 / 32 lanes per column) keeps its factors, and the
     // refinement step is substitution only; other orders use the workgroup-per-column kernel twice
-    const bool rows = (m == 8 || m == 18) && !exp_env("MIMSEM_THOMAS_WG");
-    double* Dinv = rows ? w.take((long long)nEl*K*m*m) : nullptr;
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
+    double *Tm = S.Tm, *fpad = S.fpad, *dpad = S.dpad, *Gws = S.Gws, *yws = S.yws, *Dinv = S.Dinv;
     auto sweep = [&](bool first) -> int {
         if (rows && first) {
             if (m == 8) hipLaunchKernelGGL((k_block_thomas_rows<8, 16>), dim3((unsigned)((nEl + 3)/4)), dim3(64), 0, c->stream, nEl, K, Tm, fpad, dpad, Gws, yws, Dinv);
@@ -643,9 +594,9 @@ int mimsem_column_solve_schur_3(mimsem_ctx* c, double dt, unsigned flags,
         const int a = (int)(i%(nk*n2)), e = (int)(i/(nk*n2));
         d_rt[i] = dpad[(size_t)e*K*m + a];
     }))) return rc;
-    if (!getenv("MIMSEM_NO_REFINE")) {
+    if (refine_wide()) {
         // one step of iterative refinement (see block_thomas_refined): r = F_rt - L d_rt, d_rt += solve(r)
-        double* rr = S.tA;
+        double* rr = S.rr;
         MIMSEM_HIP_TRY(hipMemcpyAsync(rr, F_rt, (size_t)nEl*nk*n2*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         if ((rc = band_mv(c, S.L, d_rt, rr, -1.0, 1.0))) return rc;
         if ((rc = each(c, (long long)nEl*K*m, [=] __device__(long long i) {

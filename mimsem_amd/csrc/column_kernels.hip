@@ -16,6 +16,7 @@
 #include <cstring>
 #include <type_traits>
 #include "ctx.hpp"
+#include "col_workspace.hpp"
 
 #define RD 287.0
 #define CV 717.5
@@ -24,6 +25,45 @@
 #define VSCALE 1.0e+8      /* eul/VertOps.cpp:21 */
 
 namespace {
+
+using mimsem::BA; using mimsem::Band; using mimsem::ColArena; using mimsem::ColDims;
+
+// the one dispatch on the order: f(std::integral_constant<int, N>) for the listed N that equals n, so that a site instantiates exactly the
+// templates it lists (block sizes are listed as n2e = n*n).  Returns f's status (MIMSEM_OK where f returns nothing), or
+// MIMSEM_ERR_UNSUPPORTED for an n that is not listed; hipGetLastError stays with the caller.
+template <int... Ns, class F>
+int for_order(int n, F&& f) {
+    int rc = MIMSEM_ERR_UNSUPPORTED;
+    auto hit = [&](auto N) {
+        if constexpr (std::is_void_v<decltype(f(N))>) { f(N); rc = MIMSEM_OK; } else rc = f(N);
+        return true;
+    };
+    (void)((n == Ns && hit(std::integral_constant<int, Ns>{})) || ...);
+    return rc;
+}
+
+// the one way to the column workspace: the plan (col_workspace.hpp) runs once to count, d_col grows to that (MIMSEM_ERR_STATE inside a
+// capture), and the plan runs again on d_col.  `path`: the flags of the plan's carve().
+template <class Plan, class... Path>
+int plan_col(mimsem_ctx* c, Plan& p, Path... path) {
+    const ColDims d{c->nEl, c->nk, c->es.n2e, c->es.mp12};
+    ColArena count;
+    p.carve(count, d, path...);
+    if (count.bad) return MIMSEM_ERR_ARG;
+    if (int rc = c->ensure_col(count.off)) return rc;
+    ColArena a(c->d_col);
+    p.carve(a, d, path...);
+    return MIMSEM_OK;
+}
+
+// refinement steps of a column solve, read per call (tests compare settings in one process).  The DPP solves allow up to four per column,
+// MIMSEM_REFINE=n overrides, MIMSEM_NO_REFINE zeroes; the wide paths do one step unless MIMSEM_NO_REFINE is set and ignore MIMSEM_REFINE.
+int refine_steps() {
+    int nref = 4;
+    if (const char* ev = getenv("MIMSEM_REFINE")) nref = std::max(0, atoi(ev));
+    return getenv("MIMSEM_NO_REFINE") ? 0 : nref;
+}
+bool refine_wide() { return !getenv("MIMSEM_NO_REFINE"); }
 
 template <class F>
 __global__ __launch_bounds__(256) void k_each(long long n, F f) {
@@ -596,18 +636,8 @@ int mimsem_block_inverse_inplace(mimsem_ctx* c, long long nblocks, int n, double
 
 namespace {
 
-// workspace carving
-struct WS {
-    mimsem_ctx* c; double* base; long long used, cap;
-    double* take(long long n) { double* p = base + used; used += n; return p; }
-};
-
-int flat_mm_impl(mimsem_ctx* c, long long nb, const double* A, const double* B, double* C);   // defined after bmm
-// C[b] = A[b] . B[b] for nb independent n x n blocks
-int flat_mm(mimsem_ctx* c, long long nb, int n, const double* A, const double* B, double* C) {
-    (void)n;
-    return flat_mm_impl(c, nb, A, B, C);
-}
+// C[b] = A[b] . B[b] for nb independent n2e x n2e blocks (defined after bmm)
+int flat_mm(mimsem_ctx* c, long long nb, const double* A, const double* B, double* C);
 
 bool colop_is_inverse(int colop) {
     return colop == MIMSEM_V_CONST_INV || colop == MIMSEM_V_CONST_RHO_INV || colop == MIMSEM_V_LINEAR_INV ||
@@ -637,9 +667,9 @@ int colop_blocks_into(mimsem_ctx* c, int colop, unsigned flags, const double* f1
         else if ((rc = coef_block_pass(c, MIMSEM_V_CONST, 0, nullptr, nullptr, Bm, nr, 1))) return rc;     // B
         const double* Binv = tmpM;
         double* t1 = M;                                                        // Binv.B lands in the output, then B.(Binv.B)
-        if ((rc = flat_mm(c, nb, n2, Binv, Bm, t1))) return rc;
+        if ((rc = flat_mm(c, nb, Binv, Bm, t1))) return rc;
         double* t2 = tmpM;                                                     // Binv no longer needed
-        if ((rc = flat_mm(c, nb, n2, Bm, t1, t2))) return rc;
+        if ((rc = flat_mm(c, nb, Bm, t1, t2))) return rc;
         MIMSEM_HIP_TRY(hipMemcpyAsync(M, t2, (size_t)nb*nn*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         return MIMSEM_OK;
     }
@@ -648,16 +678,16 @@ int colop_blocks_into(mimsem_ctx* c, int colop, unsigned flags, const double* f1
         if ((rc = coef_block_pass(c, MIMSEM_V_CONST_RHO, 0, f1, nullptr, s0, nr, 1))) return rc;
         if ((rc = mimsem_block_inverse_inplace(c, nb, n2, s0))) return rc;
         if ((rc = coef_block_pass(c, MIMSEM_V_CONST, 0, nullptr, nullptr, s1, nr, 1))) return rc;
-        if ((rc = flat_mm(c, nb, n2, s0, s1, M))) return rc;                  // BinvB
-        if ((rc = flat_mm(c, nb, n2, s1, M, s2))) return rc;                  // B_BinvB
+        if ((rc = flat_mm(c, nb, s0, s1, M))) return rc;                  // BinvB
+        if ((rc = flat_mm(c, nb, s1, M, s2))) return rc;                  // B_BinvB
         double* res = s2;
         if (f2) {
             MIMSEM_HIP_TRY(hipMemcpyAsync(s0, s1, (size_t)nb*nn*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
             if ((rc = mimsem_block_inverse_inplace(c, nb, n2, s0))) return rc;                       // B^-1
             if ((rc = coef_block_pass(c, MIMSEM_V_CONST_THETA, 0, f2, nullptr, s3, nr, 1))) return rc;
-            if ((rc = flat_mm(c, nb, n2, s3, s0, M))) return rc;
+            if ((rc = flat_mm(c, nb, s3, s0, M))) return rc;
             if ((rc = each(c, nb*n2, [=] __device__(long long i) { M[(i/n2)*nn + (i%n2)*(n2 + 1)] += 1.0; }))) return rc;
-            if ((rc = flat_mm(c, nb, n2, M, s2, s0))) return rc;
+            if ((rc = flat_mm(c, nb, M, s2, s0))) return rc;
             res = s0;
         }
         MIMSEM_HIP_TRY(hipMemcpyAsync(M, res, (size_t)nb*nn*sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -668,11 +698,6 @@ int colop_blocks_into(mimsem_ctx* c, int colop, unsigned flags, const double* f1
     if ((rc = coef_block_pass(c, colop, flags, f1, f2, M, nr, nw))) return rc;
     if (colop_is_inverse(colop)) return mimsem_block_inverse_inplace(c, nb, n2, M);
     return MIMSEM_OK;
-}
-
-long long colop_ws_doubles(const mimsem_ctx* c) {
-    const long long nbmax = (long long)c->nEl*(c->nk + 1)*2;
-    return nbmax*(c->es.mp12 + 3LL*c->es.n2e*c->es.n2e);
 }
 
 // y = A x (or A^T x) with A given by its stored blocks.
@@ -720,11 +745,9 @@ int mimsem_colop_blocks(mimsem_ctx* c, int colop, unsigned flags, const double* 
     if (!c || !out || colop < 0 || colop >= MIMSEM_V_COUNT) return MIMSEM_ERR_ARG;
     if (c->nk < 2 && colop >= MIMSEM_V_LINEAR) return MIMSEM_ERR_ARG;
     if (colop == MIMSEM_V_RAYLEIGH && c->nk < 4) return MIMSEM_ERR_ARG;
-    int rc = c->ensure_col(colop_ws_doubles(c));
-    if (rc) return rc;
-    const long long nbmax = (long long)c->nEl*(c->nk + 1)*2;
-    double* cq = c->d_col; double* tmpM = cq + nbmax*c->es.mp12;
-    return colop_blocks_into(c, colop, flags, f1, f2, out, cq, tmpM);
+    mimsem::ColopWS w;
+    if (int rc = plan_col(c, w, false)) return rc;
+    return colop_blocks_into(c, colop, flags, f1, f2, out, w.cq, w.tmpM);
 }
 
 int mimsem_colop_apply(mimsem_ctx* c, int colop, unsigned flags, int transpose,
@@ -732,12 +755,10 @@ int mimsem_colop_apply(mimsem_ctx* c, int colop, unsigned flags, int transpose,
     if (!c || !x || !y || colop < 0 || colop >= MIMSEM_V_COUNT) return MIMSEM_ERR_ARG;
     int rc = launch_colop_apply_mf(c, colop, flags, transpose, f1, f2, x, y);
     if (rc != MIMSEM_ERR_UNSUPPORTED) return rc;
-    if ((rc = c->ensure_col(colop_ws_doubles(c)))) return rc;
-    const long long nbmax = (long long)c->nEl*(c->nk + 1)*2;
-    const int nn = c->es.n2e*c->es.n2e;
-    double* cq = c->d_col; double* tmpM = cq + nbmax*c->es.mp12; double* M = tmpM + 2*nbmax*nn;
-    if ((rc = colop_blocks_into(c, colop, flags, f1, f2, M, cq, tmpM))) return rc;
-    return stored_apply(c, colop, transpose, M, x, y);
+    mimsem::ColopWS w;
+    if ((rc = plan_col(c, w, false))) return rc;
+    if ((rc = colop_blocks_into(c, colop, flags, f1, f2, w.M, w.cq, w.tmpM))) return rc;
+    return stored_apply(c, colop, transpose, w.M, x, y);
 }
 
 // MatMult with blocks the caller already holds (mimsem_colop_blocks output): the operators that depend on the geometry only
@@ -798,9 +819,10 @@ int mimsem_column_eos(mimsem_ctx* c, int which, const double* a, const double* b
     if ((which == 0 || which == 3) && !b) return MIMSEM_ERR_ARG;
     const CG g = make_cg(c);
     const int nk = c->nk;
-    int rc = c->ensure_col((long long)c->nEl*nk*g.mp12);
+    mimsem::QuadWS w;
+    int rc = plan_col(c, w);
     if (rc) return rc;
-    double* rtq = c->d_col;
+    double* rtq = w.q;
     if ((rc = each(c, (long long)c->nEl*nk*g.mp12, [=] __device__(long long i) {
         const int q = (int)(i%g.mp12); long long t = i/g.mp12;
         const int k = (int)(t%nk), e = (int)(t/nk);
@@ -847,9 +869,10 @@ int mimsem_colop_block_inverse_apply(mimsem_ctx* c, int op, int geom_lev0, int n
     const CG g = make_cg(c);
     const int n2 = g.n2, nn = n2*n2, nEl = c->nEl;
     const long long nb = (long long)nEl*nlev;
-    int rc = c->ensure_col(nb*(g.mp12 + nn));
+    mimsem::BlockInvWS w;
+    int rc = plan_col(c, w, (long long)nlev);
     if (rc) return rc;
-    double* cq = c->d_col; double* M = cq + nb*g.mp12;
+    double* cq = w.cq; double* M = w.M;
     const int* i2 = c->d_i2;
     const bool hmat = (op == MIMSEM_OP_WHMATINV);
     if ((rc = each(c, nb*g.mp12, [=] __device__(long long i) {
@@ -884,9 +907,6 @@ int mimsem_colop_block_inverse_apply(mimsem_ctx* c, int op, int geom_lev0, int n
 
 // ---- C6 / C5: theta diagnosis and the column Schur solve ---------------------------------------------
 namespace {
-
-// block-array view: X[e][slot][n2*n2] with ns slots per column
-struct BA { double* p; int ns; };
 
 // C[e][r] (+)= alpha * A[e][r+da] . B[e][r+db]   for r in [0,nr); out-of-range operand slots contribute 0.
 // A workgroup takes TPW consecutive (e,r) tasks, stages both operand blocks in LDS (coalesced 648-B reads at
@@ -926,7 +946,7 @@ int bmm(mimsem_ctx* c, int nr, BA C, BA A, int da, BA B, int db, double alpha, i
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
-int flat_mm_impl(mimsem_ctx* c, long long nb, const double* A, const double* B, double* C) {
+int flat_mm(mimsem_ctx* c, long long nb, const double* A, const double* B, double* C) {
     // view the flat arrays as [nEl][slots]: nb is always nEl * (slots per column) here
     const int per = (int)(nb/c->nEl);
     BA a{const_cast<double*>(A), per}, b{const_cast<double*>(B), per}, cc{C, per};
@@ -1114,13 +1134,9 @@ int launch_colop_apply_mf(mimsem_ctx* c, int colop, unsigned flags, int transpos
     const CG g = make_cg(c);
     const int mp12 = c->es.mp12, gw = mp12 <= 16 ? 16 : (mp12 <= 32 ? 32 : 64), tpb = 256/gw;
     const unsigned grid = (unsigned)((ntask + tpb - 1)/tpb);
-    switch (c->es.n) {
-#define MIMSEM_MF(N) case N: hipLaunchKernelGGL((k_colop_apply_mf<N>), dim3(grid), dim3(256), 0, c->stream, g, colop, flags, f1, f2, transpose, \
-                                                nr, nw, nxx, nyy, off, x, y); break;
-    MIMSEM_MF(1) MIMSEM_MF(2) MIMSEM_MF(3) MIMSEM_MF(4) MIMSEM_MF(5) MIMSEM_MF(6) MIMSEM_MF(7)
-#undef MIMSEM_MF
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    if (int rc = for_order<1, 2, 3, 4, 5, 6, 7>(c->es.n, [&](auto N) {
+            hipLaunchKernelGGL((k_colop_apply_mf<N()>), dim3(grid), dim3(256), 0, c->stream, g, colop, flags, f1, f2, transpose,
+                               nr, nw, nxx, nyy, off, x, y); })) return rc;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
@@ -1444,21 +1460,15 @@ int block_thomas(mimsem_ctx* c, const double* L, const double* f, double* d, dou
     const bool rows = !exp_env("MIMSEM_THOMAS_WAVE");          // row-per-lane kernel (4 columns per wavefront); the wave-per-column one stays selectable
     if (rows && !exp_env("MIMSEM_THOMAS_WG") && (n2 == 4 || n2 == 9 || n2 == 16)) {
         const unsigned grid = (unsigned)((c->nEl + 3)/4);
-        switch (n2) {
-#define MIMSEM_TRW(N) case N: hipLaunchKernelGGL((k_block_thomas_rows<N>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, L, f, d, Gws, yws, Dinv); \
-                     MIMSEM_HIP_TRY(hipGetLastError()); return MIMSEM_OK;
-        MIMSEM_TRW(4) MIMSEM_TRW(9) MIMSEM_TRW(16)
-#undef MIMSEM_TRW
-        }
+        for_order<4, 9, 16>(n2, [&](auto N) {
+            hipLaunchKernelGGL((k_block_thomas_rows<N()>), dim3(grid), dim3(64), 0, c->stream, c->nEl, c->nk, L, f, d, Gws, yws, Dinv); });
+        MIMSEM_HIP_TRY(hipGetLastError());
+        return MIMSEM_OK;
     }
     if (!exp_env("MIMSEM_THOMAS_WG")) {
-        switch (n2) {
-#define MIMSEM_TW(N) case N: hipLaunchKernelGGL((k_block_thomas_wave<N>), dim3(c->nEl), dim3(64), 0, c->stream, c->nk, L, f, d, Gws, yws, Dinv); \
-                     MIMSEM_HIP_TRY(hipGetLastError()); return MIMSEM_OK;
-        MIMSEM_TW(1) MIMSEM_TW(4) MIMSEM_TW(9) MIMSEM_TW(16)
-#undef MIMSEM_TW
-        default: break;
-        }
+        const int rc = for_order<1, 4, 9, 16>(n2, [&](auto N) {
+            hipLaunchKernelGGL((k_block_thomas_wave<N()>), dim3(c->nEl), dim3(64), 0, c->stream, c->nk, L, f, d, Gws, yws, Dinv); });
+        if (rc == MIMSEM_OK) { MIMSEM_HIP_TRY(hipGetLastError()); return MIMSEM_OK; }      // (other block sizes: the workgroup kernel below)
     }
     const int nt = std::min(256, ((nn + 63)/64)*64);
     const size_t lds = (size_t)(3*nn + 2*n2)*sizeof(double);
@@ -1492,17 +1502,14 @@ int block_thomas_refined(mimsem_ctx* c, const double* L, const double* f, double
     const bool wave = !exp_env("MIMSEM_THOMAS_WG") && (n2 == 1 || n2 == 4 || n2 == 9 || n2 == 16);
     const bool keep = Dinv && wave && (size_t)(64/n2)*nk*n2*sizeof(double) <= 48*1024;
     if ((rc = block_thomas(c, L, f, d, Gws, yws, keep ? Dinv : nullptr))) return rc;
-    if (getenv("MIMSEM_NO_REFINE")) return MIMSEM_OK;
+    if (!refine_wide()) return MIMSEM_OK;
     if ((rc = block_tridiag_residual(c, nk, n2, L, f, d, r))) return rc;
     if (keep) {                      // substitution only, with the factors of the first sweep
         const int cpw = 64/n2;
         const size_t lds = (size_t)cpw*nk*n2*sizeof(double);
         const unsigned grid = (unsigned)((nEl + cpw - 1)/cpw);
-        switch (n2) {
-#define MIMSEM_TR(N) case N: hipLaunchKernelGGL((k_block_thomas_resolve<N>), dim3(grid), dim3(64), lds, c->stream, nEl, nk, L, Dinv, Gws, r, dd); break;
-        MIMSEM_TR(1) MIMSEM_TR(4) MIMSEM_TR(9) MIMSEM_TR(16)
-#undef MIMSEM_TR
-        }
+        for_order<1, 4, 9, 16>(n2, [&](auto N) {      // (`keep` holds for these block sizes only)
+            hipLaunchKernelGGL((k_block_thomas_resolve<N()>), dim3(grid), dim3(64), lds, c->stream, nEl, nk, L, Dinv, Gws, r, dd); });
         MIMSEM_HIP_TRY(hipGetLastError());
     } else if ((rc = block_thomas(c, L, r, dd, Gws, yws))) return rc;
     return each(c, (long long)nEl*nk*n2, [=] __device__(long long i) { d[i] += dd[i]; });
@@ -2369,10 +2376,7 @@ __global__ __launch_bounds__(64) void k_eos_block_thread(CG g, const double* __r
     }
 }
 
-struct Schur {
-    // block arrays (all [nEl][ns][nn])
-    BA B, Binv, Ainv, T, Rr, X, Npi, Nrho, R2, C2, DIVl, DIVu, Gl, Gu, M1, L, G, AB0, AB1;
-    double *gpi, *geta, *rlump, *tA, *tB, *tC;
+struct Schur : mimsem::SchurWS {       // block arrays (all [nEl][ns][nn]) and vectors: the plan
     bool fused = false;            // G_pi (Gl, Gu) already built by k_schur_interfaces
     bool rows = false;             // ... by the row-per-lane kernels: DIV and the Helmholtz rows follow in k_schur_rows
     // right-hand sides of the solve (null for mimsem_column_helmholtz_blocks); the row-per-lane kernels update them on the way
@@ -2383,24 +2387,11 @@ struct Schur {
 // assemble every factor of the Helmholtz operator; see the derivation in DESIGN.md ("C5")
 int schur_assemble(mimsem_ctx* c, double dt, const double* theta, const double* rho, const double* eta,
                    const double* pi, Schur& S) {
-    const int nk = c->nk, nm = nk - 1, n2 = c->es.n2e, nn = n2*n2, nEl = c->nEl, mp12 = c->es.mp12;
+    const int nk = c->nk, nm = nk - 1, n2 = c->es.n2e, nn = n2*n2, nEl = c->nEl;
     int rc;
-    if ((rc = c->ensure_col((long long)nEl*(nk + 1)*(30LL*nn + 8LL*n2 + 4LL*mp12) + colop_ws_doubles(c)))) return rc;
-    WS w{c, c->d_col, 0, c->col_doubles};
-    double* cq = w.take((long long)nEl*(nk + 1)*2*mp12);
-    double* tmpM = w.take((long long)nEl*(nk + 1)*2*nn*2);
-    auto ba = [&](int ns) { BA b; b.ns = ns; b.p = w.take((long long)nEl*ns*nn); return b; };
-    S.B = ba(nk); S.Binv = ba(nk); S.Ainv = ba(nm); S.T = ba(nm); S.Rr = ba(nm); S.X = ba(nm);
-    S.Npi = ba(nk); S.Nrho = ba(nk); S.M1 = ba(nm); S.G = ba(nk); S.AB0 = ba(nm); S.AB1 = ba(nm);
-    S.R2.ns = 2*nk; S.R2.p = w.take((long long)nEl*2*nk*nn);   // RHODPI stored [k][2]
-    S.C2.ns = 2*nk; S.C2.p = w.take((long long)nEl*2*nk*nn);   // CONLIN_W stored [k][2]
+    if ((rc = plan_col(c, S))) return rc;
+    double *cq = S.cq, *tmpM = S.tmpM;
     BA R2 = S.R2, C2 = S.C2;
-    S.DIVl = ba(nk); S.DIVu = ba(nk); S.Gl = ba(nm); S.Gu = ba(nm);
-    S.L.ns = 3*nk; S.L.p = w.take((long long)nEl*3*nk*nn);
-    S.gpi = w.take((long long)nEl*nm*n2); S.geta = w.take((long long)nEl*nm*n2);
-    S.rlump = w.take((long long)nEl*nm*n2); S.tA = w.take((long long)nEl*nk*n2); S.tB = w.take((long long)nEl*nk*n2);
-    S.tC = w.take((long long)nEl*nk*n2);
-    if (w.used > w.cap) return MIMSEM_ERR_STATE;
 
     // fused assembly of the level / interface factors: default = the row-per-lane kernels where their blocks fit the register
     // file without spilling (2x2, 3x3 faces); "0" = the pipeline of wide kernels, "wave" = the earlier one-wave-per-task kernels
@@ -2416,8 +2407,8 @@ int schur_assemble(mimsem_ctx* c, double dt, const double* theta, const double* 
         fa.Ainv = S.Ainv.p; fa.X = S.X.p; fa.Gl = S.Gl.p; fa.Gu = S.Gu.p; fa.gpi = S.gpi; fa.geta = S.geta;
         if (S.F_u && strcmp(fmode, "wave") != 0) { fa.F_eta = S.F_eta; fa.F_rho = S.F_rho; fa.tE = S.tA; fa.tR = S.tC; }
         const bool rows = strcmp(fmode, "wave") != 0;
-        if (rows) rc = (n2 == 4 ? launch_schur_fused_rows<2>(c, fa) : (n2 == 9 ? launch_schur_fused_rows<3>(c, fa) : launch_schur_fused_rows<4>(c, fa)));
-        else rc = (n2 == 4 ? launch_schur_fused<4>(c, fa) : (n2 == 9 ? launch_schur_fused<9>(c, fa) : launch_schur_fused<16>(c, fa)));
+        if (rows) rc = for_order<2, 3, 4>(c->es.n, [&](auto N) { return launch_schur_fused_rows<N()>(c, fa); });
+        else rc = for_order<4, 9, 16>(n2, [&](auto N) { return launch_schur_fused<N()>(c, fa); });
         if (rc) return rc;
         if ((rc = colop_blocks_into(c, MIMSEM_V_CONLIN_RHODPI, 0, theta, S.gpi, R2.p, cq, tmpM))) return rc;       // :701
         if ((rc = colop_blocks_into(c, MIMSEM_V_CONLIN_W, 0, S.geta, nullptr, C2.p, cq, tmpM))) return rc;         // :730
@@ -2478,12 +2469,11 @@ int mimsem_column_diag_theta(mimsem_ctx* c, int which, const double* rho, const 
     if (diag_theta_fused_supported(c) && !exp_env("MIMSEM_DIAG_THETA_WIDE"))      // orders 1..3: one launch on the DPP row algebra (column_newton.inc)
         return which == 0 ? mimsem_column_diag_theta_blend(c, rho, rt, nullptr, nullptr, theta, nullptr, 1.0, 0.0)
                           : mimsem_column_diag_theta_blend(c, rho, rt, theta, nullptr, nullptr, nullptr, 1.0, 0.0);
-    const int nk = c->nk, n2 = c->es.n2e, nn = n2*n2, nEl = c->nEl;
-    int rc = c->ensure_col(colop_ws_doubles(c) + (long long)nEl*(nk + 1)*(3LL*nn + 2LL*n2));
+    const int nk = c->nk, n2 = c->es.n2e, nEl = c->nEl;
+    mimsem::ColopWS w;
+    int rc = plan_col(c, w, true);
     if (rc) return rc;
-    const long long nbmax = (long long)nEl*(nk + 1)*2;
-    double* cq = c->d_col; double* tmpM = cq + nbmax*c->es.mp12; double* M = tmpM + 2*nbmax*nn;
-    double* frt = M + (long long)nEl*(nk + 1)*2*nn;
+    double *cq = w.cq, *tmpM = w.tmpM, *M = w.M, *frt = w.frt;
     if (which == 0) {   // diagTheta_L2: VB(rho) theta = VB rt, block diagonal => exact block solves (VertSolve.cpp:339-349)
         if ((rc = colop_blocks_into(c, MIMSEM_V_CONST, 0, nullptr, nullptr, M, cq, tmpM))) return rc;
         if ((rc = stored_apply(c, MIMSEM_V_CONST, 0, M, rt, frt))) return rc;
@@ -2511,10 +2501,10 @@ int schur_operator(mimsem_ctx* c, double dt, const double* theta, const double* 
         // row-per-lane path: the lumped inverse straight from R2, VB^-1 and CONLIN_W (M1 never stored), then DIV + Helmholtz rows
         LumpArgs la{make_cg(c), hdt, R2.p, S.Binv.p, C2.p, S.rlump};
         if (S.F_u) { la.F_u = S.F_u; la.tE = S.tA; }
-        if ((rc = (n2 == 4 ? launch_schur_lump<2>(c, la) : (n2 == 9 ? launch_schur_lump<3>(c, la) : launch_schur_lump<4>(c, la))))) return rc;
+        if ((rc = for_order<2, 3, 4>(c->es.n, [&](auto N) { return launch_schur_lump<N()>(c, la); }))) return rc;
         RowsArgs ra{nEl, nk, hdt, gam, S.Nrho.p, S.Npi.p, S.X.p, C2.p, S.rlump, S.Gl.p, S.Gu.p, S.DIVl.p, S.DIVu.p, S.L.p};
         if (S.F_u) { ra.F_pi = S.F_pi; ra.F_u = S.F_u; ra.tR = S.tC; ra.F_eta = S.F_eta; S.rhs_done = true; }
-        return n2 == 4 ? launch_schur_rows<2>(c, ra) : (n2 == 9 ? launch_schur_rows<3>(c, ra) : launch_schur_rows<4>(c, ra));
+        return for_order<2, 3, 4>(c->es.n, [&](auto N) { return launch_schur_rows<N()>(c, ra); });
     }
     // M1_i = 0.5dt (R^t_i Binv_i + R^b_{i+1} Binv_{i+1})   = rows of G_rt VB_inv   (:702-703, :742)
     //   R^t_i = R2[2i+1], R^b_{i+1} = R2[2(i+1)+0]; handled by an explicit kernel (strided slots)
@@ -2722,7 +2712,7 @@ int mimsem_column_solve_schur_eta(mimsem_ctx* c, double dt,
     BA R2 = S.R2, C2 = S.C2;
     // F_u -= (G_rt VB_inv) F_eta                                                         (:772-773)
     if (!S.rhs_done) {
-        const double *R = R2.p, *Bi = S.Binv.p; double* tA = S.tA;
+        const double* R = R2.p; double* tA = S.tA;
         if ((rc = bmv(c, nk, tA, nk, S.Binv, 0, F_eta, nk, 0, 1.0, 0))) return rc;        // tA_k = Binv_k F_eta_k
         if ((rc = each(c, (long long)nEl*nm*n2, [=] __device__(long long x) {
             const int a = (int)(x%n2); long long t = x/n2; const int i = (int)(t%nm), e = (int)(t/nm);
@@ -2732,7 +2722,6 @@ int mimsem_column_solve_schur_eta(mimsem_ctx* c, double dt,
             for (int k = 0; k < n2; k++) s += Rt[a*n2 + k]*v0[k] + Rb[a*n2 + k]*v1[k];
             F_u[x] += -1.0*(hdt*s);
         }))) return rc;
-        (void)Bi;
     }
     // F_pi = -F_pi + gam DIV F_u - gam CM F_rho - gam F_eta                               (:775-780)
     if (!S.rhs_done) {
@@ -2756,7 +2745,7 @@ int mimsem_column_solve_schur_eta(mimsem_ctx* c, double dt,
         }))) return rc;
     }
     // Helmholtz solve                                                                     (:783-789)
-    if ((rc = block_thomas_refined(c, S.L.p, F_pi, d_pi, S.G.p, S.tB, S.tA, S.tC, S.Npi.p))) return rc;     // tA, Npi: free scratch by now
+    if ((rc = block_thomas_refined(c, S.L.p, F_pi, d_pi, S.Gws, S.th_y, S.th_r, S.th_dd, S.Dinv))) return rc;
     // back substitution                                                                   (:792-815)
     {
         const double *Gl = S.Gl.p, *Gu = S.Gu.p, *rl = S.rlump;
@@ -2774,7 +2763,7 @@ int mimsem_column_solve_schur_eta(mimsem_ctx* c, double dt,
     }
     if (S.rows) {
         BackArgs ba{nEl, nk, hdt, C2.p, S.X.p, S.B.p, S.Binv.p, d_u, F_eta, F_rho, d_eta, d_rho};
-        return n2 == 4 ? launch_schur_backsub<2>(c, ba) : (n2 == 9 ? launch_schur_backsub<3>(c, ba) : launch_schur_backsub<4>(c, ba));
+        return for_order<2, 3, 4>(c->es.n, [&](auto N) { return launch_schur_backsub<N()>(c, ba); });
     }
     {
         const double *Cw = C2.p, *X = S.X.p; double* tA = S.tA;

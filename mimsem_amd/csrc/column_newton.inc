@@ -412,23 +412,17 @@ __global__ __launch_bounds__(64) void k_diag_theta(DiagThetaArgs a) {
     }
 }
 
-template <template <int> class K> struct NewtonLaunch;
-#define MIMSEM_NEWTON_LAUNCH(KERNEL, ARGS, TASKS) \
-    { const unsigned grid = (unsigned)(((TASKS) + 3)/4); \
-      switch (c->es.n) { \
-      case 1: hipLaunchKernelGGL((KERNEL<1>), dim3(grid), dim3(64), 0, c->stream, ARGS); break; \
-      case 2: hipLaunchKernelGGL((KERNEL<2>), dim3(grid), dim3(64), 0, c->stream, ARGS); break; \
-      case 3: hipLaunchKernelGGL((KERNEL<3>), dim3(grid), dim3(64), 0, c->stream, ARGS); break; \
-      case 4: hipLaunchKernelGGL((KERNEL<4>), dim3(grid), dim3(64), 0, c->stream, ARGS); break; \
-      default: return MIMSEM_ERR_UNSUPPORTED; } \
-      MIMSEM_HIP_TRY(hipGetLastError()); }
+// grid of the Newton kernels: four tasks per wavefront
+unsigned newton_grid(long long tasks) { return (unsigned)((tasks + 3)/4); }
 
 int diag_theta_fused(mimsem_ctx* c, const double* rho, const double* rt, double* theta2, const double* blend2,
                      double* thetaL, const double* blendL, double wa, double wb) {
     DiagThetaArgs a{};
     fill_newton_geo(c, a.g);
     a.rho = rho; a.rt = rt; a.theta2 = theta2; a.blend2 = blend2; a.thetaL = thetaL; a.blendL = blendL; a.wa = wa; a.wb = wb;
-    MIMSEM_NEWTON_LAUNCH(k_diag_theta, a, (long long)c->nEl*(c->nk + 1))
+    const unsigned grid = newton_grid((long long)c->nEl*(c->nk + 1));
+    if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_diag_theta<N()>), dim3(grid), dim3(64), 0, c->stream, a); })) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
 
@@ -485,22 +479,24 @@ int mimsem_column_newton_residual(mimsem_ctx* c, double dt, double rayleigh,
         !F_w || !F_rho || !F_eta || !F_exner || !th_w3 || !eta || !k2i) return MIMSEM_ERR_ARG;
     if (c->nk < 2) return MIMSEM_ERR_ARG;
     if (!sweep_supported(c)) return MIMSEM_ERR_UNSUPPORTED;
-    const long long nEl = c->nEl, nk = c->nk, n2 = c->es.n2e, per = nEl*nk*n2;
-    int rc = c->ensure_col(std::max(sweep_ws_doubles(c), 5*per));
+    const long long nEl = c->nEl, nk = c->nk;
+    mimsem::NewtonWS w;
+    int rc = plan_col(c, w, true);
     if (rc) return rc;
-    double* ws = c->d_col;
     NewtonIfcArgs ia{};
     fill_newton_geo(c, ia.g);
     ia.dt = dt; ia.rayleigh = rayleigh; ia.theta = theta; ia.Pi = Pi; ia.velz1 = velz_i; ia.velz2 = velz_j; ia.rho1 = rho_i; ia.rho2 = rho_j;
     ia.add_w = add_w;
-    ia.F = ws; ia.G = ws + per; ia.u = ws + 2*per; ia.wF = ws + 3*per; ia.fwA = ws + 4*per; ia.k2 = k2i;
-    MIMSEM_NEWTON_LAUNCH(k_newton_ifc, ia, nEl*(nk - 1))
+    ia.F = w.F; ia.G = w.G; ia.u = w.u; ia.wF = w.wF; ia.fwA = w.fwA; ia.k2 = k2i;
+    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton_ifc<N()>), dim3(newton_grid(nEl*(nk - 1))), dim3(64), 0, c->stream, ia); }))) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
     NewtonLevArgs la{};
     la.g = ia.g; la.dt = dt; la.theta = theta; la.zv = zv; la.rho_i = rho_i; la.rho_j = rho_j; la.rt_i = rt_i; la.rt_j = rt_j;
     la.rho_h = rho_h; la.rt_h = rt_h; la.exner_j = exner_j; la.add_rho = add_rho; la.add_rt = add_rt;
     la.F = ia.F; la.G = ia.G; la.u = ia.u; la.wF = ia.wF; la.fwA = ia.fwA;
     la.F_w = F_w; la.F_rho = F_rho; la.F_eta = F_eta; la.F_exner = F_exner; la.th_w3 = th_w3; la.eta = eta;
-    MIMSEM_NEWTON_LAUNCH(k_newton_lev, la, nEl*nk)
+    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton_lev<N()>), dim3(newton_grid(nEl*nk)), dim3(64), 0, c->stream, la); }))) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
 
@@ -518,7 +514,9 @@ int mimsem_column_newton_update(mimsem_ctx* c, const double* d_w, const double* 
     a.velz_i = velz_i; a.rho_i = rho_i; a.rt_i = rt_i; a.exner_i = exner_i;
     a.velz_j = velz_j; a.rho_j = rho_j; a.rt_j = rt_j; a.exner_j = exner_j;
     a.velz_h = velz_h; a.rho_h = rho_h; a.rt_h = rt_h; a.exner_h = exner_h; a.nrm = norm_squares;
-    MIMSEM_NEWTON_LAUNCH(k_newton_upd, a, (long long)c->nEl*c->nk)
+    const unsigned grid = newton_grid((long long)c->nEl*c->nk);
+    if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton_upd<N()>), dim3(grid), dim3(64), 0, c->stream, a); })) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
 

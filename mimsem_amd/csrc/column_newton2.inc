@@ -1,4 +1,4 @@
-// column_newton2.inc -- included by column_kernels.hip after column_newton.inc (same translation unit: ColTask, NewtonGeo, MIMSEM_NEWTON_LAUNCH).
+// column_newton2.inc -- included by column_kernels.hip after column_newton.inc (same translation unit: ColTask, NewtonGeo, newton_grid).
 //
 // The residual assembly and the update of the OTHER vertical Newton loop, VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246), the
 // caller of solve_schur_column_3: assemble_residual (:386-430) with diagnose_F_z / diagnose_Phi_z (:237-286), the right-hand sides of
@@ -217,22 +217,24 @@ int mimsem_column_newton2_residual(mimsem_ctx* c, double dt, double rayleigh,
         !F_w || !F_rho || !F_rt || !F_exner || !k2i) return MIMSEM_ERR_ARG;
     int rc = newton2_check(c);
     if (rc) return rc;
-    const long long nEl = c->nEl, nk = c->nk, n2 = c->es.n2e, per = nEl*nk*n2;
+    const long long nEl = c->nEl, nk = c->nk;
     if (nEl == 0) return MIMSEM_OK;
-    if ((rc = c->ensure_col(std::max(sweep_ws_doubles(c), 4*per)))) return rc;
-    double* ws = c->d_col;
+    mimsem::NewtonWS w;
+    if ((rc = plan_col(c, w, false))) return rc;
     Newton2IfcArgs ia{};
     fill_newton_geo(c, ia.g);
     ia.dt = dt; ia.rayleigh = rayleigh; ia.theta = theta_h; ia.Pi = Pi; ia.velz1 = velz_i; ia.velz2 = velz_j; ia.rho1 = rho_i; ia.rho2 = rho_j;
     ia.add_w = add_w;
-    ia.F = ws; ia.G = ws + per; ia.u = ws + 2*per; ia.fwA = ws + 3*per; ia.k2 = k2i;
-    MIMSEM_NEWTON_LAUNCH(k_newton2_ifc, ia, nEl*(nk - 1))
+    ia.F = w.F; ia.G = w.G; ia.u = w.u; ia.fwA = w.fwA; ia.k2 = k2i;
+    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton2_ifc<N()>), dim3(newton_grid(nEl*(nk - 1))), dim3(64), 0, c->stream, ia); }))) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
     Newton2LevArgs la{};
     la.g = ia.g; la.dt = dt; la.zv = zv; la.rho_i = rho_i; la.rho_j = rho_j; la.rt_i = rt_i; la.rt_j = rt_j; la.exner_j = exner_j;
     la.add_rho_pre = add_rho_pre; la.add_rt_pre = add_rt_pre; la.add_rt_post = add_rt_post;
     la.F = ia.F; la.G = ia.G; la.u = ia.u; la.fwA = ia.fwA;
     la.F_w = F_w; la.F_rho = F_rho; la.F_rt = F_rt; la.F_exner = F_exner;
-    MIMSEM_NEWTON_LAUNCH(k_newton2_lev, la, nEl*nk)
+    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton2_lev<N()>), dim3(newton_grid(nEl*nk)), dim3(64), 0, c->stream, la); }))) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
 

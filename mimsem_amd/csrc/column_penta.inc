@@ -283,16 +283,11 @@ int launch_penta_dpp(mimsem_ctx* c, int refine, const double* L, bool rowmajor, 
     const bool two = nk >= 4 && nk%2 == 0 && !(exp_env("MIMSEM_PENTA2") && atoi(exp_env("MIMSEM_PENTA2")) == 0);
     if (refine > 0xff) refine = 0xff;
     if (c->pivot_fallback == 1 && !(exp_env("MIMSEM_THOMAS_TRIAGE") && atoi(exp_env("MIMSEM_THOMAS_TRIAGE")) == 0)) refine |= 0x100;      // (as launch_thomas_dpp)
-#define MIMSEM_PD(N) case N: \
-        if (two && !rowmajor) hipLaunchKernelGGL((k_penta_dpp<N, true, true>), dim3((unsigned)((c->nEl + 1)/2)), dim3(64), 0, c->stream, c->nEl, nk, refine, L, rs, js, f, d, Fac, yws, c->d_colstat, c->d_colratio); \
-        else if (two) hipLaunchKernelGGL((k_penta_dpp<N, true, false>), dim3((unsigned)((c->nEl + 1)/2)), dim3(64), 0, c->stream, c->nEl, nk, refine, L, rs, js, f, d, Fac, yws, c->d_colstat, c->d_colratio); \
-        else hipLaunchKernelGGL((k_penta_dpp<N, false, false>), dim3((unsigned)((c->nEl + 3)/4)), dim3(64), 0, c->stream, c->nEl, nk, refine, L, rs, js, f, d, Fac, yws, c->d_colstat, c->d_colratio); \
-        break;
-    switch (n2) {
-    MIMSEM_PD(1) MIMSEM_PD(4) MIMSEM_PD(9) MIMSEM_PD(16)
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
-#undef MIMSEM_PD
+    if (int rc = for_order<1, 4, 9, 16>(n2, [&](auto N) {
+        if (two && !rowmajor) hipLaunchKernelGGL((k_penta_dpp<N(), true, true>), dim3((unsigned)((c->nEl + 1)/2)), dim3(64), 0, c->stream, c->nEl, nk, refine, L, rs, js, f, d, Fac, yws, c->d_colstat, c->d_colratio);
+        else if (two) hipLaunchKernelGGL((k_penta_dpp<N(), true, false>), dim3((unsigned)((c->nEl + 1)/2)), dim3(64), 0, c->stream, c->nEl, nk, refine, L, rs, js, f, d, Fac, yws, c->d_colstat, c->d_colratio);
+        else hipLaunchKernelGGL((k_penta_dpp<N(), false, false>), dim3((unsigned)((c->nEl + 3)/4)), dim3(64), 0, c->stream, c->nEl, nk, refine, L, rs, js, f, d, Fac, yws, c->d_colstat, c->d_colratio);
+    })) return rc;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }

@@ -390,15 +390,8 @@ int launch_band_lu_flagged(mimsem_ctx* c, int nb, const double* L, bool rowmajor
     a.L = L; a.f = f; a.d = d; a.stat = c->d_colstat; a.ratio = c->d_colratio;
     a.W = c->d_lu; a.per = per;
     a.stop = c->blu_stop;
-#define MIMSEM_BLU(N2_, NB_) hipLaunchKernelGGL((k_band_lu_wave<N2_, NB_>), dim3((unsigned)grid), dim3(64), 0, c->stream, a)
-    switch (n2*10 + nb) {
-    case 11: MIMSEM_BLU(1, 1); break;   case 12: MIMSEM_BLU(1, 2); break;
-    case 41: MIMSEM_BLU(4, 1); break;   case 42: MIMSEM_BLU(4, 2); break;
-    case 91: MIMSEM_BLU(9, 1); break;   case 92: MIMSEM_BLU(9, 2); break;
-    case 161: MIMSEM_BLU(16, 1); break; case 162: MIMSEM_BLU(16, 2); break;
-    default: return MIMSEM_OK;
-    }
-#undef MIMSEM_BLU
+    if (for_order<1, 4, 9, 16>(n2, [&](auto N2) { return for_order<1, 2>(nb, [&](auto NB) {      // block size x half bandwidth in blocks
+            hipLaunchKernelGGL((k_band_lu_wave<N2(), NB()>), dim3((unsigned)grid), dim3(64), 0, c->stream, a); }); })) return MIMSEM_OK;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }

@@ -405,13 +405,9 @@ __global__ __launch_bounds__(64) void k_s3_factors_ifc(S3FactorArgs a) {
 
 int launch_s3_factors(mimsem_ctx* c, const S3FactorArgs& a) {
     const long long tl = (long long)a.g.nEl*a.g.nk, ti = (long long)a.g.nEl*(a.g.nk - 1);
-    switch (c->es.n) {
-#define MIMSEM_S3F(N) case N: hipLaunchKernelGGL((k_s3_factors_lev<N>), dim3((unsigned)((tl + 3)/4)), dim3(64), 0, c->stream, a); \
-                              hipLaunchKernelGGL((k_s3_factors_ifc<N>), dim3((unsigned)((ti + 3)/4)), dim3(64), 0, c->stream, a); break;
-    MIMSEM_S3F(1) MIMSEM_S3F(2) MIMSEM_S3F(3) MIMSEM_S3F(4)
-#undef MIMSEM_S3F
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) {
+            hipLaunchKernelGGL((k_s3_factors_lev<N()>), dim3((unsigned)((tl + 3)/4)), dim3(64), 0, c->stream, a);
+            hipLaunchKernelGGL((k_s3_factors_ifc<N()>), dim3((unsigned)((ti + 3)/4)), dim3(64), 0, c->stream, a); })) return rc;
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }

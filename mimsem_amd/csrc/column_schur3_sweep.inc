@@ -463,10 +463,6 @@ __global__ __launch_bounds__(64) void k_s3_backsub(S3BackArgs a) {
     }
 }
 
-long long s3_fused_ws_doubles(const mimsem_ctx* c) {
-    const long long nEl = c->nEl, nk = c->nk, n2 = c->es.n2e, nn = n2*n2;
-    return nEl*nk*((5 + 4 + 6)*nn + 2*n2) + ((nEl + 3)*(nk/2 + 1) + 8)*nn;      // + the dump blocks of the sweep (one per task, <= nk/2 + 1 tasks per column, columns rounded up to 4)
-}
 // orders 1..4.  At order 4 a block is 32 VGPRs per lane and the walk's ~20 live blocks do not fit 512 registers: k_s3_sweep<4> compiles
 // with ~390 spilled dwords per lane -- correct only while no spill lands in a divergent region (see the note on the task mapping in the
 // kernel; scripts/check_spill_slots.py checks the ISA for it, tests/test_dpp_hazards.py runs it).  MIMSEM_SCHUR3_FUSED4=0 sends order 4
@@ -481,17 +477,11 @@ bool s3_fused_supported(const mimsem_ctx* c) {
 int s3_fused_solve(mimsem_ctx* c, double dt, unsigned flags, const double* theta, const double* velz, const double* rho, const double* rt,
                    const double* pi, double* F_u, double* F_rho, double* F_rt, double* F_pi, double* d_u, double* d_rho, double* d_rt,
                    double* d_pi, double* L_out) {
-    const long long nEl = c->nEl, nk = c->nk, n2 = c->es.n2e, nn = n2*n2;
-    int rc = c->ensure_col(s3_fused_ws_doubles(c));
+    mimsem::S3FusedWS w;
+    int rc = plan_col(c, w);
     if (rc) return rc;
-    double* p = c->d_col;
-    double* L = p; p += nEl*nk*5*nn;
-    double* Fac = p; p += nEl*nk*4*nn;
-    double *GGl = p, *GGu = p + nEl*nk*nn, *Mui = p + 2*nEl*nk*nn, *X = p + 3*nEl*nk*nn, *Binv = p + 4*nEl*nk*nn, *Brti = p + 5*nEl*nk*nn; p += 6*nEl*nk*nn;
-    double* yws = p; p += nEl*nk*n2;
-    double* fu2 = p; p += nEl*nk*n2;
     S3SweepArgs a{};
-    a.dump = p;
+    a.dump = w.dump;
     // order 4: the half-row block layout (two tasks per wavefront, no spill); MIMSEM_S3_HALF=0 keeps the 16-lane layout for A/B runs
     const bool half = c->es.n == 4 && !(exp_env("MIMSEM_S3_HALF") && atoi(exp_env("MIMSEM_S3_HALF")) == 0);
     fill_geo(c, a, 1, 1024, half ? 2 : 4);
@@ -501,47 +491,37 @@ int s3_fused_solve(mimsem_ctx* c, double dt, unsigned flags, const double* theta
     a.rayleigh = (flags & MIMSEM_SCHUR3_NO_RAYLEIGH) ? 0 : 1; a.ray_param = 0.5*dt*(4.0/120.0);     // RAYLEIGH, eul/VertSolve.cpp:32, :520
     a.cv_from_velz = (flags & MIMSEM_SCHUR3_BOX_Q) ? 0 : 1;
     a.theta = theta; a.velz = a.cv_from_velz ? velz : nullptr; a.rho = rho; a.rt = rt; a.pi = pi;
-    a.F_u = F_u; a.F_rho = F_rho; a.F_pi = F_pi; a.F_rt = F_rt; a.fu2 = fu2;
-    a.L = L_out ? L_out : L; a.rowmajor = L_out ? 1 : 0;
-    a.GGl = GGl; a.GGu = GGu; a.Mui = Mui; a.X = X; a.Binv = Binv; a.Brti = Brti;
+    a.F_u = F_u; a.F_rho = F_rho; a.F_pi = F_pi; a.F_rt = F_rt; a.fu2 = w.fu2;
+    a.L = L_out ? L_out : w.L; a.rowmajor = L_out ? 1 : 0;
+    a.GGl = w.GGl; a.GGu = w.GGu; a.Mui = w.Mui; a.X = w.X; a.Binv = w.Binv; a.Brti = w.Brti;
     {
         const unsigned grid = walk_task_grid(a.nEl, a.nchunk, false, half ? 2 : 4);          // (four -- half-row layout: two -- columns of one chunk per wavefront)
-#define MIMSEM_S3S(N) case N: if (a.cv_from_velz) hipLaunchKernelGGL((k_s3_sweep<N, false>), dim3(grid), dim3(64), 0, c->stream, a); \
-                              else hipLaunchKernelGGL((k_s3_sweep<N, true>), dim3(grid), dim3(64), 0, c->stream, a); break;
+        const auto sweep = [&](auto N) {
+            if (a.cv_from_velz) hipLaunchKernelGGL((k_s3_sweep<N(), false>), dim3(grid), dim3(64), 0, c->stream, a);
+            else hipLaunchKernelGGL((k_s3_sweep<N(), true>), dim3(grid), dim3(64), 0, c->stream, a);
+        };
         if (half) {
             if (a.cv_from_velz) hipLaunchKernelGGL((k_s3_sweep<4, false, true>), dim3(grid), dim3(64), 0, c->stream, a);
             else hipLaunchKernelGGL((k_s3_sweep<4, true, true>), dim3(grid), dim3(64), 0, c->stream, a);
         } else
-        switch (c->es.n) {
-        MIMSEM_S3S(1) MIMSEM_S3S(2) MIMSEM_S3S(3)
 #ifdef MIMSEM_WITH_EXPERIMENTS
-        MIMSEM_S3S(4)                        // (order 4 on the 16-lane layout, ~700 spilled dwords per lane: MIMSEM_S3_HALF=0, DESIGN 6.5; the default is the half-row walk above)
+        if ((rc = for_order<1, 2, 3, 4>(c->es.n, sweep))) return rc;      // (order 4 on the 16-lane layout, ~700 spilled dwords per lane: MIMSEM_S3_HALF=0, DESIGN 6.5; the default is the half-row walk above)
+#else
+        if ((rc = for_order<1, 2, 3>(c->es.n, sweep))) return rc;
 #endif
-        default: return MIMSEM_ERR_UNSUPPORTED;
-        }
-#undef MIMSEM_S3S
         MIMSEM_HIP_TRY(hipGetLastError());
     }
-    int nref = 4;
-    if (const char* ev = getenv("MIMSEM_REFINE")) nref = std::max(0, atoi(ev));
-    if (getenv("MIMSEM_NO_REFINE")) nref = 0;
-    if ((rc = launch_penta_dpp(c, nref, a.L, a.rowmajor != 0, F_rt, d_rt, Fac, yws, true))) return rc;
+    if ((rc = launch_penta_dpp(c, refine_steps(), a.L, a.rowmajor != 0, F_rt, d_rt, w.Fac, w.yws, true))) return rc;
     if ((rc = launch_band_lu_flagged(c, 2, a.L, a.rowmajor != 0, F_rt, d_rt))) return rc;       // (opt-in: flagged columns by a pivoted band LU)
     c->colstat_valid = true;
     S3BackArgs b{};
     fill_geo(c, b, exp_env("MIMSEM_S3B_WPS") ? atoi(exp_env("MIMSEM_S3B_WPS")) : 2);      // wavefronts per SIMD the level chunking aims at (A/B knob)
-    b.hdt = a.hdt; b.gam = a.gam; b.pi = pi; b.d_rt = d_rt; b.fu2 = fu2;
-    b.GGl = GGl; b.GGu = GGu; b.Mui = Mui; b.X = X; b.Binv = Binv; b.Brti = Brti;
+    b.hdt = a.hdt; b.gam = a.gam; b.pi = pi; b.d_rt = d_rt; b.fu2 = w.fu2;
+    b.GGl = w.GGl; b.GGu = w.GGu; b.Mui = w.Mui; b.X = w.X; b.Binv = w.Binv; b.Brti = w.Brti;
     b.F_u = F_u; b.F_pi = F_pi; b.F_rho = F_rho; b.d_u = d_u; b.d_pi = d_pi; b.d_rho = d_rho;
     {
         const unsigned grid = walk_task_grid(b.nEl, b.nchunk, c->es.n == 4);
-        switch (c->es.n) {
-        case 1: hipLaunchKernelGGL((k_s3_backsub<1>), dim3(grid), dim3(64), 0, c->stream, b); break;
-        case 2: hipLaunchKernelGGL((k_s3_backsub<2>), dim3(grid), dim3(64), 0, c->stream, b); break;
-        case 3: hipLaunchKernelGGL((k_s3_backsub<3>), dim3(grid), dim3(64), 0, c->stream, b); break;
-        case 4: hipLaunchKernelGGL((k_s3_backsub<4>), dim3(grid), dim3(64), 0, c->stream, b); break;
-        default: return MIMSEM_ERR_UNSUPPORTED;
-        }
+        if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_s3_backsub<N()>), dim3(grid), dim3(64), 0, c->stream, b); }))) return rc;
         MIMSEM_HIP_TRY(hipGetLastError());
     }
     return MIMSEM_OK;
