@@ -158,6 +158,17 @@ int  mimsem_op_wave_stats(const mimsem_ctx* ctx, int nlev, int out[5]);
  * requested parts for that form while the two-launch form of the same context (MIMSEM_WAVE_OWN=0, split applies) keeps its chunks, so the
  * two can report different numbers until part_levels is set back to 0.  Applies to the launches that follow; not inside a stream capture. */
 int  mimsem_ctx_set_wave_split(mimsem_ctx* ctx, int part_levels, int order);
+/* Levels per work item of the passes that cut a call into (element, chunk of consecutive levels): lch = 1 .. 8 is a request that replaces
+ * their "six workgroups per CU" rule, lch = 0 (a new context's state) gives the library's own rules back; anything else is MIMSEM_ERR_ARG
+ * and changes nothing.  The request moves four passes: the element kernel of mimsem_op_apply and everything built on it (min(lch, nlev),
+ * which mimsem_op_level_chunk then reports), the register-resident and the LDS-resident shared-block applies of mimsem_elem_blocks_apply
+ * (min(lch, nlev) levels per item), and the owned-block pass with shared blocks (the request rounded DOWN to 1, 2, 4 or 8, at most
+ * min(nlev, 8); per-level blocks stay at one level per item).  NOT moved: the wave-level forms (mimsem_ctx_set_wave_split), the block
+ * residual, which runs min(nlev, 8) levels per item on any mesh, and the column kernels.  Results do not depend on it: the element kernel and
+ * the shared-block applies give the same bits at every chunk size, the owned-block pass agrees to rounding (its level count is a compile-time
+ * parameter) -- tests/test_gpu_level_chunks.py.  TUNING AND TESTS ONLY, not part of the stable surface: it is context state, not per-launch
+ * state.  Applies to the launches that follow; not inside a stream capture (MIMSEM_ERR_STATE). */
+int  mimsem_ctx_set_level_chunk(mimsem_ctx* ctx, int lch);
 /* Balanced level ranges of the one-launch Umat form (p = 3, calls of >= 2 levels, no requested split): where the default rule's workgroups
  * would all be resident at once (at most 3 per CU) without being a multiple of the CU count, a host planner deals wgs_per_cu x ncu
  * workgroups whose level-pair totals differ by at most 2 pairs instead, so that every CU carries the same work.  OPT-IN: a context starts with the

@@ -40,6 +40,7 @@ _SIGS = {
     "mimsem_op_level_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mimsem_op_wave_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "mimsem_ctx_set_wave_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "mimsem_ctx_set_level_chunk": (C.c_int, [C.c_void_p, C.c_int]),
     "mimsem_ctx_set_wave_balance": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "mimsem_ctx_wave_balance_launches": (c_ll, [C.c_void_p]),
     "mimsem_ctx_set_halo_slots": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),

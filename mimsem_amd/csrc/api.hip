@@ -1209,6 +1209,13 @@ int mimsem_ctx_set_wave_split(mimsem_ctx* c, int part_levels, int order) {
     return MIMSEM_OK;
 }
 
+int mimsem_ctx_set_level_chunk(mimsem_ctx* c, int lch) {
+    if (!c || lch < 0 || lch > 8) return MIMSEM_ERR_ARG;
+    if (c->is_capturing()) return MIMSEM_ERR_STATE;
+    c->lch_override = lch;                                // (level_chunk, launch_blocks_apply, launch_owned_nd read it at every launch)
+    return MIMSEM_OK;
+}
+
 int mimsem_ctx_set_wave_balance(mimsem_ctx* c, int ncu, int wgs_per_cu) {
     if (!c || ncu > (1 << 20) || (ncu >= 0 && (wgs_per_cu < 1 || wgs_per_cu > 3))) return MIMSEM_ERR_ARG;
     if (c->is_capturing()) return MIMSEM_ERR_STATE;

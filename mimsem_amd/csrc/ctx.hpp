@@ -183,7 +183,7 @@ struct mimsem_ctx {
     const double* col_uh = nullptr;     // horizontal velocity [nk][n1] of the *_up column operators
     long long col_uhs = 0;
     int swz = 1;                   // MIMSEM_NOSWZ=1 disables the XCD-aware block order (tuning)
-    int lch_override = 0;          // MIMSEM_LCH environment override (tuning)
+    int lch_override = 0;          // mimsem_ctx_set_level_chunk; MIMSEM_LCH in the experiments build (tuning and tests): 0 = the library's rules
     // measurement hook: event triples (start, mid, end) around pass 1 / pass 2 of mimsem_op_apply
     bool profiling = false;
     int prof_every = 1; long long prof_count = 0;

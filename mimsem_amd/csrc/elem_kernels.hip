@@ -1593,7 +1593,9 @@ int launch_blocks_apply(mimsem_ctx* c, int form, int nlev, int transposed, const
         }
         const int lpe = nd <= 16 ? 16 : (nd <= 32 ? 32 : 64), epb = 256/lpe;
         int lch = (int)(((long long)((c->nEl + epb - 1)/epb)*nlev)/(256*6));         // ~6 workgroups per CU, as k_elem_apply
-        lch = std::max(1, std::min(lch, 8)); lch = std::min(lch, std::max(nlev, 1));
+        lch = std::max(1, std::min(lch, 8));
+        if (c->lch_override > 0) lch = c->lch_override;                               // mimsem_ctx_set_level_chunk: a request replaces the rule
+        lch = std::min(lch, std::max(nlev, 1));
         const long long items = (long long)c->nEl*((nlev + lch - 1)/lch);
         const unsigned grid = (unsigned)((items + epb - 1)/epb);
 #define MIMSEM_BR(ND) case ND: hipLaunchKernelGGL((k_blocks_apply_reg<ND>), dim3(grid), dim3(256), 0, c->stream, c->nEl, nlev, lch, transposed, \
@@ -1618,7 +1620,8 @@ int launch_blocks_apply(mimsem_ctx* c, int form, int nlev, int transposed, const
         const unsigned gx = (unsigned)((c->nEl + epb - 1)/epb);
         // enough workgroups to fill 256 CUs several times over: split the level sweep when there are few element groups
         int nchunk = (int)std::min<long long>(nlev, std::max<long long>(1, (2048 + gx - 1)/gx));
-        const int lch = (nlev + nchunk - 1)/nchunk;
+        int lch = (nlev + nchunk - 1)/nchunk;
+        if (c->lch_override > 0) lch = std::min(c->lch_override, nlev);               // mimsem_ctx_set_level_chunk: a request replaces the rule
         nchunk = (nlev + lch - 1)/lch;
         const dim3 grid(gx, (unsigned)nchunk);
         const size_t lds = (size_t)epb*nd*(nd + 2)*sizeof(double);

@@ -158,7 +158,8 @@ int launch_owned_nd(mimsem_ctx* c, int kind, OwnedArgs a) {
     // chunk's, so a work item loads and multiplies no level it does not write (only the ragged last chunk of a call has fewer)
     int lch = 1;
     if (!a.bls) {
-        const long long want = std::min<long long>(std::min(a.nlev, 8), ((long long)(c->nEl + EPB - 1)/EPB)*a.nlev/(256*6));
+        long long want = std::min<long long>(std::min(a.nlev, 8), ((long long)(c->nEl + EPB - 1)/EPB)*a.nlev/(256*6));
+        if (c->lch_override > 0) want = std::min(std::min(a.nlev, 8), c->lch_override);       // mimsem_ctx_set_level_chunk: a request replaces the rule
         while (2*lch <= want) lch *= 2;
     }
     a.lch = lch;

@@ -194,6 +194,12 @@ class Engine:
         _need(int(ncu) < 0 or 1 <= int(wgs_per_cu) <= 3, "set_wave_balance: 1 .. 3 workgroups per CU")
         check(self.L.mimsem_ctx_set_wave_balance(self.ctx, int(ncu), int(wgs_per_cu)), "set_wave_balance")
 
+    def set_level_chunk(self, lch):
+        """levels per work item of the element kernel, the shared-block applies and the owned-block pass: 1 .. 8 is a request, 0 the library's
+        own rules (tuning and tests only; results do not depend on it); mimsem_ctx_set_level_chunk"""
+        _need(0 <= int(lch) <= 8, "set_level_chunk: 0 (the library's rules) or 1 .. 8 levels per work item")
+        check(self.L.mimsem_ctx_set_level_chunk(self.ctx, int(lch)), "set_level_chunk")
+
     def profile_read(self):
         """(ms in element kernels, ms in gather-sum kernels, launches) since the last read"""
         a, b, n = C.c_double(), C.c_double(), C.c_longlong()
