@@ -1437,7 +1437,7 @@ static bool fits_32bit(const mimsem_ctx* c, bool nodes) {
 static long long* g_stamps = nullptr; static size_t g_stamp_items = 0;
 static size_t stamps_begin(mimsem_ctx* c, int nlev, ElemArgs& a) {
     const size_t items = (size_t)c->wv.ngroups*std::max((nlev + a.lch - 1)/a.lch, a.wnp);     // (the kernel stamps item < wgroups x parts: never fewer slots than that)
-    if (!exp_env("MIMSEM_WAVE_STAMPS")) return items;
+    if (!std::getenv("MIMSEM_WAVE_STAMPS")) return items;      // (a diagnostic build of its own: not one of the closed experiments)
     if (items > g_stamp_items) { if (g_stamps) (void)hipFree(g_stamps); (void)hipMalloc((void**)&g_stamps, items*16*8); g_stamp_items = items; }
     (void)hipMemsetAsync(g_stamps, 0, items*16*8, c->stream);
     a.wstamps = g_stamps;

@@ -255,7 +255,8 @@ struct ElemArgs {
     const int4* wgh; const int* wgx;                     // owner-computes form: packed ghost lanes, gathered slots (build_wave_own), or null
     // level ranges (round 10, wave_level_parts): wnp > 0 -- every group is cut into wnp parts of whole level PAIRS, part k = levels
     // 2 (k wpb + min(k, wpr)) .. + 2 (wpb + (k < wpr)), clipped to nlev; a wavefront leaves at the first batch boundary at or beyond its
-    // last level.  0: the chunk arithmetic (lch, wcpp)
+    // last level.  0: the chunk arithmetic (lch, wcpp).  own4::k_apply_wave has no use for wcpp as a count: dispatch_apply_wave puts
+    // floor((2^32 - 1)/divisor) there, with which the kernel splits an item into group and part by a multiplication
     int wnp, wpb, wpr;
     int wfence;                      // finishing phase, experiment: partial sums in PLAIN memory, one agent-scope release fence per wavefront before its arrival
     double Etab[20];                 // edge-basis table E[mp1][n] by value (orders <= 4): SGPRs, no load in the kernel

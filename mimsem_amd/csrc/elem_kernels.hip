@@ -1698,9 +1698,13 @@ static int dispatch_apply_wave(mimsem_ctx* c, int op, const ElemArgs& a) {
     if (own && (N != 3 || op != MIMSEM_OP_UMAT || tile || a.wnp < 1)) return MIMSEM_ERR_STATE;
     if constexpr (N == 3 && MIMSEM_WLB == 2 && MIMSEM_WAHEAD == 2) {      // (the A/B builds of those two knobs keep the form below)
         if (own && a.wgh4 && a.lch == WLC) {             // the ghost pass per four levels (single-level calls keep the form below)
+            // the default rule splits item = group x part by a multiplication: wcpp, which this form does not use otherwise, carries
+            // floor((2^32 - 1)/divisor) -- the parts per group when the parts of a group are neighbours (swz & 2), else the groups
+            ElemArgs b = a;
+            b.wcpp = (int)(0xFFFFFFFFu/std::max((a.swz & 2) ? (unsigned)a.wnp : (unsigned)a.wgroups, 1u));
 #define MIMSEM_WL4(K, ACC) \
-            if (c->ev_k1[0]) hipExtLaunchKernelGGL((own4::K<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, a); \
-            else hipLaunchKernelGGL((own4::K<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, a)
+            if (c->ev_k1[0]) hipExtLaunchKernelGGL((own4::K<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, c->ev_k1[0], c->ev_k1[1], 0, b); \
+            else hipLaunchKernelGGL((own4::K<N, MIMSEM_OP_UMAT, WLC, ACC>), dim3(grid), dim3(64*WNW), 0, c->stream, b)
             if (listed) c->bal_launches++;
             if (listed) { if (a.accum) { MIMSEM_WL4(k_apply_wave_list, true); } else { MIMSEM_WL4(k_apply_wave_list, false); } }
             else        { if (a.accum) { MIMSEM_WL4(k_apply_wave, true); } else { MIMSEM_WL4(k_apply_wave, false); } }

@@ -626,18 +626,33 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
         cint* const it = (cint*)(unsigned long long)(wit + item);
         g = (unsigned)it[0]; lbeg = it[1]; lend_ = it[2];
     } else {
-        unsigned ch;
-        if (a.swz & 2) { g = item/nchunk; ch = item%nchunk; }
-        else           { g = item%(unsigned)a.wgroups; ch = item/(unsigned)a.wgroups; }
-        g += (unsigned)a.wg0;
+        // item = quotient*dv + rest without a division: a.wcpp carries floor((2^32 - 1)/dv) (dispatch_apply_wave), whose high product
+        // is the quotient or one less for every 32-bit item -- one wave-uniform correction makes it exact
+        const bool gmaj = (a.swz & 2) != 0;              // group-major: the parts of a group are neighbours
+        const unsigned dv = gmaj ? nchunk : (unsigned)a.wgroups;
+        unsigned qt = __umulhi(item, (unsigned)a.wcpp), rs = item - qt*dv;
+        if (rs >= dv) { qt++; rs -= dv; }
+        const unsigned ch = gmaj ? rs : qt;
+        g = (gmaj ? qt : rs) + (unsigned)a.wg0;
         lbeg = 2*((int)ch*a.wpb + min((int)ch, a.wpr));
         lend_ = min(a.nlev, lbeg + 2*(a.wpb + ((int)ch < a.wpr ? 1 : 0)));
     }
     const int lend = lend_;
+#ifdef MIMSEM_STAMPS
+    const int lbeg0 = lbeg;
+#define WSTAMP4(k) do { if constexpr (!LIST) WSTAMP(k); } while (0)      // (the stamps have a slot per item of the default rule)
+#else
+#define WSTAMP4(k) do { } while (0)
+#endif
+    WSTAMP4(0);                                          // entry: the item is known
     const int4 wl = a.wlane[(size_t)g*64 + lane];
     const int4 wp = a.wplan[(size_t)g*64 + lane];
     const int4 gh = a.wgh4[(size_t)g*64 + lane];
     const int gxs = a.wgx[(size_t)g*64 + lane];
+    // the group's tables are REQUESTED; the rows' start addresses are formed under them (from `lbeg` as it stands behind this line)
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+s"(lbeg));
+    WSTAMP4(2);                                          // tables requested
     const double2* hp = (const double2*)(a.wG + (size_t)gh.x*4);
     const double2 h01 = hp[0], h23 = hp[1];
     const bool gyn = (gh.z & 1) != 0, gsz = (gh.z & 4) != 0, gidle = (gh.z & 8) != 0;
@@ -656,27 +671,40 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
     const unsigned xo = 8u*(unsigned)wl.y;
     const unsigned to = 16u*gq;
     double2 px[LCT]; double pt0[LCT], pg[LCT], ptg[LCT/(2*LB)];
-    auto load_batch = [&](int r0, int lev0_) {
+    // The batches are requested in level order, two levels further each time, so the rows are STEPPED, not computed: wave-uniform
+    // byte pointers to the next x row and the next thickInv pair row, set here once.  A level l stands for min(l, nlev - 1) (beyond
+    // the last level: re-read it -- a valid address; nothing is stored for it): `ahead` counts the levels from the next batch's first
+    // to the call's last, an x row moves on while a level is left and stays otherwise, a pair row (whose parity the step of two
+    // keeps) moves on while two are left and otherwise becomes the last level's row -- that one may be of the other parity.
+    const auto tip_row = [&](int l) { const int L = a.lev0 + l; return (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps); };
+    const char* xrow = (const char*)(a.x + (size_t)min(lbeg, a.nlev - 1)*a.xs);
+    const char* trow = tip_row(min(lbeg, a.nlev - 1));
+    const char* const tlast = tip_row(a.nlev - 1);
+    const long long xsb = 8*a.xs, tpb = 8*a.tps;
+    int ahead = a.nlev - 1 - lbeg;
+    auto load_batch = [&](int r0) {
+        const bool two = ahead >= 2;                         // wave-uniform: the call has the level two beyond this batch's first
         {
-            const int L = a.lev0 + min(lev0_, a.nlev - 1);   // (a level beyond the range reads a valid pair; nothing is stored for it)
-            const char* row = (const char*)(a.tIp + ((size_t)(L & 1)*a.tnp + (size_t)(L >> 1))*(size_t)a.tps);
-            const double2 tp = WLOAD(double2, row + to);
+            const double2 tp = WLOAD(double2, trow + to);
             pt0[r0] = tp.x; pt0[r0 + 1] = tp.y;
             if ((r0/LB)%2 == 0) {                            // ONE load per ghost pass
-                const unsigned nx = lev0_ + 2 <= a.nlev - 1 ? 8u*(unsigned)a.tps : 0u;      // wave-uniform
-                ptg[r0/(2*LB)] = *(const double*)(row + (tgo + (ghi & nx)));
+                const unsigned nx = two ? (unsigned)tpb : 0u;
+                ptg[r0/(2*LB)] = *(const double*)(trow + (tgo + (ghi & nx)));
             }
+            trow = two ? trow + tpb : tlast;
         }
 #pragma unroll
         for (int i = 0; i < LB; i++) {
             const int r = r0 + i;
-            const int lev = min(lev0_ + i, a.nlev - 1);      // beyond the last level: re-read it (nothing is stored for it)
-            px[r] = WLOAD(double2, (const char*)(a.x + (size_t)lev*a.xs) + xo);
-            pg[r] = *(const double*)((const char*)(a.x + (size_t)lev*a.xs) + gxo);
+            px[r] = WLOAD(double2, xrow + xo);
+            pg[r] = *(const double*)(xrow + gxo);
+            xrow += ahead >= 1 + i ? xsb : 0;
         }
+        ahead -= LB;
     };
 #pragma unroll
-    for (int b = 0; b < AHEAD; b++) { load_batch(b*LB, lbeg + b*LB); __builtin_amdgcn_sched_barrier(0); }   // in THIS order: vmcnt is in-order
+    for (int b = 0; b < AHEAD; b++) { load_batch(b*LB); __builtin_amdgcn_sched_barrier(0); }   // in THIS order: vmcnt is in-order
+    WSTAMP4(3);                                          // level loads issued
     {
         double* se = sE[wv];
 #pragma unroll
@@ -691,11 +719,12 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
     for (int j = 0; j < N; j++) Ex[j] = sE[wv][qx*N + j];
     double cu[4], cp[4], pq[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int j = (qy - k) & 3;
-        cu[k] = j < 3 ? sE[wv][qy*N + j] : 0.0;
-        cp[k] = qy < 3 ? a.alpha*sE[wv][j*N + qy] : 0.0;
-        pq[k] = qx < 3 ? a.alpha*sE[wv][k*N + qx] : 0.0;
+    for (int k = 0; k < 4; k++) {                        // every entry is READ, at a clamped index, and the unused ones are then replaced
+        const int j = (qy - k) & 3;                      // by +0.0: selects, so that the LDS reads go out together (no exec-mask regions)
+        const double eu = sE[wv][qy*N + min(j, 2)], ep = a.alpha*sE[wv][j*N + min(qy, 2)], eq = a.alpha*sE[wv][k*N + min(qx, 2)];
+        cu[k] = j < 3 ? eu : 0.0;
+        cp[k] = qy < 3 ? ep : 0.0;
+        pq[k] = qx < 3 ? eq : 0.0;
     }
     double kc[3];
     const double hgaa = a.scale*h01.x, hgab = a.scale*h01.y, hgbb = a.scale*h23.x;
@@ -719,7 +748,9 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
     const bool okx = q < D::n1e, oky = qx < 3;
     const int wp00 = wp.y & 0xFFFF, wp01 = (wp.y >> 16) & 0xFFFF, wp10 = wp.z & 0xFFFF, wp11 = (wp.z >> 16) & 0xFFFF;
     const bool wy = wp.x >= 0;
-    gchar* wo = (gchar*)(wy ? (a.y + (size_t)lbeg*a.ys + wp.x) : (a.out + (size_t)lbeg*a.os + (-wp.x - 2)));
+    // (both rows are wave-uniform: two scalar candidates and a select per lane, not a branch around each row's arithmetic)
+    const unsigned long long wyr = (unsigned long long)(a.y + (size_t)lbeg*a.ys), wor = (unsigned long long)(a.out + (size_t)lbeg*a.os);
+    gchar* wo = (gchar*)((wy ? wyr : wor) + 8ull*(unsigned long long)(long long)(wy ? wp.x : -wp.x - 2));
     const long long wst = 8*(wy ? a.ys : a.os);
 #pragma unroll
     for (int i = 0; i < LB; i++) s_x[wv][i][ZERO] = 0.0;
@@ -731,7 +762,7 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
     for (int b0 = 0; b0 < LCT; b0 += LB) {
         const bool pass = (b0/LB)%2 == 0;                // (unrolled: a constant)
         __builtin_amdgcn_sched_barrier(0);
-        load_batch((b0 + AHEAD*LB)%LCT, lbeg + b0 + AHEAD*LB);
+        load_batch((b0 + AHEAD*LB)%LCT);                 // (the levels lbeg + b0 + AHEAD*LB ...: the stepped rows stand there)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < LB; i++) {
@@ -793,6 +824,9 @@ __device__ __forceinline__ void apply_wave_body(const ElemArgs& a) {
             wo += wst;
         }
         wave_fence();
+#ifdef MIMSEM_STAMPS
+        if (4 + (lbeg - lbeg0 + b0)/LB < 11) WSTAMP4(4 + (lbeg - lbeg0 + b0)/LB);      // batch computed, its stores issued (the first seven)
+#endif
         if (b0 + LB < LCT) wave_exit_if_done(nl - (b0 + LB));     // (nothing follows the level loop: see wave_exit_if_done)
     }
     }
@@ -801,6 +835,7 @@ template <int N, int OP, int LCT, bool ACCUM>
 __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_apply_wave(ElemArgs a) { apply_wave_body<N, OP, LCT, ACCUM, false>(a); }
 template <int N, int OP, int LCT, bool ACCUM>
 __global__ __launch_bounds__(64*WNW) __attribute__((amdgpu_waves_per_eu(3, 8))) void k_apply_wave_list(ElemArgs a) { apply_wave_body<N, OP, LCT, ACCUM, true>(a); }
+#undef WSTAMP4
 }  // namespace own4
 
 // k_apply_wave2<OP, LCT, ACCUM>: the 2-form-valued operators at p = 3 -- Wmat, Whmat (2-form in), WtQUmat, WtQdUdz_mat (1-form in, 1-form

@@ -2,7 +2,8 @@
 """The loop of profiles/umat_balance_ab.txt and profiles/umat_store_policy_ab.txt: the bench.py step (Umat apply over the 24 x 24 x 6
 sphere x 30 levels) 2 000 times back to back, the host clock around one synchronise, three samples; prints us per step, the plan's
 stats and a hash of y after the first call.  One library per process: MIMSEM_LIB=build_ab/libmimsem_hip_NAME.so TAG=NAME; alternate the
-processes (parent, new, three times).  WARM = calls before the first sample (50)."""
+processes (parent, new, three times).  WARM = calls before the first sample (50).  SPLIT = levels per requested part (the default
+rule otherwise; MIMSEM_WAVE_BALANCE=k selects the planned list as everywhere)."""
 import ctypes as C
 import hashlib
 import os
@@ -27,6 +28,8 @@ for g in geoms:
 dm = DeviceMesh(topos, geoms, nk=NK, numbering="global")
 rng = np.random.default_rng(1)
 eng = Engine(dm, device=0)
+if os.environ.get("SPLIT"):                            # SPLIT=10: requested parts of 10 levels (mimsem_ctx_set_wave_split, the order as it is)
+    assert eng.L.mimsem_ctx_set_wave_split(eng.ctx, int(os.environ["SPLIT"]), -1) == 0
 x = eng.tensor(rng.standard_normal((NK, dm.n1))); y = eng.zeros(NK, dm.n1)
 call, _ = eng.prepare_apply("UMAT", x, lev0=0, scale=1e8, flags=1, out=y)
 call()
