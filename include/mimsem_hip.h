@@ -645,6 +645,16 @@ int mimsem_column_max_norms(mimsem_ctx* ctx, const double* norm_squares, double*
  * (the half-time averages theta_h = 0.5 theta_j + 0.5 theta_i of :1896-1912).  theta2 / thetaL: either may be null. */
 int mimsem_column_diag_theta_blend(mimsem_ctx* ctx, const double* rho, const double* rt, double* theta2, const double* blend2,
                                    double* thetaL, const double* blendL, double wa, double wb);
+/* diagTheta2 of the box twin (box/VertSolve.cpp:499-531): theta2 = wa * VA2_up^-1 VAB2_up rt + wb * blend2 on the nk + 1 interfaces, the
+ * test functions upwinded by the VERTICAL velocity over dtw (the reference passes 0.25 dt): AssembleLinCon_up and AssembleLinearWithRho_up
+ * (box/VertOps.cpp:2601-2741).  VA2_up is block tridiagonal and not symmetric; one launch runs a block-Thomas sweep along every column.
+ * rho, rt [nEl][nk n2e], velz [nEl][(nk-1) n2e], theta2 / blend2 [nEl][(nk+1) n2e]; blend2 may be null (then wa, wb are not read).
+ * Condition of use: |dtw w| < 1 at every quadrature point (w the interpolant of velz, not divided by det).  Then the off-diagonal blocks
+ * are O(dtw w) of the diagonal ones and the sweep, which pivots neither across blocks nor inside them, is safe; the entry does not test it.
+ * Orders 1..4 (MIMSEM_ERR_UNSUPPORTED above), nk >= 2 (else MIMSEM_ERR_ARG).  Deterministic, no atomics.  The sweep's factors go through
+ * the column workspace: capturable once a call outside a capture has sized it (MIMSEM_ERR_STATE otherwise). */
+int mimsem_column_diag_theta_wup(mimsem_ctx* ctx, double dtw, const double* rho, const double* rt, const double* velz,
+                                 double* theta2, const double* blend2, double wa, double wb);
 
 /* ---- the Newton loop of solve_schur_column_3: VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246) ------------------------------- */
 /* The residual assembly and the update around mimsem_column_solve_schur_3, for EVERY column, orders 1..4 (MIMSEM_ERR_UNSUPPORTED above;

@@ -172,4 +172,11 @@ struct NewtonWS {
     }
 };
 
+// what the back substitution of mimsem_column_diag_theta_wup reads per interface: G_I = D'_I^-1 U_I for the nk interfaces that have one
+// above them (blocks lane-major, as the Thomas factors of SweepWS) and the forward vector y_I on all nk + 1
+struct ThetaWupWS {
+    double *G, *y;
+    void carve(ColArena& a, const ColDims& d) { G = a.take(d.nEl*d.nk*d.nn()); y = a.take(d.nEl*(d.nk + 1)*d.n2); }
+};
+
 }  // namespace mimsem

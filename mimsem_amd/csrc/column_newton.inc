@@ -426,6 +426,145 @@ int diag_theta_fused(mimsem_ctx* c, const double* rho, const double* rt, double*
     return MIMSEM_OK;
 }
 
+// ---- diagTheta2 of the box twin (box/VertSolve.cpp:499-531): test functions upwinded by the VERTICAL velocity ------------------------
+//   theta = VA2_up^-1 VAB2_up rt,   AssembleLinCon_up / AssembleLinearWithRho_up (box/VertOps.cpp:2601-2741), dtw = 0.25 dt.
+// At quadrature point q of level k, with wb / wt the interpolants of velz at the interfaces below / above the level (0 at the two
+// ends of the column, not divided by det):  N0b = (2 - dtw wb)/2, N1b = dtw wb/2, N0t = -dtw wt/2, N1t = (2 + dtw wt)/2, and
+//   VAB2_up rows k / k+1, column k:   W^T diag((N0b + N0t)/2 q0) W,  W^T diag((N1b + N1t)/2 q0) W            (q0 = w_q SCALE / det)
+//   VA2_up  (k,k) += rk N0b q0,  (k,k+1) = rk N0t q0,  (k+1,k) = rk N1b q0,  (k+1,k+1) += rk N1t q0          (rk = rho_k(q) / (2 det))
+// so VA2_up is block TRIDIAGONAL over the nk + 1 interfaces and not symmetric (the lumped VA2 of k_diag_theta is block diagonal).
+// One task per COLUMN: a block-Thomas sweep upwards,  D'_I = D_I - L_I G_{I-1},  G_I = D'_I^-1 U_I,  y_I = D'_I^-1 (f_I - L_I y_{I-1}),
+// then theta_I = y_I - G_I theta_{I+1} downwards; G and y of every interface wait in the column workspace (mimsem::ThetaWupWS).
+// The sweep does not pivot across blocks and the block inverse takes the diagonal pivots: with |dtw w| < 1 the off-diagonal blocks are
+// O(dtw w) of the diagonal ones (N0t, N1b against N0b, N1t), so D'_I stays a small perturbation of a mass block.  Fixed order, no atomics.
+struct DiagThetaWupArgs {
+    NewtonGeo g;
+    double dtw;
+    const double *rho, *rt, *velz;                 // [nEl][nk n2], [nEl][nk n2], [nEl][(nk-1) n2]
+    double* theta2; const double* blend2;          // [nEl][(nk+1) n2]; blend2 or null
+    double *G, *y;                                 // ThetaWupWS
+    double wa, wb;
+};
+template <int N>
+__global__ __launch_bounds__(64) void k_diag_theta_wup(DiagThetaWupArgs a) {
+    using T = ColTask<N>; using R = dpp::Rows<N>;
+    constexpr int N2 = T::N2, NP = T::NP, nn = N2*N2;
+    const int lane = threadIdx.x, r = lane%16;
+    const int nk = a.g.nk, np1 = nk + 1, nm = nk - 1;
+    const int e0 = blockIdx.x*4 + lane/16;
+    const bool live = e0 < a.g.nEl;
+    const int e = live ? e0 : a.g.nEl - 1;
+    T t; t.init(a.g, e, r);
+    const bool act = live && r < N2;
+    const double* rho = a.rho + (size_t)e*nk*N2 + t.rr;
+    const double* rt = a.rt + (size_t)e*nk*N2 + t.rr;
+    const double* vz = a.velz + (size_t)e*nm*N2 + t.rr;
+    double* Ge = a.G + (size_t)e*nk*nn + t.rr;          // blocks lane-major ([j][r]), as k_thomas_dpp keeps its factors
+    double* ye = a.y + (size_t)e*np1*N2 + t.rr;
+    double* tho = a.theta2 + (size_t)e*np1*N2 + t.rr;
+    const double* blo = a.blend2 ? a.blend2 + (size_t)e*np1*N2 + t.rr : nullptr;
+    const double wa = a.wa, wb = a.wb, dtw = a.dtw;
+    // what level I - 1 leaves for interface I: its parts of D_I and f_I, the coefficient of L_I, and w at its top (= the bottom of level I)
+    double cbb[NP], cba[NP], xm[NP], wq[NP];
+#pragma unroll
+    for (int p = 0; p < NP; p++) cbb[p] = cba[p] = xm[p] = wq[p] = 0.0;
+    double Gp[N2], yp = 0.0;
+#pragma unroll
+    for (int j = 0; j < N2; j++) Gp[j] = 0.0;
+#pragma unroll 1
+    for (int I = 0; I <= nk; I++) {                      // (I and nk are uniform: every lane of a row takes the same branches)
+        const bool lo = I > 0, hi = I < nk;
+        double cD[NP], cL[NP], cU[NP], x[NP];
+#pragma unroll
+        for (int p = 0; p < NP; p++) { cD[p] = cbb[p]; cL[p] = cba[p]; x[p] = xm[p]; cU[p] = 0.0; }
+        if (hi) {
+            // (the rows of W of my quadrature points are fetched per level too, for the three interpolations: see the projection below)
+            double Wr[NP][N2], rq[NP], tq[NP], wt[NP];
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const int q = min(r + 16*p, T::MP12 - 1);
+#pragma unroll
+                for (int j = 0; j < N2; j++) Wr[p][j] = a.g.W[q*N2 + j];
+            }
+            auto interp = [&](double (&out)[NP], double v) {
+#pragma unroll
+                for (int p = 0; p < NP; p++) { double s = 0.0; dpp::MatvecAcc<N2>::run(s, Wr[p], v); out[p] = s; }
+            };
+            interp(rq, rho[(size_t)I*N2]); interp(tq, rt[(size_t)I*N2]);
+            if (I < nm) interp(wt, vz[(size_t)I*N2]);
+            else {
+#pragma unroll
+                for (int p = 0; p < NP; p++) wt[p] = 0.0;
+            }
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                const double sb = dtw*wq[p], st = dtw*wt[p];
+                const double N0b = 0.5*(2.0 - sb), N1b = 0.5*sb, N0t = 0.5*(-st), N1t = 0.5*(2.0 + st);
+                const double rk = rq[p]*(0.5/t.det[p]);
+                cD[p] += (rk*N0b)*t.q0[p]; cU[p] = (rk*N0t)*t.q0[p];
+                cba[p] = (rk*N1b)*t.q0[p]; cbb[p] = (rk*N1t)*t.q0[p];
+                x[p] += ((0.5*(N0b + N0t))*t.q0[p])*tq[p];
+                xm[p] = ((0.5*(N1b + N1t))*t.q0[p])*tq[p];
+                wq[p] = wt[p];
+            }
+        }
+        // (W^T x)[r] with my column of W fetched here, once per interface, instead of ColTask's resident copy: at order 4 the 25 doubles
+        // are what the sweep's three live blocks leave no registers for
+        double f = 0.0;
+        {
+            double Wc[T::MP12];
+#pragma unroll
+            for (int q = 0; q < T::MP12; q++) Wc[q] = a.g.W[q*N2 + t.rr];
+            dpp::ProjAcc<N>::run(f, Wc, x);
+        }
+        double D[N2];
+        t.block(D, cD);
+        if (lo) {
+            double L[N2];
+            t.block(L, cL);
+            dpp::MulSub<N2>::run(D, L, Gp);
+            f -= R::matvec(L, yp);
+        }
+        R::inverse(D, r);
+        yp = R::matvec(D, f);
+        if (act) ye[(size_t)I*N2] = yp;
+        if (hi) {
+            double U[N2];
+            t.block(U, cU);
+            R::mul(Gp, D, U);
+            if (act) {
+#pragma unroll
+                for (int j = 0; j < N2; j++) Ge[(size_t)I*nn + j*N2] = Gp[j];
+            }
+        }
+    }
+    // back substitution: every lane re-reads its own row of G and its own entry of y (program order)
+    double th = yp;
+#pragma unroll 1
+    for (int I = nk; I >= 0; I--) {
+        if (I < nk) {
+#pragma unroll
+            for (int j = 0; j < N2; j++) Gp[j] = Ge[(size_t)I*nn + j*N2];
+            th = ye[(size_t)I*N2] - R::matvec(Gp, th);
+        }
+        const double v = blo ? wa*th + wb*blo[(size_t)I*N2] : th;
+        if (act) tho[(size_t)I*N2] = v;
+    }
+}
+
+int diag_theta_wup(mimsem_ctx* c, double dtw, const double* rho, const double* rt, const double* velz, double* theta2,
+                   const double* blend2, double wa, double wb) {
+    mimsem::ThetaWupWS w;
+    if (int rc = plan_col(c, w)) return rc;
+    DiagThetaWupArgs a{};
+    fill_newton_geo(c, a.g);
+    a.dtw = dtw; a.rho = rho; a.rt = rt; a.velz = velz; a.theta2 = theta2; a.blend2 = blend2; a.G = w.G; a.y = w.y; a.wa = wa; a.wb = wb;
+    const unsigned grid = newton_grid(c->nEl);
+    if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_diag_theta_wup<N()>), dim3(grid), dim3(64), 0, c->stream, a); })) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
+    return MIMSEM_OK;
+}
+
 // VertSolve::MaxNorm (eul/VertSolve.cpp:228) on the squares mimsem_column_newton_update leaves: one workgroup per column forms the eight sums
 // (fixed order: a 256-thread tree over a strided partition -- reproducible) and writes the four ratios; a second launch takes their maxima
 // over the columns (NaN wins, as a comparison on the host would see it)
@@ -535,6 +674,15 @@ int mimsem_column_diag_theta_blend(mimsem_ctx* c, const double* rho, const doubl
     if (!c || !rho || !rt || (!theta2 && !thetaL)) return MIMSEM_ERR_ARG;
     if (!sweep_supported(c)) return MIMSEM_ERR_UNSUPPORTED;
     return diag_theta_fused(c, rho, rt, theta2, blend2, thetaL, blendL, wa, wb);
+}
+
+int mimsem_column_diag_theta_wup(mimsem_ctx* c, double dtw, const double* rho, const double* rt, const double* velz,
+                                 double* theta2, const double* blend2, double wa, double wb) {
+    if (!c || !rho || !rt || !velz || !theta2) return MIMSEM_ERR_ARG;
+    if (c->nk < 2) return MIMSEM_ERR_ARG;
+    if (!sweep_supported(c)) return MIMSEM_ERR_UNSUPPORTED;
+    if (c->nEl == 0) return MIMSEM_OK;
+    return diag_theta_wup(c, dtw, rho, rt, velz, theta2, blend2, wa, wb);
 }
 
 }  // extern "C"

@@ -882,6 +882,17 @@ class Engine:
               "diag_theta_blend")
         return th2, thL
 
+    def diag_theta_wup(self, dtw, rho, rt, velz, blend2=None, wa=1.0, wb=0.0):
+        """diagTheta2 of the box twin (box/VertSolve.cpp:499-531): theta on the nk+1 interfaces with the test functions upwinded by the
+        vertical velocity velz [nEl, (nk-1) n2e] over dtw, optionally blended: wa * theta(rho, rt, velz) + wb * blend2
+        (mimsem_column_diag_theta_wup; |dtw w| < 1 is the caller's to keep)"""
+        self._col(rho, self.nk, "rho"); self._col(rt, self.nk, "rt"); self._col(velz, self.nk - 1, "velz")
+        self._col(blend2, self.nk + 1, "blend2", optional=True)
+        th2 = self._cols(self.nk + 1)
+        check(self.L.mimsem_column_diag_theta_wup(self.ctx, dtw, _ptr(rho), _ptr(rt), _ptr(velz), _ptr(th2), _ptr(blend2), wa, wb),
+              "diag_theta_wup")
+        return th2
+
     def newton_residual(self, dt, rayleigh, theta, Pi, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, rho_h, rt_h, exner_j,
                         add_w=None, add_rho=None, add_rt=None):
         """mimsem_column_newton_residual: (F_w, F_rho, F_eta, F_exner, th_w3, eta, k2i) for every column (VertSolve.cpp:1806-1851)"""

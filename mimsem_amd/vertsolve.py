@@ -240,7 +240,7 @@ class VertSolve:
         return fw, F, G
 
     def solve_schur_2(self, velz_i, rho_i, rt_i, exner_i, zv, horiz_forcing=None, udwdx=None, hs_lat=None, maxit=20, tol=1.0e-12,
-                      schur3_flags=0, verbose=False, fused=None):
+                      schur3_flags=0, verbose=False, fused=None, theta_up=False, vert_mom_vort=None):
         """VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246) for EVERY column at once: Newton iterations on (w, rho, rt, Pi) with
         solve_schur_column_3 as the linear solve, all state in the "vertical" layout [nEl][slots*n2e] (L2Vecs::vz).
 
@@ -248,12 +248,19 @@ class VertSolve:
         theta_h is on the nk+1 interfaces; the two join dF_z / dG_z BEFORE the VB product.  udwdx: optional [nEl][(nk-1)*n2e] (:1134).
         hs_lat: latitude of the quadrature points [nEl][mp12] switches the Held-Suarez temperature forcing on (:1151-1154).
         schur3_flags: passed to solve_schur_3 (3 with rayleigh = 0: the box twin's solve).  fused: None = the default route of this order.
+        theta_up / vert_mom_vort: the loop of the box twin (box/VertSolve.cpp:1264-1458; with schur3_flags = 3, rayleigh = 0, no hs_lat).
+        theta_up: theta_i / theta_j come from diagTheta2 with the test functions upwinded by velz_i / velz_j over 0.25 dt (box :1312, :1394;
+        Engine.diag_theta_wup, orders 1..4, needs |0.25 dt w| < 1).  vert_mom_vort(velz_j) -> uuz [nEl][(nk-1)*n2e] (VortDiag.vert_mom_vort
+        bound to u2l): with udwdx it makes the term time-centred, F_w += 0.5 dt udwdx + 0.5 dt uuz_j (box :1343-1346), uuz_j = udwdx in
+        the first iteration (:1326) and recomputed from velz_j at the end of each (:1403).
         Stops when the exner, rho AND rt norms are below tol (:1202).  Returns (velz, rho, rt, exner) at the new time level and leaves
         theta_h / exner_h (what Euler::Strang reads), the per-iteration max-norms (history: exner, w, rho, rt) and k2i_z in self.*"""
         eng, nk, dt = self.eng, self.nk, self.dt
         fused = self.fused2 if fused is None else (fused and eng.mesh.n <= 4)       # (above order 4 the entries are unsupported: composed)
         velz_j, rho_j, rt_j, exner_j = velz_i.clone(), rho_i.clone(), rt_i.clone(), exner_i.clone()      # :1099-1102
-        if fused:
+        if theta_up:
+            theta_i = eng.diag_theta_wup(0.25 * dt, rho_i, rt_i, velz_i)                                # diagTheta2, box :1312
+        elif fused:
             theta_i, _ = eng.diag_theta_blend(rho_i, rt_i, wantL=False)                                 # diagTheta2 :1105
         else:
             theta_i = eng.diag_theta(1, rho_i, rt_i)
@@ -261,16 +268,20 @@ class VertSolve:
         exner_h, velz_h, rho_h, rt_h = exner_i, velz_i, rho_i, rt_i                                     # :1112-1117 (never written in place)
         self.history = []
         self._k2i = None
+        centred = udwdx is not None and vert_mom_vort is not None
+        uuz_j = udwdx                                                                                   # box :1326
         for itt in range(1, maxit + 1):
             dFx, dGx = horiz_forcing(rho_i, rho_j, theta_h) if horiz_forcing is not None else (None, None)      # :1124
             hs = eng.temp_forcing_hs(hs_lat, exner_h, theta_h, rho_h) if hs_lat is not None else None          # :1152
             if fused:
                 F_w, F_rho, F_rt, F_exner, self._k2i = eng.newton2_residual(
                     dt, self.rayleigh or 0.0, theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, exner_j,
-                    add_w=udwdx, add_rho_pre=dFx, add_rt_pre=dGx, add_rt_post=hs)
+                    add_w=0.5 * udwdx + 0.5 * uuz_j if centred else udwdx, add_rho_pre=dFx, add_rt_pre=dGx, add_rt_post=hs)
             else:
                 F_w, F_z, G_z = self.assemble_residual(theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv)     # :1131
-                if udwdx is not None:
+                if centred:
+                    F_w = F_w + 0.5 * dt * udwdx + 0.5 * dt * uuz_j                                        # box :1343-1346
+                elif udwdx is not None:
                     F_w = F_w + dt * udwdx                                                                 # :1134
                 F_exner = eng.column_eos(0, rt_j, exner_j)                                                 # Assemble_EOS_Residual :1135
                 dF_z = rho_j + dt * self.V10(F_z) - rho_i                                                  # :1137-1142
@@ -296,10 +307,16 @@ class VertSolve:
                 rho_h = 0.5 * rho_i + 0.5 * rho_j; rt_h = 0.5 * rt_i + 0.5 * rt_j
             nv = eng.allreduce(nv, op="max")                                                               # MPI_Allreduce(MAX) :1195-1198
             # (the theta diagnosis does not depend on the norms: launched BEFORE the host waits for them)
-            if fused:
+            if theta_up and fused:
+                theta_h = eng.diag_theta_wup(0.25 * dt, rho_j, rt_j, velz_j, blend2=theta_i, wa=0.5, wb=0.5)   # box :1394-1399
+            elif theta_up:
+                theta_h = 0.5 * eng.diag_theta_wup(0.25 * dt, rho_j, rt_j, velz_j) + 0.5 * theta_i
+            elif fused:
                 theta_h, _ = eng.diag_theta_blend(rho_j, rt_j, blend2=theta_i, wa=0.5, wb=0.5, wantL=False)   # :1186-1191
             else:
                 theta_h = 0.5 * eng.diag_theta(1, rho_j, rt_j) + 0.5 * theta_i
+            if centred:
+                uuz_j = vert_mom_vort(velz_j)                                                              # AssembleVertMomVort, box :1403
             nv = nv.tolist()
             norms = dict(exner=nv[0], w=nv[1], rho=nv[2], rt=nv[3])
             self.history.append(norms)

@@ -33,11 +33,13 @@ class VortDiag:
         self.eng, self.horiz, self.vert, self.rtol = eng, horiz, vert, rtol
         self.nk, self.ni = eng.nk, eng.nk - 1
         self._its = {"uz": None, "dwdx": None}          # fixed PCG length per solve: None = find it adaptively, 0 = adaptive from now on
-        self._log = torch.zeros(2, self.ni, dtype=torch.float64, device=eng.device)     # worst |b - A x|^2 / |b|^2 per interface since check()
+        # worst |b - A x|^2 / |b|^2 per interface since check(): rows uz, dwdx and the unit-thickness mass solve of vert_mom_vort
+        self._log = torch.zeros(3, self.ni, dtype=torch.float64, device=eng.device)
         self.its = {}                                   # iterations of the last solve of each kind
         self.fixed_its = {}                             # the fixed_its its PCG was launched with (0: adaptive)
         self.logged = 0
         self.missed = 0
+        self.unit_mass = None                           # vert_mom_vort's mass solver without thickness (made on first use)
 
     @property
     def m_its(self):
@@ -69,8 +71,8 @@ class VortDiag:
         return x
 
     def check(self):
-        """the ONE read of the fixed-length solves since the last call.  False: some interface missed 30 rtol -- both solves have switched
-        to the adaptive PCG; the caller redoes the diagnoses"""
+        """the ONE read of the fixed-length solves since the last call.  False: some interface missed 30 rtol -- the solves have switched
+        to the adaptive PCG (vert_mom_vort's mass solver leaves its fixed-length mode); the caller redoes the diagnoses"""
         v, = CheckLog.read(self._log)
         self._log.zero_()
         self.logged = 0
@@ -78,6 +80,8 @@ class VortDiag:
         if not ok:
             self.missed += 1
             self.m_its = 0
+            if self.unit_mass is not None:
+                self.unit_mass.chebyshev = False
         return ok
 
     def horiz_pot_vort(self, velx, rho):
@@ -98,6 +102,25 @@ class VortDiag:
         P = eng.elem_block_pc_levels("UHMAT", self.ni, f=rb, lev0=0, lev_step=0, scale=SCALE)
         A = lambda v: eng.apply_levels("UHMAT", v, 0, f=rb, lev0=0, scale=SCALE)  # F->assemble(rho_h, 0, false, SCALE)
         return self._solve("dwdx", A, rhs, P)
+
+    def vert_mom_vort(self, ul, velz_h):
+        """VertSolve::AssembleVertMomVort of the box twin (box/VertSolve.cpp:1460-1499): uuz [nEl, (nk-1) n2e] in the VERTICAL layout from
+        ul [nk, n1] and velz_h [nk-1, n2] (horizontal layout), all nk - 1 interfaces per call:
+            dwdx_i = M1o^-1 E12 M2o velz_i,   uuz_i = Rz(1/2 u_i + 1/2 u_{i+1}; SCALE) dwdx_i,   HorizToVert
+        M1o / M2o: level 0, SCALE, no thickness (box/Assembly.cpp:45,172); Rz = WtQdUdz_mat.  The mass solve is unit_mass, a MassSolver
+        without thickness, fixed length.  Its TRUE residual is logged with the other solves of this class and read by check(): on a uniform
+        box the element-block preconditioner is exact (P M1o = I), the residual the last Chebyshev sweep saw -- what MassSolver.verify()
+        judges -- is then zero after the first step whatever the later steps do, and only the true residual shows a solve cut short"""
+        eng = self.eng
+        if self.unit_mass is None:
+            from .krylov import MassSolver
+            self.unit_mass = MassSolver(eng, SCALE, vert_scale=False)
+        rhs = eng.incidence("E12", eng.apply_levels("WMAT", velz_h, 0, lev0=0, scale=SCALE, flags=0))        # M2->assemble(0, SCALE, false), E12
+        dwdx, self.its["unit_mass"] = self.unit_mass.solve(rhs, lev0=0)                                  # KSPSolve(ksp1, tmp1, dwdx)
+        log_true_residual(eng, lambda v: self.unit_mass.apply(v, 0), dwdx, rhs, self._log[2])
+        self.logged += 1
+        ub = eng.combine(ul[:-1], 0.5, beta=0.5, c=ul[1:])                                                # 0.5 ul[kk] + 0.5 ul[kk+1]
+        return eng.l2_horiz_to_vert(eng.apply("WTQDUDZ", dwdx, f=ub, lev0=0, scale=SCALE))              # Rz->assemble(_ul, SCALE), HorizToVert
 
     def vert_mass_flux(self, velz1, velz2, rho1, rho2):
         """Fz [nk-1, n2] in the horizontal layout from velz [nk-1, n2] and rho [nk, n2] in the horizontal layout"""
