@@ -2585,7 +2585,6 @@ int schur_operator(mimsem_ctx* c, double dt, const double* theta, const double* 
 #include "column_dpp.inc"
 #include "column_penta.inc"
 #include "column_newton.inc"
-#include "column_newton2.inc"
 
 namespace {
 // default for orders 1..3: the LDS-free fused path of column_dpp.inc; MIMSEM_SCHUR_FUSED=rows|wave|0 selects the round-1 kernels

@@ -8,6 +8,13 @@
 //   k_newton_lev   one task per (column, level):     F_w completed, F_rho, F_rt -> F_eta, F_exner, theta in W3, eta
 //   k_newton_upd   one task per (column, level):     eta_j, the state update, rho theta from the EOS, the half-time states, norms
 //   k_diag_theta   one task per (column, interface / level): diagTheta2 and diagTheta_L2 (:289-352)
+// The OTHER vertical Newton loop, VertSolve::solve_schur_2 (:1059-1246, the caller of solve_schur_column_3: assemble_residual :386-430, the
+// right-hand sides of :1134-1154, the update of :1159-1183) runs on the same two residual kernels with EC = false and an update of its own:
+//   k_newton_ifc / k_newton_lev <N, EC>   EC = true is the list above.  EC = false: theta lives on the nk+1 INTERFACES
+//                  (AssembleLinearWithTheta, VertOps.cpp:669-730, not AssembleLinearWithRT), the pressure gradient and V10 G_z enter with dt
+//                  (not dt/2), there are no entropy-conservation terms, no f_theta_corr and no entropy variables (F_rt is the output), and
+//                  the horizontal forcing is added BEFORE the VB product (:1145-1149), the Held-Suarez term after it (:1151-1154)
+//   k_newton2_upd  one thread per level entry:       x_j += d_x, x_h = 0.5 x_i + 0.5 x_j, the squares MaxNorm sums
 // Every operator of the chain is W^T diag(c) W (or the inverse of one) with c a pointwise function of interpolated fields, so
 // an APPLY never needs the block: interpolate the vector to the quadrature points (9 DPP FMAs), scale, project back (16 DPP
 // FMAs).  Blocks are only formed where an inverse is needed (A^-1, B^-1, B(rho)^-1, B(rho theta)^-1).  Tasks are 16 lanes
@@ -50,6 +57,19 @@ struct ColTask {
             q0[p] = Q[p]*(VSCALE/det[p]);
         }
     }
+    // the opening of a task kernel: four 16-lane tasks per wavefront, `per` of them in a column.  Sets me up for my task's column, hands
+    // back its index within the column (a level or an interface) and says whether this lane stores: the rows past the last task of the
+    // grid redo that task and store nothing, and so do the lanes past the block row (r >= N2)
+    __device__ bool start(const NewtonGeo& G, int per, int& idx) {
+        const int lane = threadIdx.x, r_ = lane%16;
+        const long long task0 = (long long)blockIdx.x*4 + lane/16, ntask = (long long)G.nEl*per;
+        const bool live = task0 < ntask;
+        const long long task = live ? task0 : ntask - 1;
+        const int e_ = (int)(task/per);
+        idx = (int)(task%per);
+        init(G, e_, r_);
+        return live && r_ < N2;
+    }
     __device__ void geo(double (&tI)[NP], double (&th)[NP], int k) const {
 #pragma unroll
         for (int p = 0; p < NP; p++) {
@@ -73,28 +93,26 @@ struct ColTask {
 struct NewtonIfcArgs {
     NewtonGeo g;
     double dt, rayleigh;
-    const double *theta, *Pi, *velz1, *velz2, *rho1, *rho2, *add_w;     // add_w optional
-    double *F, *G, *u, *wF, *fwA, *k2;                                    // [nEl][nk-1][n2] each
+    const double *theta, *Pi, *velz1, *velz2, *rho1, *rho2, *add_w;     // theta: EC [nEl][nk][n2], else [nEl][nk+1][n2]; add_w optional
+    double *F, *G, *u, *wF, *fwA, *k2;                                    // [nEl][nk-1][n2] each; wF: EC only
 };
-template <int N>
+template <int N, bool EC>
 __global__ __launch_bounds__(64) void k_newton_ifc(NewtonIfcArgs a) {
     using T = ColTask<N>; using R = dpp::Rows<N>;
     constexpr int N2 = T::N2, NP = T::NP;
-    const int lane = threadIdx.x, r = lane%16;
     const int nk = a.g.nk, nm = nk - 1;
-    const long long task0 = (long long)blockIdx.x*4 + lane/16, ntask = (long long)a.g.nEl*nm;
-    const bool live = task0 < ntask;
-    const long long task = live ? task0 : ntask - 1;
-    const int e = (int)(task/nm), i = (int)(task%nm);
-    T t; t.init(a.g, e, r);
-    const bool act = live && r < N2;
+    T t; int i;
+    const bool act = t.start(a.g, nm, i);
+    const int e = t.e;
     const double hdt = 0.5*a.dt;
     const size_t v0 = ((size_t)e*nk + i)*N2 + t.rr, v1 = v0 + N2, io = ((size_t)e*nm + i)*N2 + t.rr;
 
     double tI0[NP], th0[NP], tI1[NP], th1[NP];
     t.geo(tI0, th0, i); t.geo(tI1, th1, i + 1);
+    // theta at the quadrature points: EC from the levels below and above, else of THIS interface, slot i+1 of the nk+1 (AssembleLinearWithTheta)
     double thq0[NP], thq1[NP], piq0[NP], piq1[NP], c[NP], x[NP];
-    t.interp(thq0, a.theta[v0]); t.interp(thq1, a.theta[v1]);
+    if constexpr (EC) { t.interp(thq0, a.theta[v0]); t.interp(thq1, a.theta[v1]); }
+    else t.interp(thq0, a.theta[((size_t)e*(nk + 1) + i + 1)*N2 + t.rr]);
     t.interp(piq0, a.Pi[v0]);    t.interp(piq1, a.Pi[v1]);
     // A^-1                                               AssembleLinearInv, VertOps.cpp:422-430
     double Ai[N2];
@@ -139,12 +157,15 @@ __global__ __launch_bounds__(64) void k_newton_ifc(NewtonIfcArgs a) {
     const double gPi = R::matvec(Ai, bp);
     double cT[NP], gq[NP];
 #pragma unroll
-    for (int p = 0; p < NP; p++) cT[p] = t.q0[p]*(0.5*thq0[p]/t.det[p]) + t.q0[p]*(0.5*thq1[p]/t.det[p]);
+    for (int p = 0; p < NP; p++) {
+        if constexpr (EC) cT[p] = t.q0[p]*(0.5*thq0[p]/t.det[p]) + t.q0[p]*(0.5*thq1[p]/t.det[p]);          // AssembleLinearWithRT :621-662
+        else cT[p] = t.q0[p]*(0.5*th0[p])*(thq0[p]/t.det[p]) + t.q0[p]*(0.5*th1[p])*(thq0[p]/t.det[p]);      // AssembleLinearWithTheta :685-725
+    }
     t.interp(gq, gPi);
 #pragma unroll
     for (int p = 0; p < NP; p++) x[p] = cT[p]*gq[p];
     const double tA1 = t.proj(x);
-    fw += hdt*tA1;
+    fw += (EC ? hdt : a.dt)*tA1;                                                                              // assemble_residual_ec: dt/2; assemble_residual: dt (:412)
     // G_z = A^-1 VA(theta) F
     t.interp(gq, F);
 #pragma unroll
@@ -158,56 +179,63 @@ __global__ __launch_bounds__(64) void k_newton_ifc(NewtonIfcArgs a) {
         for (int p = 0; p < NP; p++) x[p] = (t.q0[p]*(wgt*(th1[p] + th0[p])))*(v2q[p] + v1q[p]);
         fw += hdt*a.rayleigh*t.proj(x);
     }
-    // entropy-conservation terms: + 0.5dt V01 (VB(theta) Pi) - 0.5dt C(grad theta)^T Pi;  grad theta = A^-1 V01 (VB theta)
+    double wF = 0.0;
+    if constexpr (EC) {
+        // entropy-conservation terms: + 0.5dt V01 (VB(theta) Pi) - 0.5dt C(grad theta)^T Pi;  grad theta = A^-1 V01 (VB theta)
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = (cB1[p]*(thq1[p]/(th1[p]*t.det[p])))*piq1[p];                    // AssembleConstWithRho(theta) :508-521
-    double btp = t.proj(x);
+        for (int p = 0; p < NP; p++) x[p] = (cB1[p]*(thq1[p]/(th1[p]*t.det[p])))*piq1[p];                    // AssembleConstWithRho(theta) :508-521
+        double btp = t.proj(x);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = (cB0[p]*(thq0[p]/(th0[p]*t.det[p])))*piq0[p];
-    btp -= t.proj(x);
-    fw += hdt*btp;
+        for (int p = 0; p < NP; p++) x[p] = (cB0[p]*(thq0[p]/(th0[p]*t.det[p])))*piq0[p];
+        btp -= t.proj(x);
+        fw += hdt*btp;
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB1[p]*thq1[p];
-    double bt = t.proj(x);
+        for (int p = 0; p < NP; p++) x[p] = cB1[p]*thq1[p];
+        double bt = t.proj(x);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB0[p]*thq0[p];
-    bt -= t.proj(x);
-    const double gTh = R::matvec(Ai, bt);
-    double cg[NP];
-    t.interp(gq, gTh);
+        for (int p = 0; p < NP; p++) x[p] = cB0[p]*thq0[p];
+        bt -= t.proj(x);
+        const double gTh = R::matvec(Ai, bt);
+        double cg[NP];
+        t.interp(gq, gTh);
 #pragma unroll
-    for (int p = 0; p < NP; p++) cg[p] = t.q0[p]*(0.5*gq[p]/t.det[p]);
+        for (int p = 0; p < NP; p++) cg[p] = t.q0[p]*(0.5*gq[p]/t.det[p]);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cg[p]*(piq0[p] + piq1[p]);
-    fw -= hdt*t.proj(x);
-    t.interp(gq, F);
+        for (int p = 0; p < NP; p++) x[p] = cg[p]*(piq0[p] + piq1[p]);
+        fw -= hdt*t.proj(x);
+        t.interp(gq, F);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cg[p]*gq[p];
-    const double wF = t.proj(x);
+        for (int p = 0; p < NP; p++) x[p] = cg[p]*gq[p];
+        wF = t.proj(x);
+    }
     if (a.add_w) fw += a.dt*a.add_w[io];
-    if (act) { a.F[io] = F; a.G[io] = G; a.u[io] = u; a.wF[io] = wF; a.fwA[io] = fw; a.k2[io] = F*tA1; }
+    if (act) {
+        a.F[io] = F; a.G[io] = G; a.u[io] = u;
+        if constexpr (EC) a.wF[io] = wF;
+        a.fwA[io] = fw; a.k2[io] = F*tA1;
+    }
 }
 
 // ---- launch 2: levels ----------------------------------------------------------------------------------------------------------
 struct NewtonLevArgs {
     NewtonGeo g;
     double dt;
+    // theta, rho_h, rt_h: EC only.  add_rho / add_rt (optional, times dt): EC adds them to F_rho / F_rt AFTER the VB product, else they
+    // join dF_z / dG_z BEFORE it (:1145-1149)
     const double *theta, *zv, *rho_i, *rho_j, *rt_i, *rt_j, *rho_h, *rt_h, *exner_j, *add_rho, *add_rt;
-    const double *F, *G, *u, *wF, *fwA;
-    double *F_w, *F_rho, *F_eta, *F_exner, *th_w3, *eta;
+    const double *F, *G, *u, *wF, *fwA;                       // what k_newton_ifc left (wF: EC only)
+    double *F_w, *F_rho, *F_eta, *F_exner, *th_w3, *eta;      // F_eta, th_w3, eta: EC only
+    const double* add_rt_post;                                // not EC only (optional, times dt): joins F_rt after the VB product (:1151-1154)
+    double* F_rt;                                             // not EC only
 };
-template <int N>
+template <int N, bool EC>
 __global__ __launch_bounds__(64) void k_newton_lev(NewtonLevArgs a) {
     using T = ColTask<N>; using R = dpp::Rows<N>;
     constexpr int N2 = T::N2, NP = T::NP;
-    const int lane = threadIdx.x, r = lane%16;
     const int nk = a.g.nk, nm = nk - 1;
-    const long long task0 = (long long)blockIdx.x*4 + lane/16, ntask = (long long)a.g.nEl*nk;
-    const bool live = task0 < ntask;
-    const long long task = live ? task0 : ntask - 1;
-    const int e = (int)(task/nk), k = (int)(task%nk);
-    T t; t.init(a.g, e, r);
-    const bool act = live && r < N2;
+    T t; int k;
+    const bool act = t.start(a.g, nk, k);
+    const int e = t.e;
     const double dt = a.dt, hdt = 0.5*a.dt;
     const size_t vo = ((size_t)e*nk + k)*N2 + t.rr;
     const bool lo = k > 0, hi = k < nk - 1;
@@ -226,51 +254,65 @@ __global__ __launch_bounds__(64) void k_newton_lev(NewtonLevArgs a) {
 #pragma unroll
     for (int p = 0; p < NP; p++) cB[p] = t.q0[p]*tI[p];
     // f_theta_corr = 0.5dt VB(theta) V10 F + 0.5dt C(grad theta) F       (:497-500)
-    double thq[NP];
-    t.interp(thq, a.theta[vo]); t.interp(q, V10F);
+    double ftc = 0.0;
+    if constexpr (EC) {
+        double thq[NP];
+        t.interp(thq, a.theta[vo]); t.interp(q, V10F);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = (cB[p]*(thq[p]/(th[p]*t.det[p])))*q[p];
-    const double ftc = hdt*t.proj(x) + hdt*((lo ? a.wF[im] : 0.0) + (hi ? a.wF[ik] : 0.0));
-    // F_rho = VB (rho_j + dt V10 F - rho_i),  F_rt = VB (rt_j + 0.5dt V10 G - rt_i) + f_theta_corr      (:1815-1826)
-    t.interp(q, (a.rho_j[vo] + dt*V10F) - a.rho_i[vo]);
+        for (int p = 0; p < NP; p++) x[p] = (cB[p]*(thq[p]/(th[p]*t.det[p])))*q[p];
+        ftc = hdt*t.proj(x) + hdt*((lo ? a.wF[im] : 0.0) + (hi ? a.wF[ik] : 0.0));
+    }
+    // EC:   F_rho = VB (rho_j + dt V10 F - rho_i) + dt dFx,   F_rt = VB (rt_j + 0.5dt V10 G - rt_i) + f_theta_corr + dt dGx    (:1815-1826)
+    // else: F_rho = VB (rho_j + dt V10 F - rho_i + dt dFx),   F_rt = VB (rt_j + dt V10 G - rt_i + dt dGx) + dt HS               (:1137-1154)
+    double dF = (a.rho_j[vo] + dt*V10F) - a.rho_i[vo];
+    if constexpr (!EC) { if (a.add_rho) dF += dt*a.add_rho[vo]; }
+    t.interp(q, dF);
 #pragma unroll
     for (int p = 0; p < NP; p++) x[p] = cB[p]*q[p];
     double F_rho = t.proj(x);
-    t.interp(q, (a.rt_j[vo] + hdt*V10G) - a.rt_i[vo]);
+    double dG = (a.rt_j[vo] + (EC ? hdt : dt)*V10G) - a.rt_i[vo];
+    if constexpr (!EC) { if (a.add_rt) dG += dt*a.add_rt[vo]; }
+    t.interp(q, dG);
 #pragma unroll
     for (int p = 0; p < NP; p++) x[p] = cB[p]*q[p];
-    double F_rt = t.proj(x) + ftc;
-    if (a.add_rho) F_rho += dt*a.add_rho[vo];
-    if (a.add_rt) F_rt += dt*a.add_rt[vo];
-    // entropy residual  F_eta = VB (VB(rt_h)^-1 F_rt - VB(rho_h)^-1 F_rho)                            (:1836-1842)
-    double M[N2], rtq[NP];
-    t.interp(rtq, a.rt_h[vo]);
+    double F_rt = t.proj(x);
+    double F_eta = 0.0, th_w3 = 0.0, eta = 0.0;
+    if constexpr (EC) {
+        F_rt += ftc;
+        if (a.add_rho) F_rho += dt*a.add_rho[vo];
+        if (a.add_rt) F_rt += dt*a.add_rt[vo];
+        // entropy residual  F_eta = VB (VB(rt_h)^-1 F_rt - VB(rho_h)^-1 F_rho)                            (:1836-1842)
+        double M[N2], rtq[NP];
+        t.interp(rtq, a.rt_h[vo]);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB[p]*(rtq[p]/(th[p]*t.det[p]));                                 // AssembleConstWithRhoInv :461-474
-    t.inv_block(M, x);
-    double t1 = R::matvec(M, F_rt);
-    t.interp(q, a.rho_h[vo]);
+        for (int p = 0; p < NP; p++) x[p] = cB[p]*(rtq[p]/(th[p]*t.det[p]));                                 // AssembleConstWithRhoInv :461-474
+        t.inv_block(M, x);
+        double t1 = R::matvec(M, F_rt);
+        t.interp(q, a.rho_h[vo]);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB[p]*(q[p]/(th[p]*t.det[p]));
-    t.inv_block(M, x);
-    t1 -= R::matvec(M, F_rho);
-    t.interp(q, t1);
+        for (int p = 0; p < NP; p++) x[p] = cB[p]*(q[p]/(th[p]*t.det[p]));
+        t.inv_block(M, x);
+        t1 -= R::matvec(M, F_rho);
+        t.interp(q, t1);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB[p]*q[p];
-    const double F_eta = t.proj(x);
-    // theta_h in W3 and eta_h = VB^-1 (W^T Q log theta)                                               (:1844-1851)
+        for (int p = 0; p < NP; p++) x[p] = cB[p]*q[p];
+        F_eta = t.proj(x);
+        // theta_h in W3 and eta_h = VB^-1 (W^T Q log theta)                                               (:1844-1851)
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB[p]*rtq[p];
-    const double th_w3 = R::matvec(M, t.proj(x));                         // M = VB(rho_h)^-1
-    t.interp(q, th_w3);
+        for (int p = 0; p < NP; p++) x[p] = cB[p]*rtq[p];
+        th_w3 = R::matvec(M, t.proj(x));                                      // M = VB(rho_h)^-1
+        t.interp(q, th_w3);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = t.Q[p]*(VSCALE*log(q[p]/(th[p]*t.det[p])));                      // AssembleConstWithLogThetaPlusEta :1204-1255
-    const double lg = t.proj(x);
+        for (int p = 0; p < NP; p++) x[p] = t.Q[p]*(VSCALE*log(q[p]/(th[p]*t.det[p])));                      // AssembleConstWithLogThetaPlusEta :1204-1255
+        const double lg = t.proj(x);
 #pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = cB[p];
-    t.inv_block(M, x);
-    const double eta = R::matvec(M, lg);
-    // EOS residual                                                                                     Assemble_EOS_Residual :987-1047
+        for (int p = 0; p < NP; p++) x[p] = cB[p];
+        t.inv_block(M, x);
+        eta = R::matvec(M, lg);
+    } else {
+        if (a.add_rt_post) F_rt += dt*a.add_rt_post[vo];
+    }
+    // EOS residual                                                                                    Assemble_EOS_Residual :987-1047
     double ek[NP];
     t.interp(q, a.rt_j[vo]); t.interp(ek, a.exner_j[vo]);
 #pragma unroll
@@ -280,7 +322,10 @@ __global__ __launch_bounds__(64) void k_newton_lev(NewtonLevArgs a) {
         x[p] = v*(0.5*t.Q[p]*VSCALE);
     }
     const double F_ex = 2.0*t.proj(x);
-    if (act) { a.F_rho[vo] = F_rho; a.F_eta[vo] = F_eta; a.F_exner[vo] = F_ex; a.th_w3[vo] = th_w3; a.eta[vo] = eta; }
+    if (act) {
+        if constexpr (EC) { a.F_rho[vo] = F_rho; a.F_eta[vo] = F_eta; a.F_exner[vo] = F_ex; a.th_w3[vo] = th_w3; a.eta[vo] = eta; }
+        else { a.F_rho[vo] = F_rho; a.F_rt[vo] = F_rt; a.F_exner[vo] = F_ex; }
+    }
 }
 
 // ---- launch 3 (after the Schur solve): eta_j, update, EOS, half states, norm partials --------------------------------------------
@@ -296,14 +341,10 @@ template <int N>
 __global__ __launch_bounds__(64) void k_newton_upd(NewtonUpdArgs a) {
     using T = ColTask<N>; using R = dpp::Rows<N>;
     constexpr int N2 = T::N2, NP = T::NP;
-    const int lane = threadIdx.x, r = lane%16;
     const int nk = a.g.nk, nm = nk - 1;
-    const long long task0 = (long long)blockIdx.x*4 + lane/16, ntask = (long long)a.g.nEl*nk;
-    const bool live = task0 < ntask;
-    const long long task = live ? task0 : ntask - 1;
-    const int e = (int)(task/nk), k = (int)(task%nk);
-    T t; t.init(a.g, e, r);
-    const bool act = live && r < N2;
+    T t; int k;
+    const bool act = t.start(a.g, nk, k);
+    const int e = t.e;
     const size_t vo = ((size_t)e*nk + k)*N2 + t.rr;
     const bool hi = k < nk - 1;
     const size_t ik = ((size_t)e*nm + (hi ? k : 0))*N2 + t.rr;
@@ -358,6 +399,35 @@ __global__ __launch_bounds__(64) void k_newton_upd(NewtonUpdArgs a) {
     }
 }
 
+// ---- launch 3 of the solve_schur_2 loop: the update, the half-time states, the norm partials (:1159-1183) -- elementwise, no EOS ---
+struct Newton2UpdArgs {
+    long long per; int nkn2, nmn2;                            // nEl nk n2; nk n2; (nk-1) n2
+    const double *d_w, *d_rho, *d_rt, *d_exner;
+    const double *velz_i, *rho_i, *rt_i, *exner_i;
+    double *velz_j, *rho_j, *rt_j, *exner_j;                  // in: iterate before the update, out: after
+    double *velz_h, *rho_h, *rt_h, *exner_h;                  // 0.5 x_i + 0.5 x_j
+    double *nrm;                                              // [8][nEl][nk*n2]: squares of d_exner, exner, d_w, w, d_rho, rho, d_rt, rt
+};
+__global__ __launch_bounds__(256) void k_newton2_upd(Newton2UpdArgs a) {
+    const long long vo = (long long)blockIdx.x*256 + threadIdx.x;
+    if (vo >= a.per) return;
+    const long long e = vo/a.nkn2; const int s = (int)(vo%a.nkn2);
+    const double d_ex = a.d_exner[vo], d_rho = a.d_rho[vo], d_rt = a.d_rt[vo];
+    const double ex = a.exner_j[vo] + d_ex, rho = a.rho_j[vo] + d_rho, rt = a.rt_j[vo] + d_rt;
+    a.exner_j[vo] = ex; a.rho_j[vo] = rho; a.rt_j[vo] = rt;
+    a.exner_h[vo] = 0.5*a.exner_i[vo] + 0.5*ex; a.rho_h[vo] = 0.5*a.rho_i[vo] + 0.5*rho; a.rt_h[vo] = 0.5*a.rt_i[vo] + 0.5*rt;
+    a.nrm[0*a.per + vo] = d_ex*d_ex;   a.nrm[1*a.per + vo] = ex*ex;
+    a.nrm[4*a.per + vo] = d_rho*d_rho; a.nrm[5*a.per + vo] = rho*rho;
+    a.nrm[6*a.per + vo] = d_rt*d_rt;   a.nrm[7*a.per + vo] = rt*rt;
+    double dw = 0.0, wn = 0.0;
+    if (s < a.nmn2) {                                         // the nk-1 interfaces of the column; the row's last n2 entries stay zero
+        const long long io = e*a.nmn2 + s;
+        dw = a.d_w[io]; wn = a.velz_j[io] + dw;
+        a.velz_j[io] = wn; a.velz_h[io] = 0.5*a.velz_i[io] + 0.5*wn;
+    }
+    a.nrm[2*a.per + vo] = dw*dw; a.nrm[3*a.per + vo] = wn*wn;
+}
+
 // ---- diagTheta2 / diagTheta_L2 (VertSolve.cpp:289-352) -----------------------------------------------------------------------
 //   interface I in 0..nk:  theta_I = VA2(rho)_I^-1 (VAB2 rt)_I,  VA2 lumped (block diagonal): AssembleLinearWithRho2 :361-409, AssembleLinCon2 :319-359
 //   level k:               theta_k = VB(rho)_k^-1 (VB rt)_k                                  : AssembleConstWithRhoInv, AssembleConst
@@ -373,14 +443,10 @@ template <int N>
 __global__ __launch_bounds__(64) void k_diag_theta(DiagThetaArgs a) {
     using T = ColTask<N>; using R = dpp::Rows<N>;
     constexpr int N2 = T::N2, NP = T::NP;
-    const int lane = threadIdx.x, r = lane%16;
     const int nk = a.g.nk, np1 = nk + 1;
-    const long long task0 = (long long)blockIdx.x*4 + lane/16, ntask = (long long)a.g.nEl*np1;
-    const bool live = task0 < ntask;
-    const long long task = live ? task0 : ntask - 1;
-    const int e = (int)(task/np1), I = (int)(task%np1);
-    T t; t.init(a.g, e, r);
-    const bool act = live && r < N2;
+    T t; int I;
+    const bool act = t.start(a.g, np1, I);
+    const int e = t.e;
     const bool lo = I > 0, hi = I < nk;
     const size_t vm = ((size_t)e*nk + (lo ? I - 1 : 0))*N2 + t.rr, vk = ((size_t)e*nk + (hi ? I : 0))*N2 + t.rr;
     double x[NP], c[NP], q[NP], M[N2];
@@ -605,6 +671,49 @@ __global__ __launch_bounds__(256) void k_max_norms_all(int nEl, const double* __
     }
 }
 
+// the level counts mimsem_column_solve_schur_3 takes (column_hs.inc: nk < 4 is an argument error there too)
+int newton2_check(const mimsem_ctx* c) {
+    if (c->nk < 4) return MIMSEM_ERR_ARG;
+    if (c->es.n < 1 || c->es.n > 4) return MIMSEM_ERR_UNSUPPORTED;
+    return MIMSEM_OK;
+}
+
+// The two launches of a residual, for the entry of either loop (which has checked its arguments and its shape): ec = the solve_schur_eta
+// loop.  The pointers of the other mode are null and its kernels never read them.
+int newton_residual(mimsem_ctx* c, bool ec, double dt, double rayleigh,
+        const double* theta, const double* Pi, const double* velz_i, const double* velz_j, const double* rho_i, const double* rho_j,
+        const double* zv, const double* rt_i, const double* rt_j, const double* rho_h, const double* rt_h, const double* exner_j,
+        const double* add_w, const double* add_rho, const double* add_rt, const double* add_rt_post,
+        double* F_w, double* F_rho, double* F_eta, double* F_rt, double* F_exner, double* th_w3, double* eta, double* k2i) {
+    const long long nEl = c->nEl, nk = c->nk;
+    mimsem::NewtonWS w;
+    int rc = plan_col(c, w, ec);                       // (wF is the entropy-conservation loop's alone)
+    if (rc) return rc;
+    NewtonIfcArgs ia{};
+    fill_newton_geo(c, ia.g);
+    ia.dt = dt; ia.rayleigh = rayleigh; ia.theta = theta; ia.Pi = Pi; ia.velz1 = velz_i; ia.velz2 = velz_j; ia.rho1 = rho_i; ia.rho2 = rho_j;
+    ia.add_w = add_w;
+    ia.F = w.F; ia.G = w.G; ia.u = w.u; ia.wF = w.wF; ia.fwA = w.fwA; ia.k2 = k2i;
+    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) {
+            const dim3 grid(newton_grid(nEl*(nk - 1)));
+            if (ec) hipLaunchKernelGGL((k_newton_ifc<N(), true>), grid, dim3(64), 0, c->stream, ia);
+            else hipLaunchKernelGGL((k_newton_ifc<N(), false>), grid, dim3(64), 0, c->stream, ia);
+        }))) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
+    NewtonLevArgs la{};
+    la.g = ia.g; la.dt = dt; la.theta = ec ? theta : nullptr; la.zv = zv; la.rho_i = rho_i; la.rho_j = rho_j; la.rt_i = rt_i; la.rt_j = rt_j;
+    la.rho_h = rho_h; la.rt_h = rt_h; la.exner_j = exner_j; la.add_rho = add_rho; la.add_rt = add_rt; la.add_rt_post = add_rt_post;
+    la.F = ia.F; la.G = ia.G; la.u = ia.u; la.wF = ia.wF; la.fwA = ia.fwA;
+    la.F_w = F_w; la.F_rho = F_rho; la.F_eta = F_eta; la.F_rt = F_rt; la.F_exner = F_exner; la.th_w3 = th_w3; la.eta = eta;
+    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) {
+            const dim3 grid(newton_grid(nEl*nk));
+            if (ec) hipLaunchKernelGGL((k_newton_lev<N(), true>), grid, dim3(64), 0, c->stream, la);
+            else hipLaunchKernelGGL((k_newton_lev<N(), false>), grid, dim3(64), 0, c->stream, la);
+        }))) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
+    return MIMSEM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -618,25 +727,23 @@ int mimsem_column_newton_residual(mimsem_ctx* c, double dt, double rayleigh,
         !F_w || !F_rho || !F_eta || !F_exner || !th_w3 || !eta || !k2i) return MIMSEM_ERR_ARG;
     if (c->nk < 2) return MIMSEM_ERR_ARG;
     if (!sweep_supported(c)) return MIMSEM_ERR_UNSUPPORTED;
-    const long long nEl = c->nEl, nk = c->nk;
-    mimsem::NewtonWS w;
-    int rc = plan_col(c, w, true);
-    if (rc) return rc;
-    NewtonIfcArgs ia{};
-    fill_newton_geo(c, ia.g);
-    ia.dt = dt; ia.rayleigh = rayleigh; ia.theta = theta; ia.Pi = Pi; ia.velz1 = velz_i; ia.velz2 = velz_j; ia.rho1 = rho_i; ia.rho2 = rho_j;
-    ia.add_w = add_w;
-    ia.F = w.F; ia.G = w.G; ia.u = w.u; ia.wF = w.wF; ia.fwA = w.fwA; ia.k2 = k2i;
-    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton_ifc<N()>), dim3(newton_grid(nEl*(nk - 1))), dim3(64), 0, c->stream, ia); }))) return rc;
-    MIMSEM_HIP_TRY(hipGetLastError());
-    NewtonLevArgs la{};
-    la.g = ia.g; la.dt = dt; la.theta = theta; la.zv = zv; la.rho_i = rho_i; la.rho_j = rho_j; la.rt_i = rt_i; la.rt_j = rt_j;
-    la.rho_h = rho_h; la.rt_h = rt_h; la.exner_j = exner_j; la.add_rho = add_rho; la.add_rt = add_rt;
-    la.F = ia.F; la.G = ia.G; la.u = ia.u; la.wF = ia.wF; la.fwA = ia.fwA;
-    la.F_w = F_w; la.F_rho = F_rho; la.F_eta = F_eta; la.F_exner = F_exner; la.th_w3 = th_w3; la.eta = eta;
-    if ((rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton_lev<N()>), dim3(newton_grid(nEl*nk)), dim3(64), 0, c->stream, la); }))) return rc;
-    MIMSEM_HIP_TRY(hipGetLastError());
-    return MIMSEM_OK;
+    return newton_residual(c, true, dt, rayleigh, theta, Pi, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, rho_h, rt_h, exner_j,
+                           add_w, add_rho, add_rt, nullptr, F_w, F_rho, F_eta, nullptr, F_exner, th_w3, eta, k2i);
+}
+
+// The residual of the OTHER loop, VertSolve::solve_schur_2 (eul/VertSolve.cpp:1059-1246): assemble_residual (:386-430) and the right-hand
+// sides of :1134-1154.  theta_h on the nk+1 interfaces; add_rho_pre / add_rt_pre join dF_z / dG_z before the VB product, add_rt_post after it
+int mimsem_column_newton2_residual(mimsem_ctx* c, double dt, double rayleigh,
+        const double* theta_h, const double* Pi, const double* velz_i, const double* velz_j, const double* rho_i, const double* rho_j,
+        const double* zv, const double* rt_i, const double* rt_j, const double* exner_j,
+        const double* add_w, const double* add_rho_pre, const double* add_rt_pre, const double* add_rt_post,
+        double* F_w, double* F_rho, double* F_rt, double* F_exner, double* k2i) {
+    if (!c || !theta_h || !Pi || !velz_i || !velz_j || !rho_i || !rho_j || !zv || !rt_i || !rt_j || !exner_j ||
+        !F_w || !F_rho || !F_rt || !F_exner || !k2i) return MIMSEM_ERR_ARG;
+    if (int rc = newton2_check(c)) return rc;
+    if (c->nEl == 0) return MIMSEM_OK;
+    return newton_residual(c, false, dt, rayleigh, theta_h, Pi, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, nullptr, nullptr, exner_j,
+                           add_w, add_rho_pre, add_rt_pre, add_rt_post, F_w, F_rho, nullptr, F_rt, F_exner, nullptr, nullptr, k2i);
 }
 
 int mimsem_column_newton_update(mimsem_ctx* c, const double* d_w, const double* d_rho, const double* d_eta, const double* d_exner,
@@ -655,6 +762,26 @@ int mimsem_column_newton_update(mimsem_ctx* c, const double* d_w, const double* 
     a.velz_h = velz_h; a.rho_h = rho_h; a.rt_h = rt_h; a.exner_h = exner_h; a.nrm = norm_squares;
     const unsigned grid = newton_grid((long long)c->nEl*c->nk);
     if (int rc = for_order<1, 2, 3, 4>(c->es.n, [&](auto N) { hipLaunchKernelGGL((k_newton_upd<N()>), dim3(grid), dim3(64), 0, c->stream, a); })) return rc;
+    MIMSEM_HIP_TRY(hipGetLastError());
+    return MIMSEM_OK;
+}
+
+int mimsem_column_newton2_update(mimsem_ctx* c, const double* d_w, const double* d_rho, const double* d_rt, const double* d_exner,
+        const double* velz_i, const double* rho_i, const double* rt_i, const double* exner_i,
+        double* velz_j, double* rho_j, double* rt_j, double* exner_j,
+        double* velz_h, double* rho_h, double* rt_h, double* exner_h, double* norm_squares) {
+    if (!c || !d_w || !d_rho || !d_rt || !d_exner || !velz_i || !rho_i || !rt_i || !exner_i || !velz_j || !rho_j || !rt_j || !exner_j ||
+        !velz_h || !rho_h || !rt_h || !exner_h || !norm_squares) return MIMSEM_ERR_ARG;
+    int rc = newton2_check(c);
+    if (rc) return rc;
+    Newton2UpdArgs a{};
+    a.nkn2 = c->nk*c->es.n2e; a.nmn2 = (c->nk - 1)*c->es.n2e; a.per = (long long)c->nEl*a.nkn2;
+    if (a.per == 0) return MIMSEM_OK;
+    a.d_w = d_w; a.d_rho = d_rho; a.d_rt = d_rt; a.d_exner = d_exner;
+    a.velz_i = velz_i; a.rho_i = rho_i; a.rt_i = rt_i; a.exner_i = exner_i;
+    a.velz_j = velz_j; a.rho_j = rho_j; a.rt_j = rt_j; a.exner_j = exner_j;
+    a.velz_h = velz_h; a.rho_h = rho_h; a.rt_h = rt_h; a.exner_h = exner_h; a.nrm = norm_squares;
+    hipLaunchKernelGGL(k_newton2_upd, dim3((unsigned)((a.per + 255)/256)), dim3(256), 0, c->stream, a);
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }

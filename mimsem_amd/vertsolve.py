@@ -2,6 +2,7 @@
 432-502): compositions of VertOps operators and mat-vecs, here issued for ALL columns at once through the C ABI
 (mimsem_colop_apply) on "vertical" device arrays [nEl][nslots*n2e] (L2Vecs::vz concatenated)."""
 import os
+import types
 
 import torch
 
@@ -66,7 +67,8 @@ class VertSolve:
         return Phi + zv
 
     def assemble_residual_ec(self, theta, Pi, velz1, velz2, rho1, rho2, zv):
-        """eul/VertSolve.cpp:432-502 -> (fw, F, G, f_theta_corr); theta/Pi/rho on levels, velz on interfaces"""
+        """eul/VertSolve.cpp:432-502 -> (fw, F, G, f_theta_corr); theta/Pi/rho on levels, velz on interfaces.  Leaves F * tA1 (the
+        integrand of k2i_z) in self._k2i"""
         nk, nm, dt = self.nk, self.nk - 1, self.dt
         F = self.diagnose_F_z(velz1, velz2, rho1, rho2)
         Phi = self.diagnose_Phi_z(velz1, velz2, zv)
@@ -76,7 +78,7 @@ class VertSolve:
         tA2 = self._mv("LINEAR_INV", self.V01(tB), rows=nm)                 # pressure gradient
         tA1 = self._mv("LINEAR_RT", tA2, f1=theta, flags=FLAG_VERT, rows=nm)
         fw += 0.5 * dt * tA1
-        self.k2i_z += float((F * tA1).sum()) / SCALE                        # kinetic to internal energy power
+        self._k2i = F * tA1                                                 # kinetic to internal energy power, entry by entry (k2i_z: _newton)
         G = self._mv("LINEAR_INV", self._mv("LINEAR_RT", F, f1=theta, flags=FLAG_VERT, rows=nm), rows=nm)
         if self.rayleigh:
             fw += 0.5 * dt * self.rayleigh * (self._mv("RAYLEIGH", velz2, rows=nm) + self._mv("RAYLEIGH", velz1, rows=nm))
@@ -119,107 +121,114 @@ class VertSolve:
         Returns (velz, rho, rt, exner) at the new time level and leaves theta_h / theta_l2_h / exner_h (the time-centred fields
         the horizontal corrector reads) and the per-iteration max-norms in self.*"""
         eng, nk, dt = self.eng, self.nk, self.dt
-        if self.fused and eng.mesh.n <= 4:
-            return self._solve_schur_eta_fused(velz_i, rho_i, rt_i, exner_i, zv, horiz_forcing, udwdx, hs_lat, maxit, tol, verbose)
+        x_i = (velz_i, rho_i, rt_i, exner_i)
         mv = self._mv
-        velz_j, rho_j, rt_j, exner_j = velz_i.clone(), rho_i.clone(), rt_i.clone(), exner_i.clone()
-        theta_i = eng.diag_theta(1, rho_i, rt_i)                          # diagTheta2 :1766
-        theta_h = theta_i.clone()
-        theta_l2_i = eng.diag_theta(0, rho_i, rt_i)                       # diagTheta_L2 :1773
-        theta_l2_h = theta_l2_i.clone()
-        exner_h, velz_h, rho_h, rt_h = exner_i.clone(), velz_i.clone(), rho_i.clone(), rt_i.clone()
-        self.history = []
-        for itt in range(1, maxit + 1):
-            self.k2i_z = 0.0
-            dFx, dGx = horiz_forcing(rho_i, rho_j, theta_l2_h) if horiz_forcing is not None else (None, None)
-            F_w, F_z, G_z, ftc = self.assemble_residual_ec(theta_l2_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv)     # :1806
+
+        def composed(S):
+            """one iteration on the single-operator entry points: every order"""
+            dFx, dGx = horiz_forcing(rho_i, S.rho_j, S.theta_l2_h) if horiz_forcing is not None else (None, None)
+            F_w, F_z, G_z, ftc = self.assemble_residual_ec(S.theta_l2_h, S.exner_h, velz_i, S.velz_j, rho_i, S.rho_j, zv)     # :1806
             if udwdx is not None:
                 F_w = F_w + dt * udwdx
-            F_exner = eng.column_eos(0, rt_j, exner_j)                    # Assemble_EOS_Residual :1810
-            dF_z = rho_j + dt * self.V10(F_z) - rho_i                     # VecAYPX / VecAXPY :1815-1819
-            dG_z = rt_j + 0.5 * dt * self.V10(G_z) - rt_i
+            F_exner = eng.column_eos(0, S.rt_j, S.exner_j)                # Assemble_EOS_Residual :1810
+            dF_z = S.rho_j + dt * self.V10(F_z) - rho_i                   # VecAYPX / VecAXPY :1815-1819
+            dG_z = S.rt_j + 0.5 * dt * self.V10(G_z) - rt_i
             F_rho = mv("CONST", dF_z, rows=nk)
             F_rt = mv("CONST", dG_z, rows=nk) + ftc
             if dFx is not None:
                 F_rho = F_rho + dt * dFx
                 F_rt = F_rt + dt * dGx
             if hs_lat is not None:
-                F_rt = F_rt + dt * eng.temp_forcing_hs(hs_lat, exner_h, theta_h, rho_h)                               # :1831-1834
+                F_rt = F_rt + dt * eng.temp_forcing_hs(hs_lat, S.exner_h, S.theta_h, S.rho_h)                         # :1831-1834
             # entropy residual from the (rho theta) and rho residuals :1836-1842
-            t1 = mv("CONST_RHO_INV", F_rt, f1=rt_h, rows=nk) - mv("CONST_RHO_INV", F_rho, f1=rho_h, rows=nk)
+            t1 = mv("CONST_RHO_INV", F_rt, f1=S.rt_h, rows=nk) - mv("CONST_RHO_INV", F_rho, f1=S.rho_h, rows=nk)
             F_eta = mv("CONST", t1, rows=nk)
             # theta_h in W3 and eta_h :1844-1851
-            th_w3 = mv("CONST_RHO_INV", mv("CONST", rt_h, rows=nk), f1=rho_h, rows=nk)
+            th_w3 = mv("CONST_RHO_INV", mv("CONST", S.rt_h, rows=nk), f1=S.rho_h, rows=nk)
             eta = mv("CONST_INV", eng.column_eos(2, th_w3, None), rows=nk)
-            d_w, d_rho, d_eta, d_exner = eng.solve_schur_eta(dt, th_w3, rho_h, eta, exner_h, F_w, F_rho, F_eta, F_exner)   # :1855
+            d_w, d_rho, d_eta, d_exner = eng.solve_schur_eta(dt, th_w3, S.rho_h, eta, S.exner_h, F_w, F_rho, F_eta, F_exner)   # :1855
             # theta_j (before the update) and eta_j :1858-1865
-            th_w3 = mv("CONST_RHO_INV", mv("CONST", rt_j, rows=nk), f1=rho_j, rows=nk)
+            th_w3 = mv("CONST_RHO_INV", mv("CONST", S.rt_j, rows=nk), f1=S.rho_j, rows=nk)
             eta = mv("CONST_INV", eng.column_eos(2, th_w3, d_eta), rows=nk)
-            velz_j = velz_j + d_w; rho_j = rho_j + d_rho; exner_j = exner_j + d_exner
-            rt_j = mv("CONST_INV", eng.column_eos(3, rho_j, eta), rows=nk)                                            # :1871-1872
-            col = lambda dx, x: float((torch.linalg.vector_norm(dx, dim=1) / torch.linalg.vector_norm(x, dim=1)).max())   # MaxNorm :228
-            nv = torch.tensor([col(d_exner, exner_j), col(d_w, velz_j), col(d_rho, rho_j), col(d_eta, eta)], dtype=torch.float64, device=eng.device)
-            nv = eng.allreduce(nv, op="max").tolist()                    # MPI_Allreduce(MAX) :1915-1918
-            norms = dict(exner=nv[0], w=nv[1], rho=nv[2], eta=nv[3])
-            self.history.append(norms)
-            exner_h = 0.5 * exner_i + 0.5 * exner_j; velz_h = 0.5 * velz_i + 0.5 * velz_j
-            rho_h = 0.5 * rho_i + 0.5 * rho_j; rt_h = 0.5 * rt_i + 0.5 * rt_j
-            theta_h = 0.5 * eng.diag_theta(1, rho_j, rt_j) + 0.5 * theta_i                                            # :1896-1903
-            theta_l2_h = 0.5 * eng.diag_theta(0, rho_j, rt_j) + 0.5 * theta_l2_i                                      # :1905-1912
-            if verbose:
-                print("\t%d:\t|d_exner|/|exner|: %.6e\t|d_w|/|w|: %.6e\t|d_rho|/|rho|: %.6e\t|d_eta|/|eta|: %.6e"
-                      % (itt, norms["exner"], norms["w"], norms["rho"], norms["eta"]))
-            if norms["exner"] < tol and norms["rho"] < tol:               # :1922
-                break
-        self.theta_h, self.theta_l2_h, self.exner_h = theta_h, theta_l2_h, exner_h
-        return velz_j, rho_j, rt_j, exner_j
+            S.velz_j = S.velz_j + d_w; S.rho_j = S.rho_j + d_rho; S.exner_j = S.exner_j + d_exner
+            S.rt_j = mv("CONST_INV", eng.column_eos(3, S.rho_j, eta), rows=nk)                                        # :1871-1872
+            return self._composed_norms_and_halves(S, d_exner, d_w, d_rho, d_eta, eta)
 
-    def _solve_schur_eta_fused(self, velz_i, rho_i, rt_i, exner_i, zv, horiz_forcing, udwdx, hs_lat, maxit, tol, verbose):
-        """the same Newton loop on the fused entry points (orders 1..4): per iteration mimsem_column_newton_residual (2 launches),
-        mimsem_column_solve_schur_eta (3), mimsem_column_newton_update (1), mimsem_column_diag_theta_blend (1) and one reduction of
-        the norm partials; every statement of the composed loop above has its counterpart inside those kernels"""
-        eng, dt = self.eng, self.dt
-        velz_j, rho_j, rt_j, exner_j = velz_i.clone(), rho_i.clone(), rt_i.clone(), exner_i.clone()
-        theta_i, theta_l2_i = eng.diag_theta_blend(rho_i, rt_i)                    # diagTheta2 :1766, diagTheta_L2 :1773
-        theta_h, theta_l2_h = theta_i, theta_l2_i
-        exner_h, velz_h, rho_h, rt_h = exner_i, velz_i, rho_i, rt_i
-        self.history = []
-        self._k2i = None
-        for itt in range(1, maxit + 1):
+        def fused(S):
+            """the same iteration on the fused entry points (orders 1..4): mimsem_column_newton_residual (2 launches),
+            mimsem_column_solve_schur_eta (3), mimsem_column_newton_update (1) and the reduction of the norm partials; every statement of
+            composed() has its counterpart inside those kernels"""
             add_rho = add_rt = None
             if horiz_forcing is not None:
-                add_rho, add_rt = horiz_forcing(rho_i, rho_j, theta_l2_h)
+                add_rho, add_rt = horiz_forcing(rho_i, S.rho_j, S.theta_l2_h)
             if hs_lat is not None:
-                hs = eng.temp_forcing_hs(hs_lat, exner_h, theta_h, rho_h)                                            # :1831-1834
+                hs = eng.temp_forcing_hs(hs_lat, S.exner_h, S.theta_h, S.rho_h)                                      # :1831-1834
                 add_rt = hs if add_rt is None else add_rt + hs
-            F_w, F_rho, F_eta, F_exner, th_w3, eta, k2i = eng.newton_residual(
-                dt, self.rayleigh or 0.0, theta_l2_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, rho_h, rt_h, exner_j,
+            F_w, F_rho, F_eta, F_exner, th_w3, eta, self._k2i = eng.newton_residual(
+                dt, self.rayleigh or 0.0, S.theta_l2_h, S.exner_h, velz_i, S.velz_j, rho_i, S.rho_j, zv, rt_i, S.rt_j, S.rho_h, S.rt_h, S.exner_j,
                 add_w=udwdx, add_rho=add_rho, add_rt=add_rt)
-            self._k2i = k2i
             if getattr(self, "keep_solve_args", False):     # (bench: the linear solve of this iteration again, alone, on the state it was given)
-                self.last_solve_args = (dt, th_w3.clone(), rho_h.clone(), eta.clone(), exner_h.clone(), [F_w.clone(), F_rho.clone(), F_eta.clone(), F_exner.clone()])
-            d_w, d_rho, d_eta, d_exner = eng.solve_schur_eta(dt, th_w3, rho_h, eta, exner_h, F_w, F_rho, F_eta, F_exner)   # :1855
-            velz_h, rho_h, rt_h, exner_h, nrm = eng.newton_update(d_w, d_rho, d_eta, d_exner, velz_i, rho_i, rt_i, exner_i,
-                                                                  velz_j, rho_j, rt_j, exner_j)
+                self.last_solve_args = (dt, th_w3.clone(), S.rho_h.clone(), eta.clone(), S.exner_h.clone(), [F_w.clone(), F_rho.clone(), F_eta.clone(), F_exner.clone()])
+            d_w, d_rho, d_eta, d_exner = eng.solve_schur_eta(dt, th_w3, S.rho_h, eta, S.exner_h, F_w, F_rho, F_eta, F_exner)   # :1855
+            S.velz_h, S.rho_h, S.rt_h, S.exner_h, nrm = eng.newton_update(d_w, d_rho, d_eta, d_exner, velz_i, rho_i, rt_i, exner_i,
+                                                                          S.velz_j, S.rho_j, S.rt_j, S.exner_j)
             if hasattr(eng, "max_norms"):
-                nv = eng.max_norms(nrm)                                             # MaxNorm :228 for exner, w, rho, eta (two launches)
-            else:
-                cs = nrm.sum(dim=2)                                                 # [8, nEl]: column sums of squares
-                nv = torch.sqrt(cs[0::2] / cs[1::2]).amax(dim=1)
-            nv = eng.allreduce(nv, op="max")                                        # MPI_Allreduce(MAX) :1915-1918
+                return eng.max_norms(nrm)                                           # MaxNorm :228 for exner, w, rho, eta (two launches)
+            cs = nrm.sum(dim=2)                                                     # [8, nEl]: column sums of squares
+            return torch.sqrt(cs[0::2] / cs[1::2]).amax(dim=1)
+
+        if self.fused and eng.mesh.n <= 4:
+            def theta(S, blend):                                                    # diagTheta2 :1766, diagTheta_L2 :1773; blended :1896-1912
+                if not blend:
+                    return eng.diag_theta_blend(S.rho_j, S.rt_j)
+                return eng.diag_theta_blend(S.rho_j, S.rt_j, blend2=S.theta_i, blendL=S.theta_l2_i, wa=0.5, wb=0.5)
+            step = fused
+        else:
+            def theta(S, blend):
+                th, thl = eng.diag_theta(1, S.rho_j, S.rt_j), eng.diag_theta(0, S.rho_j, S.rt_j)
+                return (0.5 * th + 0.5 * S.theta_i, 0.5 * thl + 0.5 * S.theta_l2_i) if blend else (th, thl)
+            step = composed
+        return self._newton(x_i, maxit, tol, verbose, "eta", ("exner", "rho"), step, theta)                          # stop rule :1922
+
+    @staticmethod
+    def _composed_norms_and_halves(S, d_exner, d_w, d_rho, d_last, x_last):
+        """what the update kernels of the fused routes leave, composed: the four max-norms of VertSolve::MaxNorm (:228; exner, w, rho and the
+        loop's fourth variable) as a device tensor, and the half-time states of the updated iterate"""
+        col = lambda dx, x: (torch.linalg.vector_norm(dx, dim=1) / torch.linalg.vector_norm(x, dim=1)).max()
+        S.exner_h = 0.5 * S.exner_i + 0.5 * S.exner_j; S.velz_h = 0.5 * S.velz_i + 0.5 * S.velz_j
+        S.rho_h = 0.5 * S.rho_i + 0.5 * S.rho_j; S.rt_h = 0.5 * S.rt_i + 0.5 * S.rt_j
+        return torch.stack([col(d_exner, S.exner_j), col(d_w, S.velz_j), col(d_rho, S.rho_j), col(d_last, x_last)])
+
+    def _newton(self, x_i, maxit, tol, verbose, last, stop, step, theta):
+        """The loop of both solves on either route.  x_i = (velz_i, rho_i, rt_i, exner_i).  The state S holds them, the iterate x_j (clones),
+        the half-time fields x_h and theta_i / theta_l2_i / theta_h / theta_l2_h (the _l2 ones None where the loop has none).  step(S) runs one
+        iteration up to and including the update of x_j and x_h and returns the four max-norms (exner, w, rho, `last`) as a device tensor;
+        theta(S, blend) diagnoses theta of x_j -> (theta2, theta_l2 | None), blended half and half with theta_i where blend.  stop: the norms
+        that must be below tol.  Leaves history, k2i_z (of the last iteration's self._k2i), theta_h, theta_l2_h and exner_h in self.*"""
+        S = types.SimpleNamespace()
+        S.velz_i, S.rho_i, S.rt_i, S.exner_i = x_i
+        S.velz_j, S.rho_j, S.rt_j, S.exner_j = (x.clone() for x in x_i)                                   # :1099-1102
+        S.velz_h, S.rho_h, S.rt_h, S.exner_h = x_i                                                        # :1112-1117 (never written in place)
+        S.theta_i, S.theta_l2_i = theta(S, False)
+        S.theta_h, S.theta_l2_h = S.theta_i, S.theta_l2_i
+        self.history = []
+        self._k2i = None
+        keys = ("exner", "w", "rho", last)
+        for itt in range(1, maxit + 1):
+            nv = self.eng.allreduce(step(S), op="max")                                                    # MPI_Allreduce(MAX) :1915-1918, :1195-1198
             # (the theta diagnosis does not depend on the norms: launched BEFORE the host waits for them, it runs under the read-back)
-            theta_h, theta_l2_h = eng.diag_theta_blend(rho_j, rt_j, blend2=theta_i, blendL=theta_l2_i, wa=0.5, wb=0.5)     # :1896-1912
-            nv = nv.tolist()
-            norms = dict(exner=nv[0], w=nv[1], rho=nv[2], eta=nv[3])
+            S.theta_h, S.theta_l2_h = theta(S, True)
+            norms = dict(zip(keys, nv.tolist()))
             self.history.append(norms)
             if verbose:
-                print("\t%d:\t|d_exner|/|exner|: %.6e\t|d_w|/|w|: %.6e\t|d_rho|/|rho|: %.6e\t|d_eta|/|eta|: %.6e"
-                      % (itt, norms["exner"], norms["w"], norms["rho"], norms["eta"]))
-            if norms["exner"] < tol and norms["rho"] < tol:
+                print("\t%d:\t" % itt + "\t".join("|d_%s|/|%s|: %.6e" % (k, k, norms[k]) for k in keys))
+            if all(norms[k] < tol for k in stop):
                 break
-        self.k2i_z = float(self._k2i.sum()) / SCALE if self._k2i is not None else 0.0
-        self.theta_h, self.theta_l2_h, self.exner_h = theta_h, theta_l2_h, exner_h
-        return velz_j, rho_j, rt_j, exner_j
+        self.k2i_z = float(self._k2i.sum()) / SCALE if self._k2i is not None else 0.0                     # :415-416, last iteration
+        self.theta_h, self.exner_h = S.theta_h, S.exner_h
+        if S.theta_l2_h is not None:
+            self.theta_l2_h = S.theta_l2_h
+        return S.velz_j, S.rho_j, S.rt_j, S.exner_j
 
     # ---- the other vertical implicit solve: the caller of solve_schur_column_3, the vertical half of Euler::Strang -----------------------
     def assemble_residual(self, theta, Pi, velz1, velz2, rho1, rho2, zv):
@@ -257,35 +266,26 @@ class VertSolve:
         theta_h / exner_h (what Euler::Strang reads), the per-iteration max-norms (history: exner, w, rho, rt) and k2i_z in self.*"""
         eng, nk, dt = self.eng, self.nk, self.dt
         fused = self.fused2 if fused is None else (fused and eng.mesh.n <= 4)       # (above order 4 the entries are unsupported: composed)
-        velz_j, rho_j, rt_j, exner_j = velz_i.clone(), rho_i.clone(), rt_i.clone(), exner_i.clone()      # :1099-1102
-        if theta_up:
-            theta_i = eng.diag_theta_wup(0.25 * dt, rho_i, rt_i, velz_i)                                # diagTheta2, box :1312
-        elif fused:
-            theta_i, _ = eng.diag_theta_blend(rho_i, rt_i, wantL=False)                                 # diagTheta2 :1105
-        else:
-            theta_i = eng.diag_theta(1, rho_i, rt_i)
-        theta_h = theta_i
-        exner_h, velz_h, rho_h, rt_h = exner_i, velz_i, rho_i, rt_i                                     # :1112-1117 (never written in place)
-        self.history = []
-        self._k2i = None
+        x_i = (velz_i, rho_i, rt_i, exner_i)
         centred = udwdx is not None and vert_mom_vort is not None
         uuz_j = udwdx                                                                                   # box :1326
-        for itt in range(1, maxit + 1):
-            dFx, dGx = horiz_forcing(rho_i, rho_j, theta_h) if horiz_forcing is not None else (None, None)      # :1124
-            hs = eng.temp_forcing_hs(hs_lat, exner_h, theta_h, rho_h) if hs_lat is not None else None          # :1152
+
+        def step(S):
+            dFx, dGx = horiz_forcing(rho_i, S.rho_j, S.theta_h) if horiz_forcing is not None else (None, None)      # :1124
+            hs = eng.temp_forcing_hs(hs_lat, S.exner_h, S.theta_h, S.rho_h) if hs_lat is not None else None        # :1152
             if fused:
                 F_w, F_rho, F_rt, F_exner, self._k2i = eng.newton2_residual(
-                    dt, self.rayleigh or 0.0, theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv, rt_i, rt_j, exner_j,
+                    dt, self.rayleigh or 0.0, S.theta_h, S.exner_h, velz_i, S.velz_j, rho_i, S.rho_j, zv, rt_i, S.rt_j, S.exner_j,
                     add_w=0.5 * udwdx + 0.5 * uuz_j if centred else udwdx, add_rho_pre=dFx, add_rt_pre=dGx, add_rt_post=hs)
             else:
-                F_w, F_z, G_z = self.assemble_residual(theta_h, exner_h, velz_i, velz_j, rho_i, rho_j, zv)     # :1131
+                F_w, F_z, G_z = self.assemble_residual(S.theta_h, S.exner_h, velz_i, S.velz_j, rho_i, S.rho_j, zv)     # :1131
                 if centred:
                     F_w = F_w + 0.5 * dt * udwdx + 0.5 * dt * uuz_j                                        # box :1343-1346
                 elif udwdx is not None:
                     F_w = F_w + dt * udwdx                                                                 # :1134
-                F_exner = eng.column_eos(0, rt_j, exner_j)                                                 # Assemble_EOS_Residual :1135
-                dF_z = rho_j + dt * self.V10(F_z) - rho_i                                                  # :1137-1142
-                dG_z = rt_j + dt * self.V10(G_z) - rt_i
+                F_exner = eng.column_eos(0, S.rt_j, S.exner_j)                                             # Assemble_EOS_Residual :1135
+                dF_z = S.rho_j + dt * self.V10(F_z) - rho_i                                                # :1137-1142
+                dG_z = S.rt_j + dt * self.V10(G_z) - rt_i
                 if dFx is not None:
                     dF_z = dF_z + dt * dFx                                                                 # :1145-1146
                     dG_z = dG_z + dt * dGx
@@ -293,38 +293,28 @@ class VertSolve:
                 F_rt = self._mv("CONST", dG_z, rows=nk)
                 if hs is not None:
                     F_rt = F_rt + dt * hs                                                                  # :1153
-            d_w, d_rho, d_rt, d_exner = eng.solve_schur_3(dt, theta_h, velz_h, rho_h, rt_h, exner_h, F_w, F_rho, F_rt, F_exner,
+            d_w, d_rho, d_rt, d_exner = eng.solve_schur_3(dt, S.theta_h, S.velz_h, S.rho_h, S.rt_h, S.exner_h, F_w, F_rho, F_rt, F_exner,
                                                           flags=schur3_flags)                              # :1156
             if fused:
-                velz_h, rho_h, rt_h, exner_h, nrm = eng.newton2_update(d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i,
-                                                                       velz_j, rho_j, rt_j, exner_j)     # :1159-1183
-                nv = eng.max_norms(nrm)                                                                    # MaxNorm :228 (two launches)
-            else:
-                velz_j = velz_j + d_w; rho_j = rho_j + d_rho; rt_j = rt_j + d_rt; exner_j = exner_j + d_exner
-                col = lambda dx, x: (torch.linalg.vector_norm(dx, dim=1) / torch.linalg.vector_norm(x, dim=1)).max()
-                nv = torch.stack([col(d_exner, exner_j), col(d_w, velz_j), col(d_rho, rho_j), col(d_rt, rt_j)])
-                exner_h = 0.5 * exner_i + 0.5 * exner_j; velz_h = 0.5 * velz_i + 0.5 * velz_j
-                rho_h = 0.5 * rho_i + 0.5 * rho_j; rt_h = 0.5 * rt_i + 0.5 * rt_j
-            nv = eng.allreduce(nv, op="max")                                                               # MPI_Allreduce(MAX) :1195-1198
-            # (the theta diagnosis does not depend on the norms: launched BEFORE the host waits for them)
-            if theta_up and fused:
-                theta_h = eng.diag_theta_wup(0.25 * dt, rho_j, rt_j, velz_j, blend2=theta_i, wa=0.5, wb=0.5)   # box :1394-1399
-            elif theta_up:
-                theta_h = 0.5 * eng.diag_theta_wup(0.25 * dt, rho_j, rt_j, velz_j) + 0.5 * theta_i
+                S.velz_h, S.rho_h, S.rt_h, S.exner_h, nrm = eng.newton2_update(d_w, d_rho, d_rt, d_exner, velz_i, rho_i, rt_i, exner_i,
+                                                                               S.velz_j, S.rho_j, S.rt_j, S.exner_j)     # :1159-1183
+                return eng.max_norms(nrm)                                                                  # MaxNorm :228 (two launches)
+            S.velz_j = S.velz_j + d_w; S.rho_j = S.rho_j + d_rho; S.rt_j = S.rt_j + d_rt; S.exner_j = S.exner_j + d_exner
+            return self._composed_norms_and_halves(S, d_exner, d_w, d_rho, d_rt, S.rt_j)
+
+        def theta(S, blend):
+            """diagTheta2 of the iterate (:1105, box :1312), blended with theta_i (:1186-1191, box :1394-1399); this loop has no theta_l2"""
+            nonlocal uuz_j
+            bl = dict(blend2=S.theta_i, wa=0.5, wb=0.5) if blend and fused else {}
+            if theta_up:
+                th = eng.diag_theta_wup(0.25 * dt, S.rho_j, S.rt_j, S.velz_j, **bl)
             elif fused:
-                theta_h, _ = eng.diag_theta_blend(rho_j, rt_j, blend2=theta_i, wa=0.5, wb=0.5, wantL=False)   # :1186-1191
+                th, _ = eng.diag_theta_blend(S.rho_j, S.rt_j, wantL=False, **bl)
             else:
-                theta_h = 0.5 * eng.diag_theta(1, rho_j, rt_j) + 0.5 * theta_i
-            if centred:
-                uuz_j = vert_mom_vort(velz_j)                                                              # AssembleVertMomVort, box :1403
-            nv = nv.tolist()
-            norms = dict(exner=nv[0], w=nv[1], rho=nv[2], rt=nv[3])
-            self.history.append(norms)
-            if verbose:
-                print("\t%d:\t|d_exner|/|exner|: %.6e\t|d_w|/|w|: %.6e\t|d_rho|/|rho|: %.6e\t|d_rt|/|rt|: %.6e"
-                      % (itt, norms["exner"], norms["w"], norms["rho"], norms["rt"]))
-            if norms["exner"] < tol and norms["rho"] < tol and norms["rt"] < tol:                          # :1202
-                break
-        self.k2i_z = float(self._k2i.sum()) / SCALE if self._k2i is not None else 0.0                      # :415-416, last iteration
-        self.theta_h, self.exner_h = theta_h, exner_h
-        return velz_j, rho_j, rt_j, exner_j
+                th = eng.diag_theta(1, S.rho_j, S.rt_j)
+            if blend and not fused:
+                th = 0.5 * th + 0.5 * S.theta_i
+            if blend and centred:
+                uuz_j = vert_mom_vort(S.velz_j)                                                            # AssembleVertMomVort, box :1403
+            return th, None
+        return self._newton(x_i, maxit, tol, verbose, "rt", ("exner", "rho", "rt"), step, theta)           # stop rule :1202

@@ -407,20 +407,12 @@ def test_selectable_kernel_variants_agree(setup, monkeypatch, var):
         assert rel_l2(a.cpu().numpy(), b.cpu().numpy()) < TOL, var
 
 
-def test_vertical_newton_loop_matches_oracle(setup):
-    """the caller of the column path: VertSolve::solve_schur_eta (eul/VertSolve.cpp:1721-1973) for all columns at once
-    (mimsem_amd/vertsolve.py) against the column-by-column numpy restatement oracle/vert_oracle.py -- three Newton iterations,
-    no horizontal wind; state and max-norm history.  Also VertSolve::initGZ (:89-175) against its formula."""
-    from mimsem_amd.vertsolve import SCALE as VSCALE, VertSolve
-    from oracle import vert_oracle
-    eng, P = setup
-    if P.nk < 4:
-        pytest.skip("Rayleigh layer needs nk >= 4")
-    r = np.random.default_rng(29)
+def _newton_start(eng, P, vs, seed=29):
+    """the start state of the vertical Newton loop tests: zv from VertSolve::initGZ (device and formula), an EOS-consistent column at rest
+    plus 1e-4 perturbations, the latitudes of the quadrature points and a small u dw/dx term"""
+    from mimsem_amd.vertsolve import SCALE as VSCALE
+    r = np.random.default_rng(seed)
     nEl, nk, n2 = P.nEl, P.nk, P.n2e
-    dt = 0.5
-    t = eng.tensor
-    vs = VertSolve(eng, dt)
     levs = eng.mesh.geoms[0].levs
     zv_d = vs.init_gz(levs)
     W, Q = P.arr("W", (P.mp12, n2)), P.arr("Q", (P.mp12,))
@@ -430,7 +422,6 @@ def test_vertical_newton_loop_matches_oracle(setup):
         for k in range(nk):
             gz = 9.80616 * (levs[k, inds0[e]] + levs[k + 1, inds0[e]])
             zv[e, k * n2:(k + 1) * n2] = W.T @ (VSCALE * 0.5 * Q * gz)
-    assert rel_l2(zv_d.cpu().numpy(), zv) < 1e-13
     # an EOS-consistent column at rest plus small perturbations: Newton steps stay in the physical range of log / exp / pow.  A
     # constant value v is the 2-form with DoF_j = v * (area of sub-cell j) * det * thickness (the edge functions histopolate)
     wd = np.diff(P.arr("qx", (P.mp1,)))
@@ -449,6 +440,26 @@ def test_vertical_newton_loop_matches_oracle(setup):
     pert = lambda: 1.0 + 1e-4 * r.standard_normal((nEl, nk * n2))
     rho, rt, exner = col(rho_v) * pert(), col(rho_v * th_v) * pert(), col(pi_v) * pert()
     velz = np.zeros((nEl, (nk - 1) * n2))
+    lat = np.ascontiguousarray(P.sq[:, 1][P.elinds("q")])              # Geom::s[elInds0_l][1]: latitude of the quadrature points
+    udwdx = 1e-3 * r.standard_normal((nEl, (nk - 1) * n2)) * float(np.abs(zv).mean()) / 9.80616 / 1.5e4
+    return dict(zv_d=zv_d, zv=zv, velz=velz, rho=rho, rt=rt, exner=exner, lat=lat, udwdx=udwdx)
+
+
+def test_vertical_newton_loop_matches_oracle(setup):
+    """the caller of the column path: VertSolve::solve_schur_eta (eul/VertSolve.cpp:1721-1973) for all columns at once
+    (mimsem_amd/vertsolve.py) against the column-by-column numpy restatement oracle/vert_oracle.py -- three Newton iterations,
+    no horizontal wind; state and max-norm history.  Also VertSolve::initGZ (:89-175) against its formula."""
+    from mimsem_amd.vertsolve import VertSolve
+    from oracle import vert_oracle
+    eng, P = setup
+    if P.nk < 4:
+        pytest.skip("Rayleigh layer needs nk >= 4")
+    dt = 0.5
+    t = eng.tensor
+    vs = VertSolve(eng, dt)
+    S = _newton_start(eng, P, vs)
+    zv_d, zv, velz, rho, rt, exner, udwdx = (S[k] for k in ("zv_d", "zv", "velz", "rho", "rt", "exner", "udwdx"))
+    assert rel_l2(zv_d.cpu().numpy(), zv) < 1e-13
     got = vs.solve_schur_eta(t(velz), t(rho), t(rt), t(exner), zv_d, maxit=3, tol=0.0)
     want = vert_oracle.solve_schur_eta(P, dt, velz, rho, rt, exner, zv, 3)
     for a, b, name in zip(got, want[:4], ("velz", "rho", "rt", "exner")):
@@ -458,12 +469,49 @@ def test_vertical_newton_loop_matches_oracle(setup):
         for k in ("exner", "w", "rho", "eta"):
             assert abs(hd[k] - ho[k]) <= 1e-5 * ho[k] + 1e-15, (k, hd[k], ho[k])
     # with the Held-Suarez temperature forcing and the u dw/dx term switched on
-    lat = P.sq[:, 1][P.elinds("q")]                                    # Geom::s[elInds0_l][1]: latitude of the quadrature points
-    udwdx = 1e-3 * r.standard_normal((nEl, (nk - 1) * n2)) * float(np.abs(zv).mean()) / 9.80616 / 1.5e4
-    got = vs.solve_schur_eta(t(velz), t(rho), t(rt), t(exner), zv_d, maxit=2, tol=0.0, hs_lat=t(np.ascontiguousarray(lat)), udwdx=t(udwdx))
+    got = vs.solve_schur_eta(t(velz), t(rho), t(rt), t(exner), zv_d, maxit=2, tol=0.0, hs_lat=t(S["lat"]), udwdx=t(udwdx))
     want = vert_oracle.solve_schur_eta(P, dt, velz, rho, rt, exner, zv, 2, hs_forcing=True, udwdx=udwdx)
     for a, b, name in zip(got, want[:4], ("velz", "rho", "rt", "exner")):
         assert np.all(np.isfinite(b)) and rel_l2(a.cpu().numpy(), b) < TOL, name
+
+
+@pytest.mark.parametrize("pn,ne,nk", [(3, 2, 5), (2, 2, 4), (4, 1, 6), (5, 1, 4)], ids=lambda v: str(v))
+def test_composed_eta_loop_matches_the_restatement_and_the_fused_loop(oracle, pn, ne, nk):
+    """the COMPOSED solve_schur_eta loop (single-operator calls: the only route above order 4, and what MIMSEM_NEWTON_FUSED=0 selects)
+    against oracle/vert_oracle.py and, at the orders that have one, against the fused loop: three iterations without forcing, two with
+    the Held-Suarez forcing and u dw/dx; state, history and the published theta_h / theta_l2_h / exner_h.  An odd level count, the
+    smallest the Rayleigh layer takes, the half-row layout of order 4, and an order with no fused route"""
+    from mimsem_amd.device import DeviceMesh, Engine
+    from mimsem_amd.vertsolve import VertSolve
+    from oracle import vert_oracle
+    cs, topo, geom, P, rng = make_patch(oracle, pn, ne, 6, 1, nk=nk, seed=500 + 7 * nk + pn)
+    eng = Engine(DeviceMesh([topo], [geom], nk=nk, numbering="local"))
+    dt = 0.5
+    t = eng.tensor
+    vs = VertSolve(eng, dt)
+    vs.fused = False
+    S = _newton_start(eng, P, vs)
+    zv_d, zv, velz, rho, rt, exner, udwdx = (S[k] for k in ("zv_d", "zv", "velz", "rho", "rt", "exner", "udwdx"))
+    names = ("velz", "rho", "rt", "exner")
+    halves = ("theta_h", "theta_l2_h", "exner_h")
+    fz = VertSolve(eng, dt)
+    fz.fused = True
+    for nits, kw, okw in ((3, {}, {}), (2, dict(hs_lat=t(S["lat"]), udwdx=t(udwdx)), dict(hs_forcing=True, udwdx=udwdx))):
+        got = vs.solve_schur_eta(t(velz), t(rho), t(rt), t(exner), zv_d, maxit=nits, tol=0.0, **kw)
+        want = vert_oracle.solve_schur_eta(P, dt, velz, rho, rt, exner, zv, nits, **okw)
+        assert len(vs.history) == nits
+        for a, b, name in zip(got, want[:4], names):
+            assert np.all(np.isfinite(b)), name
+            assert rel_l2(a.cpu().numpy(), b) < TOL, (name, nits)
+        for hd, ho in zip(vs.history, want[4]):
+            for k in ("exner", "w", "rho", "eta"):
+                assert abs(hd[k] - ho[k]) <= 1e-5 * ho[k] + 1e-15, (k, hd[k], ho[k])
+        if pn <= 4:
+            fus = fz.solve_schur_eta(t(velz), t(rho), t(rt), t(exner), zv_d, maxit=nits, tol=0.0, **kw)
+            for a, b, name in zip(got, fus, names):
+                assert rel_l2(a.cpu().numpy(), b.cpu().numpy()) < TOL, (name, nits)
+            for name in halves:
+                assert rel_l2(getattr(vs, name).cpu().numpy(), getattr(fz, name).cpu().numpy()) < TOL, (name, nits)
 
 
 def test_max_norms_against_the_composed_reduction(setup):
