@@ -642,7 +642,10 @@ int mimsem_column_newton_update(mimsem_ctx* ctx, const double* d_w, const double
  * workspace of 4 nEl doubles (the per-column ratios stay there).  Two launches; a NaN ratio wins the maximum. */
 int mimsem_column_max_norms(mimsem_ctx* ctx, const double* norm_squares, double* ratio_ws, double* out4);
 /* diagTheta2 and / or diagTheta_L2 (:289-352) in one launch, optionally blended: out = wa * theta(rho, rt) + wb * blend
- * (the half-time averages theta_h = 0.5 theta_j + 0.5 theta_i of :1896-1912).  theta2 / thetaL: either may be null. */
+ * (the half-time averages theta_h = 0.5 theta_j + 0.5 theta_i of :1896-1912).  theta2 / thetaL: either may be null.
+ * Orders 1..4, like the fused Newton entries it serves (MIMSEM_ERR_UNSUPPORTED above: nothing launched, theta2 / thetaL untouched;
+ * mimsem_column_diag_theta covers every order).  There it is the one kernel mimsem_column_diag_theta launches too: with blend2 / blendL
+ * null the outputs of the two entries are the same bits. */
 int mimsem_column_diag_theta_blend(mimsem_ctx* ctx, const double* rho, const double* rt, double* theta2, const double* blend2,
                                    double* thetaL, const double* blendL, double wa, double wb);
 /* diagTheta2 of the box twin (box/VertSolve.cpp:499-531): theta2 = wa * VA2_up^-1 VAB2_up rt + wb * blend2 on the nk + 1 interfaces, the

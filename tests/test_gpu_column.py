@@ -69,7 +69,7 @@ def test_colop_blocks_and_apply(setup, colop, k1, k2, flag):
     x = r.standard_normal((P.nEl, cols)); xt = r.standard_normal((P.nEl, rows))
     y = eng.colop_apply(colop, eng.tensor(x), f1=t(f1), f2=t(f2), flags=flag, nout_slots=rows // P.n2e).cpu().numpy()
     yt = eng.colop_apply(colop, eng.tensor(xt), f1=t(f1), f2=t(f2), flags=flag, transpose=True, nout_slots=cols // P.n2e).cpu().numpy()
-    for e in (0, P.nEl - 1):
+    for e in range(P.nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         want = P.colop_dense(colop, ex, ey, flag=flag, f1=None if f1 is None else f1[e], f2=None if f2 is None else f2[e])
         got = _dense_from_blocks(P, colop, blk[e])
@@ -94,7 +94,7 @@ def test_eos_vectors(setup):
     t = eng.tensor
     got = [eng.column_eos(0, t(F["rt"]), t(F["pi"])), eng.column_eos(1, t(F["rt"]), None, 1004.5 * (287.0 / 1e5) ** (287.0 / 717.5), 287.0 / 717.5),
            eng.column_eos(2, t(F["thetaL"]), None), eng.column_eos(2, t(F["thetaL"]), t(F["eta"])), eng.column_eos(3, t(F["rho"]), t(F["eta"] * 1e-3))]
-    for e in (0, P.nEl - 1):
+    for e in range(P.nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         want = [P.eos_residual(ex, ey, F["rt"][e], F["pi"][e]),
                 P.eos_rhs(ex, ey, F["rt"][e], 1004.5 * (287.0 / 1e5) ** (287.0 / 717.5), 287.0 / 717.5),
@@ -109,7 +109,7 @@ def test_diag_theta(setup):
     F = _col_fields(P)
     th0 = eng.diag_theta(0, eng.tensor(F["rho"]), eng.tensor(F["rt"])).cpu().numpy()
     th1 = eng.diag_theta(1, eng.tensor(F["rho"]), eng.tensor(F["rt"])).cpu().numpy()
-    for e in (0, P.nEl - 1):
+    for e in range(P.nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         assert rel_l2(th0[e], P.diag_theta_L2(ex, ey, F["rho"][e], F["rt"][e])) < TOL
         assert rel_l2(th1[e], P.diag_theta2(ex, ey, F["rho"][e], F["rt"][e])) < TOL
@@ -129,7 +129,7 @@ def test_schur_column_solve(setup):
     dFu, dFrho, dFeta, dFpi = t(Fu), t(Frho), t(Feta), t(Fpi)
     d_u, d_rho, d_eta, d_pi = eng.solve_schur_eta(dt, t(F["thetaL"]), t(F["rho"]), t(F["eta"]), t(F["pi"]), dFu, dFrho, dFeta, dFpi)
     n2, nk = P.n2e, P.nk
-    for e in (0, nEl - 1):
+    for e in range(nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         ref = P.solve_schur_column_eta(ex, ey, dt, F["thetaL"][e], F["rho"][e], F["eta"][e], F["pi"][e], Fu[e], Frho[e], Feta[e], Fpi[e])
         Ld = dense_from_band(L[e], nk, n2, lo=1)
@@ -231,7 +231,7 @@ def test_residual_compositions(setup):
             if k > 0: V10[k*n2+i, (k-1)*n2+i] = -1.0
             if k < nk - 1: V10[k*n2+i, k*n2+i] = +1.0
     V01 = -V10.T
-    for e in (0, nEl - 1):
+    for e in range(nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         D = lambda op, **kw: P.colop_dense(op, ex, ey, **kw)
         VAinv = D("LINEAR_INV")
@@ -283,7 +283,7 @@ def test_hs_colops(setup, colop, k1, k2, param, up):
     rows, cols = P.colop_dims(colop)
     x = r.standard_normal((P.nEl, cols))
     y = eng.colop_apply_ex(colop, eng.tensor(x), rows // P.n2e, param=param, f1=t(f1), f2=t(f2), uh=t(uh)).cpu().numpy()
-    for e in (0, P.nEl - 1):
+    for e in range(P.nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         want = P.colop_dense_ex(colop, ex, ey, param=param, f1=None if f1 is None else f1[e], f2=None if f2 is None else f2[e], uh=uh)
         got = _dense_from_blocks(P, colop, blk[e])
@@ -307,7 +307,7 @@ def test_diag_theta_up_and_temp_forcing(setup):
     sig = np.linspace(1.0, 0.3, P.nk)[None, :, None] * r.uniform(0.97, 1.0, (P.nEl, 1, P.n2e))
     exner = (1004.5 * sig ** (287.0 / 1004.5) * area * P.thick.mean(axis=1)[None, :, None]).reshape(P.nEl, -1)
     got = eng.temp_forcing_hs(t(lat), t(exner), t(F["theta"]), t(F["rho"])).cpu().numpy()
-    for e in (0, P.nEl - 1):
+    for e in range(P.nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         assert rel_l2(th[e], P.diag_theta_up(ex, ey, dt, F["rho"][e], F["rt"][e], uh)) < TOL
         assert rel_l2(got[e], P.temp_forcing_hs(ex, ey, exner[e], F["theta"][e], F["rho"][e])) < TOL
@@ -329,7 +329,7 @@ def test_schur_column_3_pentadiagonal(setup, flags):
     d_u, d_rho, d_rt, d_pi, L = eng.solve_schur_3(dt, t(F["theta"]), t(F["velz"]), t(F["rho"]), t(F["rt"]), t(F["pi"]),
                                                   dFu, dFrho, dFrt, dFpi, want_L=True, flags=flags)
     L = L.cpu().numpy()
-    for e in (0, nEl - 1):
+    for e in range(nEl):
         ex, ey = e % P.nElsX, e // P.nElsX
         ref = P.solve_schur_column_3(ex, ey, dt, F["theta"][e], F["velz"][e], F["rho"][e], F["rt"][e], F["pi"][e],
                                      Fu[e], Frho[e], Frt[e], Fpi[e], flags=flags)
