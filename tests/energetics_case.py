@@ -91,13 +91,18 @@ def make_box_case(oracle, pn=4, ne=3, nk=2, seed=43):
     g.set_levels(levs)
     P = oracle.Patch(pn, pn, bx.nel, nk)
     P.set_metric(g.det, g.J); P.set_levels(levs)
-    area = P.det.mean() * 4.0 / (pn * pn); dz = P.thick.mean(); ln = np.sqrt(area)
-    N1, N2 = bx.nDofs1G, bx.nDofs2G
-    F = dict(u1=r.standard_normal((nk, N1)) * 20.0 * ln * dz, h1=r.uniform(0.8, 1.2, (nk, N2)) * area * dz,
-             th=r.uniform(290, 310, (nk, N2)) * area * dz, Pi=r.uniform(900, 1000, (nk, N2)) * area * dz,
-             velz1=r.standard_normal((nk - 1, N2)) * area)
+    F = state_fields(P, r, pn, nk, bx.nDofs1G, bx.nDofs2G)
     c = dict(topos=[t], geoms=[g], levs=levs, gd=None, patches=[(t, g, P)], F=F)
     return _finish(c, nk, F)
+
+
+def state_fields(P, r, pn, nk, N1, N2):
+    """a physically scaled 3-D state on the one patch P, every level its own draw: u1 [nk, N1], h1 (density), th (density-weighted potential
+    temperature), Pi (Exner) [nk, N2] and velz1 [nk-1, N2] as DoFs (fluxes and cell integrals: the area and thickness factors)"""
+    area = P.det.mean() * 4.0 / (pn * pn); dz = P.thick.mean(); ln = np.sqrt(area)
+    return dict(u1=r.standard_normal((nk, N1)) * 20.0 * ln * dz, h1=r.uniform(0.8, 1.2, (nk, N2)) * area * dz,
+                th=r.uniform(290, 310, (nk, N2)) * area * dz, Pi=r.uniform(900, 1000, (nk, N2)) * area * dz,
+                velz1=r.standard_normal((nk - 1, N2)) * area)
 
 
 def theta_L2(c, rho=None, rt=None):

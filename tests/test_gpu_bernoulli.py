@@ -10,6 +10,7 @@ import torch
 
 from tests import energetics_case as ec
 from tests import vort_diag_case as vc
+from tests.euler_fused_cases import phi_from_element_matrices            # (moved there: shared with tests/test_gpu_euler_fused_orders.py)
 from tests.helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -40,28 +41,6 @@ def _fields(c, nk, seed):
     c["np"] = (u1, u2, z1, z2)
     c["t"] = tuple(c["eng"].tensor(a) for a in c["np"])
     return c
-
-
-def phi_from_element_matrices(c, nk):
-    """diagnose_Phi per level from the oracle's WtQUmat / Whmat element matrices of one patch (a case without dense global matrices)"""
-    (t, g, P), = c["patches"]
-    u1, u2, z1, z2 = c["np"]
-    gx, gy, g2 = t.all_inds1x_g(), t.all_inds1y_g(), t.all_inds2_g()
-    out = np.zeros((nk, z1.shape[1]))
-    for k in range(nk):
-        zb = []
-        for z in (z1, z2):
-            a = np.zeros(z.shape[1])
-            if k > 0: a += 0.5 * z[k - 1]
-            if k < nk - 1: a += 0.5 * z[k]
-            zb.append(a)
-        K = [P.op_elmats("WTQUMAT", k, SCALE, 0, ec._patch_local_1form(t, P, u[k])).reshape(P.nEl, 2, P.n2e, P.n1e) for u in (u1, u2)]
-        W = [P.op_elmats("WHMAT", k, SCALE, 0, np.ascontiguousarray(a)).reshape(P.nEl, P.n2e, P.n2e) for a in zb]
-        for e in range(P.nEl):
-            ap = lambda Ke, u: Ke[0] @ u[k, gx[e]] + Ke[1] @ u[k, gy[e]]
-            out[k, g2[e]] = (ap(K[0][e], u1) + ap(K[0][e], u2) + ap(K[1][e], u2)) / 3.0 \
-                + (W[0][e] @ zb[0][g2[e]] + W[0][e] @ zb[1][g2[e]] + W[1][e] @ zb[1][g2[e]]) / 6.0
-    return out
 
 
 def _fused(c, *a):

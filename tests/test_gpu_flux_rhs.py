@@ -11,6 +11,7 @@ import torch
 from tests import energetics_case as ec
 from tests import strang2_case as s2c
 from tests import vort_diag_case as vc
+from tests.euler_fused_cases import flux_rhs_scattered                   # (moved there: shared with tests/test_gpu_euler_fused_orders.py)
 from tests.helpers import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -71,17 +72,7 @@ def box(oracle):
     """p = 4, ne = 3, nk = 2 periodic box: 25 points on 32 lanes, one patch whose edges wrap around"""
     c = ec.make_box_case(oracle)
     c = _fields(_engine(c, c["nk"]), 4)
-    (t, g, P), = c["patches"]
-    u1, u2, h1, h2 = c["np"]
-    gmap = np.zeros(P.n1, dtype=np.int64)
-    gmap[t.all_inds1x_l().ravel()] = t.all_inds1x_g().ravel()
-    gmap[t.all_inds1y_l().ravel()] = t.all_inds1y_g().ravel()
-    ref = np.zeros_like(u1)
-    for k in range(c["nk"]):
-        loc = s2c.flux_rhs_pointwise(P, k, ec._patch_local_1form(t, P, u1[k]), ec._patch_local_1form(t, P, u2[k]),
-                                     np.ascontiguousarray(h1[k]), np.ascontiguousarray(h2[k]))
-        np.add.at(ref[k], gmap, loc)
-    c["ref"] = ref
+    c["ref"] = flux_rhs_scattered(c, c["nk"], c["np"])
     return c
 
 
