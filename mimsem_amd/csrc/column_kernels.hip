@@ -17,6 +17,7 @@
 #include <type_traits>
 #include "ctx.hpp"
 #include "col_workspace.hpp"
+#include "small_block_inverse.hpp"
 
 #define RD 287.0
 #define CV 717.5
@@ -27,6 +28,7 @@
 namespace {
 
 using mimsem::BA; using mimsem::Band; using mimsem::ColArena; using mimsem::ColDims;
+using mimsem::wsync; using mimsem::wsync_lds; using mimsem::reg_inverse; using mimsem::rows_gauss_jordan;
 
 // the one dispatch on the order: f(std::integral_constant<int, N>) for the listed N that equals n, so that a site instantiates exactly the
 // templates it lists (block sizes are listed as n2e = n*n).  Returns f's status (MIMSEM_OK where f returns nothing), or
@@ -305,60 +307,19 @@ int coef_block_pass(mimsem_ctx* c, int colop, unsigned flags, const double* f1, 
 }
 
 // ---- batched Gauss-Jordan with full pivoting: one thread per block, private copy in LDS ------------
-// (thread-minor layout => conflict-free; pivot search / swaps / elimination exactly as LinAlg.cpp:186-269)
+// (thread-minor layout => conflict-free; sweep A of small_block_inverse.hpp)
 __global__ __launch_bounds__(64) void k_block_inverse(long long nb, int n, int T, double* blocks, int* errcount) {
     extern __shared__ double lds[];
     const int t = threadIdx.x;
     const long long b = (long long)blockIdx.x*T + t;
-    double* A = lds;                                   // A[(i*n+j)*T + t]
-    int* ipiv = (int*)(lds + (size_t)n*n*T);           // [n][T]
-    int* indxr = ipiv + n*T;
-    int* indxc = indxr + n*T;
+    const mimsem::Strided<double> A{lds, T, t};        // A[(i*n+j)*T + t]
+    const mimsem::Strided<int> ipiv{(int*)(lds + (size_t)n*n*T), T, t};      // [n][T]
+    const mimsem::Strided<int> indxr{ipiv.p + n*T, T, t}, indxc{indxr.p + n*T, T, t};
     if (t >= T || b >= nb) return;
     double* src = blocks + b*n*n;
-    for (int k = 0; k < n*n; k++) A[k*T + t] = src[k];
-    for (int j = 0; j < n; j++) ipiv[j*T + t] = 0;
-    int err = 0, irow = 0, icol = 0;
-    for (int i = 0; i < n; i++) {
-        double big = 0.0;
-        for (int j = 0; j < n; j++) {
-            if (ipiv[j*T + t] == 1) continue;
-            for (int k = 0; k < n; k++) {
-                if (ipiv[k*T + t] == 0) {
-                    const double v = fabs(A[(j*n + k)*T + t]);
-                    if (v >= big) { big = v; irow = j; icol = k; }
-                } else if (ipiv[k*T + t] > 1) err = 1;
-            }
-        }
-        ++ipiv[icol*T + t];
-        if (irow != icol)
-            for (int l = 0; l < n; l++) {
-                const double tmp = A[(irow*n + l)*T + t];
-                A[(irow*n + l)*T + t] = A[(icol*n + l)*T + t];
-                A[(icol*n + l)*T + t] = tmp;
-            }
-        indxr[i*T + t] = irow; indxc[i*T + t] = icol;
-        if (fabs(A[(icol*n + icol)*T + t]) < 1.0e-12) err = 2;
-        const double pivinv = 1.0/A[(icol*n + icol)*T + t];
-        A[(icol*n + icol)*T + t] = 1.0;
-        for (int l = 0; l < n; l++) A[(icol*n + l)*T + t] *= pivinv;
-        for (int ll = 0; ll < n; ll++) {
-            if (ll == icol) continue;
-            const double dum = A[(ll*n + icol)*T + t];
-            A[(ll*n + icol)*T + t] = 0.0;
-            for (int l = 0; l < n; l++) A[(ll*n + l)*T + t] -= A[(icol*n + l)*T + t]*dum;
-        }
-    }
-    for (int l = n - 1; l >= 0; l--) {
-        const int ir = indxr[l*T + t], ic = indxc[l*T + t];
-        if (ir == ic) continue;
-        for (int k = 0; k < n; k++) {
-            const double tmp = A[(k*n + ir)*T + t];
-            A[(k*n + ir)*T + t] = A[(k*n + ic)*T + t];
-            A[(k*n + ic)*T + t] = tmp;
-        }
-    }
-    for (int k = 0; k < n*n; k++) src[k] = A[k*T + t];
+    for (int k = 0; k < n*n; k++) A[k] = src[k];
+    const int err = mimsem::serial_pivot_inverse(n, A, ipiv, indxr, indxc);
+    for (int k = 0; k < n*n; k++) src[k] = A[k];
     if (err && errcount) atomicAdd(errcount, 1);
 }
 
@@ -366,10 +327,7 @@ __global__ __launch_bounds__(64) void k_block_inverse(long long nb, int n, int T
 // Round 5: ONE WAVEFRONT per block for 16 < n <= 64 (the 24 x 24 / 40 x 40 element blocks of M1 and the 33 x 33 / 56 x 56 coupled [u|h]
 // blocks of the shallow-water preconditioner at p = 3 / 4; the 25 .. 49-wide 2-form blocks of p = 5 .. 7).  The thread-per-block kernel
 // above walks n^3 entries through LDS with ONE lane working per block: 2.9 ms for the 3 456 blocks of SWEqn's PCSetUp (round-4 verdict).
-// Here lane = row of the elimination (and column of the row swap / scaling), the block in LDS with an ODD row stride (conflict-free row
-// and column walks), the same algorithm in the same order -- full pivoting with LinAlg.cpp:186-269's tie-breaking (the LAST entry of the
-// row-major scan that attains the maximum), normalise, eliminate, un-permute the columns -- so the same pivots and the same operations
-// per entry as the kernel above: identical bits.
+// Here lane = row of the elimination, the block in LDS with an odd row stride: sweep B of small_block_inverse.hpp.
 __global__ __launch_bounds__(64) void k_block_inverse_wave(long long nb, int n, double* blocks, int* errcount) {
     extern __shared__ double lds[];
     const int lane = threadIdx.x, ns = n | 1;
@@ -382,46 +340,7 @@ __global__ __launch_bounds__(64) void k_block_inverse_wave(long long nb, int n, 
     for (int idx = lane; idx < n*n; idx += 64) A[(idx/n)*ns + idx%n] = src[idx];
     if (lane < n) ipiv[lane] = 0;
     __syncthreads();
-    int err = 0;
-    for (int i = 0; i < n; i++) {
-        // pivot search: my row, then the wavefront.  Sequential semantics of the reference: the last (j, k) in row-major order with |a| == max
-        double big = -1.0; int kk = 0;
-        if (lane < n && ipiv[lane] != 1)
-            for (int k = 0; k < n; k++) {
-                const int pk = ipiv[k];
-                if (pk == 0) { const double v = fabs(A[lane*ns + k]); if (v >= big) { big = v; kk = k; } }
-                else if (pk > 1) err = 1;
-            }
-        double vmax = big;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, off));
-        int jsel = (big == vmax && big >= 0.0) ? lane : -1;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) jsel = max(jsel, __shfl_xor(jsel, off));
-        if (jsel < 0) { err = 2; jsel = 0; }           // (nothing left to pivot on / NaN: reported like a vanishing pivot)
-        const int irow = jsel, icol = __shfl(kk, jsel);
-        __syncthreads();
-        if (lane == 0) { ++ipiv[icol]; indxr[i] = irow; indxc[i] = icol; }
-        if (irow != icol && lane < n) { const double t0 = A[irow*ns + lane]; A[irow*ns + lane] = A[icol*ns + lane]; A[icol*ns + lane] = t0; }
-        __syncthreads();
-        const double piv = A[icol*ns + icol];
-        if (fabs(piv) < 1.0e-12) err = 2;
-        const double pivinv = 1.0/piv;
-        __syncthreads();
-        if (lane < n) A[icol*ns + lane] = (lane == icol ? 1.0 : A[icol*ns + lane])*pivinv;
-        __syncthreads();
-        if (lane < n && lane != icol) {
-            const double dum = A[lane*ns + icol];
-            A[lane*ns + icol] = 0.0;
-            for (int l = 0; l < n; l++) A[lane*ns + l] -= A[icol*ns + l]*dum;
-        }
-        __syncthreads();
-    }
-    for (int l = n - 1; l >= 0; l--) {
-        const int ir = indxr[l], ic = indxc[l];
-        if (ir != ic && lane < n) { const double t0 = A[lane*ns + ir]; A[lane*ns + ir] = A[lane*ns + ic]; A[lane*ns + ic] = t0; }
-        __syncthreads();
-    }
+    const int err = mimsem::wave_pivot_inverse(A, n, ns, ipiv, indxr, indxc, lane);
     for (int idx = lane; idx < n*n; idx += 64) src[idx] = A[(idx/n)*ns + idx%n];
     if (errcount) { const unsigned long long any = __ballot(err != 0); if (lane == 0 && any) atomicAdd(errcount, 1); }
 }
@@ -520,64 +439,15 @@ __global__ __launch_bounds__(64) void k_block_inverse_reg(long long nb, double* 
     double a[N*N];
 #pragma unroll
     for (int k = 0; k < N*N; k++) a[k] = src[k];
-    double dmax = 0.0;
-#pragma unroll
-    for (int k = 0; k < N; k++) dmax = fmax(dmax, fabs(a[k*N + k]));
-    bool ok = true;
-#pragma unroll
-    for (int p = 0; p < N; p++) {
-        const double piv = a[p*N + p];
-        if (!(fabs(piv) >= 1.0e-8*dmax) || !(fabs(piv) >= 1.0e-12)) ok = false;
-        const double pinv = 1.0/piv;
-        a[p*N + p] = 1.0;
-#pragma unroll
-        for (int c = 0; c < N; c++) a[p*N + c] *= pinv;
-#pragma unroll
-        for (int r = 0; r < N; r++) {
-            if (r == p) continue;
-            const double d = a[r*N + p];
-            a[r*N + p] = 0.0;
-#pragma unroll
-            for (int c = 0; c < N; c++) a[r*N + c] -= a[p*N + c]*d;
-        }
-    }
-    if (ok) {
+    if (reg_inverse<N>(a)) {
 #pragma unroll
         for (int k = 0; k < N*N; k++) src[k] = a[k];
         return;
     }
-    // ---- slow path: exact restatement with full pivoting on a private copy ----
+    // ---- slow path: the reference's full pivoting on a private copy (sweep A) ----
     double A[N*N]; int ipiv[N], indxr[N], indxc[N];
     for (int k = 0; k < N*N; k++) A[k] = src[k];
-    for (int j = 0; j < N; j++) ipiv[j] = 0;
-    int err = 0, irow = 0, icol = 0;
-    for (int i = 0; i < N; i++) {
-        double big = 0.0;
-        for (int j = 0; j < N; j++) {
-            if (ipiv[j] == 1) continue;
-            for (int k = 0; k < N; k++) {
-                if (ipiv[k] == 0) { const double v = fabs(A[j*N + k]); if (v >= big) { big = v; irow = j; icol = k; } }
-                else if (ipiv[k] > 1) err = 1;
-            }
-        }
-        ++ipiv[icol];
-        if (irow != icol) for (int l = 0; l < N; l++) { const double t = A[irow*N + l]; A[irow*N + l] = A[icol*N + l]; A[icol*N + l] = t; }
-        indxr[i] = irow; indxc[i] = icol;
-        if (fabs(A[icol*N + icol]) < 1.0e-12) err = 2;
-        const double pivinv = 1.0/A[icol*N + icol];
-        A[icol*N + icol] = 1.0;
-        for (int l = 0; l < N; l++) A[icol*N + l] *= pivinv;
-        for (int ll = 0; ll < N; ll++) {
-            if (ll == icol) continue;
-            const double dum = A[ll*N + icol];
-            A[ll*N + icol] = 0.0;
-            for (int l = 0; l < N; l++) A[ll*N + l] -= A[icol*N + l]*dum;
-        }
-    }
-    for (int l = N - 1; l >= 0; l--) {
-        if (indxr[l] == indxc[l]) continue;
-        for (int k = 0; k < N; k++) { const double t = A[k*N + indxr[l]]; A[k*N + indxr[l]] = A[k*N + indxc[l]]; A[k*N + indxc[l]] = t; }
-    }
+    const int err = mimsem::serial_pivot_inverse(N, &A[0], &ipiv[0], &indxr[0], &indxc[0]);
     for (int k = 0; k < N*N; k++) src[k] = A[k];
     if (err && errcount) atomicAdd(errcount, 1);
 }
@@ -1058,21 +928,6 @@ __global__ void k_block_thomas(int nk, int n2, const double* __restrict__ L, con
     }
 }
 
-// Wave-per-column variant (n2 <= 16): the whole sweep of a column is carried by ONE wavefront, so the
-// level-to-level dependency chain needs only wave-level LDS ordering (no s_barrier); the previous level's
-// G_{k-1} = D'^{-1} sup and y_{k-1} stay in LDS.  Gauss-Jordan with partial pivoting on the running diagonal block.
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// the same hand-off when only LDS data crosses lanes: the fences name the local address space, so outstanding GLOBAL loads /
-// stores (the prefetch of the next level, the stores of G and D^-1) are not waited for
-__device__ __forceinline__ void wsync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-}
 // y = M x (or M^T x) WITHOUT the blocks, for the operators whose block (r, w) is W^T diag(c_{r,w}) W: one group of lanes per (column,
 // output slot) task, lane q owns quadrature point q -- it evaluates the coefficient (the same colop_coef the block assembly
 // uses), interpolates the input there and scales; lanes a < n2 project back.  Replaces k_coef_block (53 us) + the stored apply
@@ -1141,46 +996,50 @@ int launch_colop_apply_mf(mimsem_ctx* c, int colop, unsigned flags, int transpos
     return MIMSEM_OK;
 }
 
+// wave-cooperative algebra on N2 x N2 blocks in LDS (the wave-per-column Thomas sweep below, the fused Schur kernels further down)
 template <int N2>
-__global__ __launch_bounds__(64) void k_block_thomas_wave(int nk, const double* __restrict__ L, const double* __restrict__ f,
-                                                          double* __restrict__ d, double* __restrict__ Gws, double* __restrict__ yws,
-                                                          double* __restrict__ Dinv /* optional [nEl][nk][nn]: kept for re-solves */) {
-    constexpr int nn = N2*N2, EPL = (nn + 63)/64;           // entries per lane
-    __shared__ double D[nn], Di[nn], Gp[nn], S[nn], U[nn], v[N2], yp[N2], dn[N2];
-    const int lane = threadIdx.x, e = blockIdx.x;
-    const double* Le = L + (size_t)e*nk*3*nn;
-    double* G = Gws + (size_t)e*nk*nn;
-    double* yv = yws + (size_t)e*nk*N2;
-    for (int k = 0; k < nk; k++) {
-        const double* sub = Le + ((size_t)k*3 + 0)*nn;
-        const double* dia = Le + ((size_t)k*3 + 1)*nn;
-        const double* sup = Le + ((size_t)k*3 + 2)*nn;
-#pragma unroll
-        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) { S[t] = sub[t]; U[t] = sup[t]; } }
+struct WaveBlocks {
+    static constexpr int nn = N2*N2, EPL = (nn + 63)/64;
+    // M = W^T diag(c) W by sum factorisation (W[q][j] = E[qx][jx] E[qy][jy]); lanes (iy, jy)
+    __device__ static void assemble(double* M, const double* cq, const double* sE, const double* sEE, int n, int mp1, int lane) {
+        if (lane < N2) {
+            const int iy = lane/n, jy = lane%n;
+            double t1[8];
+            for (int qx = 0; qx < mp1; qx++) {
+                double s = 0.0;
+                for (int qy = 0; qy < mp1; qy++) s += (sE[qy*n + iy]*cq[qy*mp1 + qx])*sE[qy*n + jy];
+                t1[qx] = s;
+            }
+            for (int ix = 0; ix < n; ix++)
+                for (int jx = 0; jx < n; jx++) {
+                    double s = 0.0;
+                    for (int qx = 0; qx < mp1; qx++) s += sEE[qx*N2 + ix*n + jx]*t1[qx];
+                    M[(iy*n + ix)*N2 + jy*n + jx] = s;
+                }
+        }
         wsync();
+    }
+    // C = alpha * A . B   (C must not alias A or B)
+    __device__ static void mul(double* C, const double* A, const double* B, double alpha, int lane) {
 #pragma unroll
         for (int r = 0; r < EPL; r++) {
             const int t = lane + 64*r;
             if (t < nn) {
                 const int i = t/N2, j = t%N2;
-                double s = dia[t];
-                if (k > 0) {
+                double s = 0.0;
 #pragma unroll
-                    for (int m = 0; m < N2; m++) s -= S[i*N2 + m]*Gp[m*N2 + j];
-                }
-                D[t] = s; Di[t] = (i == j) ? 1.0 : 0.0;
+                for (int m = 0; m < N2; m++) s += A[i*N2 + m]*B[m*N2 + j];
+                C[t] = alpha*s;
             }
-        }
-        if (lane < N2) {
-            double s = f[((size_t)e*nk + k)*N2 + lane];
-            if (k > 0) {
-#pragma unroll
-                for (int m = 0; m < N2; m++) s -= S[lane*N2 + m]*yp[m];
-            }
-            v[lane] = s;
         }
         wsync();
-        // Gauss-Jordan on [D | Di], partial pivoting (every lane finds the same pivot row from LDS)
+    }
+    // Di = D^-1 by Gauss-Jordan on [D | Di] with partial pivoting (every lane finds the same pivot row from LDS); D is destroyed.
+    // Sweep E of small_block_inverse.hpp.
+    __device__ static void inverse(double* D, double* Di, int lane) {
+#pragma unroll
+        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) Di[t] = (t/N2 == t%N2) ? 1.0 : 0.0; }
+        wsync();
         for (int col = 0; col < N2; col++) {
             int p = col; double big = fabs(D[col*N2 + col]);
             for (int r = col + 1; r < N2; r++) { const double a = fabs(D[r*N2 + col]); if (a > big) { big = a; p = r; } }
@@ -1217,6 +1076,60 @@ __global__ __launch_bounds__(64) void k_block_thomas_wave(int nk, const double* 
             for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) { D[t] = nd[r]; Di[t] = ni[r]; } }
             wsync();
         }
+    }
+    __device__ static void load(double* dst, const double* src, int lane) {
+#pragma unroll
+        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) dst[t] = src[t]; }
+        wsync();
+    }
+    __device__ static void store(double* dst, const double* src, int lane) {     // LDS -> global, no sync needed after (LDS is only read)
+#pragma unroll
+        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) dst[t] = src[t]; }
+    }
+};
+
+// Wave-per-column variant (n2 <= 16): the whole sweep of a column is carried by ONE wavefront, so the
+// level-to-level dependency chain needs only wave-level LDS ordering (no s_barrier); the previous level's
+// G_{k-1} = D'^{-1} sup and y_{k-1} stay in LDS.  Gauss-Jordan with partial pivoting on the running diagonal block.
+template <int N2>
+__global__ __launch_bounds__(64) void k_block_thomas_wave(int nk, const double* __restrict__ L, const double* __restrict__ f,
+                                                          double* __restrict__ d, double* __restrict__ Gws, double* __restrict__ yws,
+                                                          double* __restrict__ Dinv /* optional [nEl][nk][nn]: kept for re-solves */) {
+    constexpr int nn = N2*N2, EPL = (nn + 63)/64;           // entries per lane
+    __shared__ double D[nn], Di[nn], Gp[nn], S[nn], U[nn], v[N2], yp[N2], dn[N2];
+    const int lane = threadIdx.x, e = blockIdx.x;
+    const double* Le = L + (size_t)e*nk*3*nn;
+    double* G = Gws + (size_t)e*nk*nn;
+    double* yv = yws + (size_t)e*nk*N2;
+    for (int k = 0; k < nk; k++) {
+        const double* sub = Le + ((size_t)k*3 + 0)*nn;
+        const double* dia = Le + ((size_t)k*3 + 1)*nn;
+        const double* sup = Le + ((size_t)k*3 + 2)*nn;
+#pragma unroll
+        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) { S[t] = sub[t]; U[t] = sup[t]; } }
+        wsync();
+#pragma unroll
+        for (int r = 0; r < EPL; r++) {
+            const int t = lane + 64*r;
+            if (t < nn) {
+                const int i = t/N2, j = t%N2;
+                double s = dia[t];
+                if (k > 0) {
+#pragma unroll
+                    for (int m = 0; m < N2; m++) s -= S[i*N2 + m]*Gp[m*N2 + j];
+                }
+                D[t] = s;
+            }
+        }
+        if (lane < N2) {
+            double s = f[((size_t)e*nk + k)*N2 + lane];
+            if (k > 0) {
+#pragma unroll
+                for (int m = 0; m < N2; m++) s -= S[lane*N2 + m]*yp[m];
+            }
+            v[lane] = s;
+        }
+        WaveBlocks<N2>::inverse(D, Di, lane);               // (its first hand-off publishes D and v too)
         // G_k = Di . sup ; y_k = Di . v
 #pragma unroll
         for (int r = 0; r < EPL; r++) {
@@ -1256,19 +1169,10 @@ __global__ __launch_bounds__(64) void k_block_thomas_wave(int nk, const double* 
     }
 }
 
-// rotate within each row of 16 lanes (DPP row_ror: a VALU modifier, no LDS crossbar trip like ds_bpermute)
-template <int N> __device__ __forceinline__ int row_ror(int v) {
-    return __builtin_amdgcn_update_dpp(v, v, 0x120 + N, 0xF, 0xF, false);
-}
-template <int N> __device__ __forceinline__ double row_ror(double v) {
-    return __hiloint2double(row_ror<N>(__double2hiint(v)), row_ror<N>(__double2loint(v)));
-}
-
 // The same sweep with ONE ROW PER LANE: 16 lanes per column (4 columns per wavefront), the running diagonal block lives in
 // registers (row r in lane r) and the Gauss-Jordan steps talk through cross-lane shuffles instead of LDS round trips:
-// pivot search = 4 butterfly rounds, pivot row = N2 broadcasts.  Rows are never swapped -- the lane chosen at step c keeps the
-// row and remembers c; the in-place inverse T then satisfies  D^-1[c_l][p_c] = T[l][c]  (c_l: step at which lane l was the pivot,
-// p_c: pivot lane of step c), which is how it is scattered into LDS.  LDS only carries the operands of the two block products.
+// pivot search = 4 butterfly rounds, pivot row = N2 broadcasts (rows_gauss_jordan, sweep F of small_block_inverse.hpp, whose in-place
+// result is scattered into LDS in natural order).  LDS only carries the operands of the two block products.
 template <int N2, int GW = 16>
 __global__ __launch_bounds__(64) void k_block_thomas_rows(int nEl, int nk, const double* __restrict__ L, const double* __restrict__ f,
                                                           double* __restrict__ d, double* __restrict__ Gws, double* __restrict__ yws,
@@ -1323,38 +1227,8 @@ __global__ __launch_bounds__(64) void k_block_thomas_rows(int nEl, int nk, const
                 vv -= sm*sy[g][m];
             }
         }
-        // in-place Gauss-Jordan inverse, implicit row pivoting
-        bool used = !act;
-        int myc = 0, piv[N2];
-#pragma unroll
-        for (int c = 0; c < N2; c++) {
-            double cand = used ? -1.0 : fabs(T[c]);
-            int bl = r;
-            // arg-max over the 16 lanes of the column: rotations by 1, 2, 4, 8 (ties -> lowest lane, so every lane agrees)
-#define MIMSEM_ARGMAX_ROUND(N) { const double oc = row_ror<N>(cand); const int ol = row_ror<N>(bl); \
-                                 if (oc > cand || (oc == cand && ol < bl)) { cand = oc; bl = ol; } }
-            MIMSEM_ARGMAX_ROUND(1) MIMSEM_ARGMAX_ROUND(2) MIMSEM_ARGMAX_ROUND(4) MIMSEM_ARGMAX_ROUND(8)
-#undef MIMSEM_ARGMAX_ROUND
-            if constexpr (GW == 32) {            // the two 16-lane rows of the column compare notes
-                const double oc = __shfl_xor(cand, 16, 32); const int ol = __shfl_xor(bl, 16, 32);
-                if (oc > cand || (oc == cand && ol < bl)) { cand = oc; bl = ol; }
-            }
-            piv[c] = bl;
-            double pr[N2];
-#pragma unroll
-            for (int j = 0; j < N2; j++) pr[j] = __shfl(T[j], bl, GW);
-            const double pinv = 1.0/pr[c];
-            if (r == bl) {
-#pragma unroll
-                for (int j = 0; j < N2; j++) T[j] = pr[j]*pinv;
-                T[c] = pinv; used = true; myc = c;
-            } else {
-                const double fct = T[c];
-#pragma unroll
-                for (int j = 0; j < N2; j++) T[j] -= fct*(pr[j]*pinv);
-                T[c] = -fct*pinv;
-            }
-        }
+        int myc, piv[N2];
+        rows_gauss_jordan<N2, GW>(T, r, act, myc, piv);
         if (act) {
 #pragma unroll
             for (int c = 0; c < N2; c++) sI[g][myc*N2 + piv[c]] = T[c];
@@ -1546,96 +1420,7 @@ __global__ __launch_bounds__(256) void k_helmholtz_rows(int n2, int nk, double g
 
 // ---- fused assembly of the Schur factors: one WAVE per (column, level) resp. (column, interface) ----------------------------
 // All intermediate blocks of a task live in LDS; only what later stages need is written.  Wave-cooperative block algebra on
-// N2 x N2 blocks (N2 = 4, 9, 16): sum-factorised W^T diag(c) W, Gauss-Jordan inverse with partial pivoting, products.
-template <int N2>
-struct WaveBlocks {
-    static constexpr int nn = N2*N2, EPL = (nn + 63)/64;
-    // M = W^T diag(c) W by sum factorisation (W[q][j] = E[qx][jx] E[qy][jy]); lanes (iy, jy)
-    __device__ static void assemble(double* M, const double* cq, const double* sE, const double* sEE, int n, int mp1, int lane) {
-        if (lane < N2) {
-            const int iy = lane/n, jy = lane%n;
-            double t1[8];
-            for (int qx = 0; qx < mp1; qx++) {
-                double s = 0.0;
-                for (int qy = 0; qy < mp1; qy++) s += (sE[qy*n + iy]*cq[qy*mp1 + qx])*sE[qy*n + jy];
-                t1[qx] = s;
-            }
-            for (int ix = 0; ix < n; ix++)
-                for (int jx = 0; jx < n; jx++) {
-                    double s = 0.0;
-                    for (int qx = 0; qx < mp1; qx++) s += sEE[qx*N2 + ix*n + jx]*t1[qx];
-                    M[(iy*n + ix)*N2 + jy*n + jx] = s;
-                }
-        }
-        wsync();
-    }
-    // C = alpha * A . B   (C must not alias A or B)
-    __device__ static void mul(double* C, const double* A, const double* B, double alpha, int lane) {
-#pragma unroll
-        for (int r = 0; r < EPL; r++) {
-            const int t = lane + 64*r;
-            if (t < nn) {
-                const int i = t/N2, j = t%N2;
-                double s = 0.0;
-#pragma unroll
-                for (int m = 0; m < N2; m++) s += A[i*N2 + m]*B[m*N2 + j];
-                C[t] = alpha*s;
-            }
-        }
-        wsync();
-    }
-    // Di = D^-1 by Gauss-Jordan with partial pivoting; D is destroyed
-    __device__ static void inverse(double* D, double* Di, int lane) {
-#pragma unroll
-        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) Di[t] = (t/N2 == t%N2) ? 1.0 : 0.0; }
-        wsync();
-        for (int col = 0; col < N2; col++) {
-            int p = col; double big = fabs(D[col*N2 + col]);
-            for (int r = col + 1; r < N2; r++) { const double a = fabs(D[r*N2 + col]); if (a > big) { big = a; p = r; } }
-            if (p != col) {
-                double t0[EPL], t1[EPL];
-#pragma unroll
-                for (int r = 0; r < EPL; r++) {
-                    const int t = lane + 64*r;
-                    if (t < 2*N2) { double* M = (t < N2) ? D : Di; const int j = t%N2; t0[r] = M[col*N2 + j]; t1[r] = M[p*N2 + j]; }
-                }
-                wsync();
-#pragma unroll
-                for (int r = 0; r < EPL; r++) {
-                    const int t = lane + 64*r;
-                    if (t < 2*N2) { double* M = (t < N2) ? D : Di; const int j = t%N2; M[col*N2 + j] = t1[r]; M[p*N2 + j] = t0[r]; }
-                }
-                wsync();
-            }
-            const double pinv = 1.0/D[col*N2 + col];
-            double nd[EPL], ni[EPL];
-#pragma unroll
-            for (int r = 0; r < EPL; r++) {
-                const int t = lane + 64*r;
-                if (t < nn) {
-                    const int i = t/N2, j = t%N2;
-                    const double dcj = D[col*N2 + j]*pinv, icj = Di[col*N2 + j]*pinv;
-                    if (i == col) { nd[r] = dcj; ni[r] = icj; }
-                    else { const double u = D[i*N2 + col]; nd[r] = D[t] - u*dcj; ni[r] = Di[t] - u*icj; }
-                }
-            }
-            wsync();
-#pragma unroll
-            for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) { D[t] = nd[r]; Di[t] = ni[r]; } }
-            wsync();
-        }
-    }
-    __device__ static void load(double* dst, const double* src, int lane) {
-#pragma unroll
-        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) dst[t] = src[t]; }
-        wsync();
-    }
-    __device__ static void store(double* dst, const double* src, int lane) {     // LDS -> global, no sync needed after (LDS is only read)
-#pragma unroll
-        for (int r = 0; r < EPL; r++) { const int t = lane + 64*r; if (t < nn) dst[t] = src[t]; }
-    }
-};
-
+// N2 x N2 blocks (N2 = 4, 9, 16; WaveBlocks above): sum-factorised W^T diag(c) W, Gauss-Jordan inverse with partial pivoting, products.
 struct FusedArgs {
     CG g; double hdt;
     const double *theta, *rho, *eta, *pi;
@@ -1753,7 +1538,7 @@ __global__ __launch_bounds__(256) void k_schur_interfaces(FusedArgs a) {
 }
 
 // ---- the same two fused kernels on ROW-PER-LANE block algebra: 16 lanes per task (4 tasks per wavefront), every block of a task
-// lives in registers (its row r in lane r), Gauss-Jordan as in k_block_thomas_rows (DPP row rotations for the pivot search,
+// lives in registers (its row r in lane r), Gauss-Jordan by rows_gauss_jordan (DPP row rotations for the pivot search,
 // bpermute broadcasts of the pivot row, implicit pivoting); LDS only holds the right-hand operand of a product.
 template <int N>
 struct RowBlocks {
@@ -1783,32 +1568,8 @@ struct RowBlocks {
     }
     // T <- my row of T^-1 (natural row order); sI: this task's nn doubles of LDS scratch
     __device__ static void inverse(double (&T)[N2], double* sI, int r, bool act) {
-        bool used = !act;
-        int myc = 0, piv[N2];
-#pragma unroll
-        for (int c = 0; c < N2; c++) {
-            double cand = used ? -1.0 : fabs(T[c]);
-            int bl = r;
-#define MIMSEM_ARGMAX_ROUND(K) { const double oc = row_ror<K>(cand); const int ol = row_ror<K>(bl); \
-                                 if (oc > cand || (oc == cand && ol < bl)) { cand = oc; bl = ol; } }
-            MIMSEM_ARGMAX_ROUND(1) MIMSEM_ARGMAX_ROUND(2) MIMSEM_ARGMAX_ROUND(4) MIMSEM_ARGMAX_ROUND(8)
-#undef MIMSEM_ARGMAX_ROUND
-            piv[c] = bl;
-            double pr[N2];
-#pragma unroll
-            for (int j = 0; j < N2; j++) pr[j] = __shfl(T[j], bl, GW);
-            const double pinv = 1.0/pr[c];
-            if (r == bl) {
-#pragma unroll
-                for (int j = 0; j < N2; j++) T[j] = pr[j]*pinv;
-                T[c] = pinv; used = true; myc = c;
-            } else {
-                const double fct = T[c];
-#pragma unroll
-                for (int j = 0; j < N2; j++) T[j] -= fct*(pr[j]*pinv);
-                T[c] = -fct*pinv;
-            }
-        }
+        int myc, piv[N2];
+        rows_gauss_jordan<N2, GW>(T, r, act, myc, piv);
         wsync_lds();                                 // earlier readers of sI are done
         if (act) {
 #pragma unroll
@@ -2257,32 +2018,6 @@ __device__ __forceinline__ void reg_assemble(const double (&E)[(N + 1)*N], const
                     P[(iy*N + ix)*N2 + jy*N + jx] = s;
                 }
         }
-}
-// in place; returns false when a natural-order pivot is too small (caller falls back)
-template <int N2>
-__device__ __forceinline__ bool reg_inverse(double (&P)[N2*N2]) {
-    double dmax = 0.0;
-#pragma unroll
-    for (int i = 0; i < N2; i++) dmax = fmax(dmax, fabs(P[i*N2 + i]));
-    bool ok = true;
-#pragma unroll
-    for (int p = 0; p < N2; p++) {
-        const double piv = P[p*N2 + p];
-        if (!(fabs(piv) >= 1.0e-8*dmax) || !(fabs(piv) >= 1.0e-12)) ok = false;
-        const double pinv = 1.0/piv;
-        P[p*N2 + p] = 1.0;
-#pragma unroll
-        for (int cc = 0; cc < N2; cc++) P[p*N2 + cc] *= pinv;
-#pragma unroll
-        for (int r = 0; r < N2; r++) {
-            if (r == p) continue;
-            const double d = P[r*N2 + p];
-            P[r*N2 + p] = 0.0;
-#pragma unroll
-            for (int cc = 0; cc < N2; cc++) P[r*N2 + cc] -= P[p*N2 + cc]*d;
-        }
-    }
-    return ok;
 }
 // A (private memory, dynamic indexing) -> its inverse in I, partial pivoting
 template <int N2>

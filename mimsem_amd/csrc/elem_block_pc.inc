@@ -9,7 +9,7 @@
 //   1. the per-point coefficients (aa, ab, bb) of the operator, as k_elmats probes them;
 //   2. the block, entry (i, j) = sum_q (B_i(q) c(q)) B_j(q) over the points in ascending order (k_elmats' sum), written straight into the
 //      [2 n1e][2 n1e] layout of k_em_to_block (rows and columns: x edges, then y edges);
-//   3. Gauss-Jordan with full pivoting, lane = row: the algorithm and tie-breaking of k_block_inverse_wave / k_block_inverse
+//   3. Gauss-Jordan with full pivoting, lane = row: wave_pivot_inverse (small_block_inverse.hpp), the sweep k_block_inverse_wave runs
 //      (LinAlg.cpp:186-269: the last entry of the row-major scan attaining the maximum, normalise, eliminate, un-permute the columns);
 //   4. out = A^-1 * (d_i d_j), as k_scale_blocks forms it.
 // Same operations in the same order: the same bits as mimsem_ksp_set_pc_bjacobi's blocks.  The block sits in LDS with an odd row stride
@@ -72,40 +72,8 @@ __device__ __forceinline__ void elem_block_pc_body(const ElmatArgs& a, const dou
         sA[i*NS + j] = s;
     }
     __syncthreads();
-    // 3. the inverse (k_block_inverse_wave, error count dropped: PCSetUp does not report it)
-    for (int i = 0; i < ND; i++) {
-        double big = -1.0; int kk = 0;
-        if (lane < ND && ipiv[lane] != 1)
-            for (int k = 0; k < ND; k++)
-                if (ipiv[k] == 0) { const double v = fabs(sA[lane*NS + k]); if (v >= big) { big = v; kk = k; } }
-        double vmax = big;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) vmax = fmax(vmax, __shfl_xor(vmax, off));
-        int jsel = (big == vmax && big >= 0.0) ? lane : -1;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) jsel = max(jsel, __shfl_xor(jsel, off));
-        if (jsel < 0) jsel = 0;                                  // (nothing left to pivot on / NaN)
-        const int irow = jsel, icol = __shfl(kk, jsel);
-        __syncthreads();
-        if (lane == 0) { ++ipiv[icol]; indxr[i] = irow; indxc[i] = icol; }
-        if (irow != icol && lane < ND) { const double t0 = sA[irow*NS + lane]; sA[irow*NS + lane] = sA[icol*NS + lane]; sA[icol*NS + lane] = t0; }
-        __syncthreads();
-        const double pivinv = 1.0/sA[icol*NS + icol];
-        __syncthreads();
-        if (lane < ND) sA[icol*NS + lane] = (lane == icol ? 1.0 : sA[icol*NS + lane])*pivinv;
-        __syncthreads();
-        if (lane < ND && lane != icol) {
-            const double dum = sA[lane*NS + icol];
-            sA[lane*NS + icol] = 0.0;
-            for (int l = 0; l < ND; l++) sA[lane*NS + l] -= sA[icol*NS + l]*dum;
-        }
-        __syncthreads();
-    }
-    for (int l = ND - 1; l >= 0; l--) {
-        const int ir = indxr[l], ic = indxc[l];
-        if (ir != ic && lane < ND) { const double t0 = sA[lane*NS + ir]; sA[lane*NS + ir] = sA[lane*NS + ic]; sA[lane*NS + ic] = t0; }
-        __syncthreads();
-    }
+    // 3. the inverse (error code dropped: PCSetUp does not report it)
+    (void)mimsem::wave_pivot_inverse(sA, ND, NS, ipiv, indxr, indxc, lane);
     // 4. D_e A_e^-1 D_e, row-major, coalesced
     const double* de = dw + (size_t)e*ND;
     double* oe = a.out + ((size_t)row*a.nEl + e)*ND*ND;

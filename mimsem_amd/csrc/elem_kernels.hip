@@ -18,6 +18,7 @@
 //  * HBM-bound by construction (1.5-3.5 flop/B against a ~10 flop/B FP64 ridge): no MFMA here.
 #include <hip/hip_ext.h>
 #include "ctx.hpp"
+#include "small_block_inverse.hpp"
 
 namespace {
 

@@ -530,7 +530,7 @@ def test_max_norms_against_the_composed_reduction(setup):
     assert np.isnan(got[1]) and np.allclose(got[[0, 2, 3]], want[[0, 2, 3]], rtol=1e-13)
 
 
-@pytest.mark.parametrize("n", [1, 4, 9, 16, 24, 33, 40, 56, 64])
+@pytest.mark.parametrize("n", [1, 4, 9, 16, 24, 33, 40, 56, 64, 65])      # (65: past the one-wavefront kernel, thread per block in LDS)
 def test_block_inverse_against_the_oracle_inv(oracle, n):
     """A5 as an entry point (mimsem_block_inverse: the PCBJACOBI blocks and WmatInv / the column inverses run through it): the batched
     Gauss-Jordan against the oracle's restatement of LinAlg::Inv (eul/LinAlg.cpp:186-269, pinned bit-for-bit against the compiled

@@ -203,7 +203,8 @@ def _worst(budgets):
     return " ".join("%s %.2e" % (k, max(b[k] for b in budgets)) for k in ("rel_L", "hip_vs_own_system", "diff", "cond"))
 
 
-def test_schur_column_solve(case):
+def _schur_eta_against_the_oracle(case, keeps_status=True):
+    """helmholtz_blocks and solve_schur_eta on the route the environment selects, every column against the oracle's; returns the solutions"""
     eng, nk, n2 = case.eng, case.nk, case.n2e
     F = case.fields()
     Fs = case.rhs(9)
@@ -212,7 +213,10 @@ def test_schur_column_solve(case):
     L = eng.helmholtz_blocks(*args).cpu().numpy()
     dF = [t(f) for f in Fs]
     d = eng.solve_schur_eta(*args, *dF)
-    _check_status(case)
+    if keeps_status:
+        _check_status(case)
+    else:
+        assert eng.solve_status()[0] == -1
     d = [a.cpu().numpy() for a in d]; dF = [a.cpu().numpy() for a in dF]
     budgets = []
     for e in range(case.nEl):
@@ -221,6 +225,23 @@ def test_schur_column_solve(case):
         others = (("d_u", d[0]), ("d_eta", d[2]), ("d_rho", d[1]), ("F_u", dF[0]), ("F_rho", dF[1]), ("F_eta", dF[2]), ("F_pi", dF[3]))
         budgets.append(_check_solve(case, e, dense_from_band(L[e], nk, n2, lo=1), dF[3], d[3], ref, "L_pi", "F_pi", "d_pi", others))
     print("solve_schur_eta on %s: worst column %s" % (case.label, _worst(budgets)))
+    return d
+
+
+def test_schur_column_solve(case):
+    _schur_eta_against_the_oracle(case)
+
+
+def test_schur_column_solve_order_one_chain(oracle, monkeypatch):
+    """order 1 with MIMSEM_SCHUR_FUSED=0: the chain of wide kernels ends in the wave-per-column Thomas sweep at n2e = 1, which no other
+    setting of the default library launches (order 1 otherwise takes the fused sweep, and the chain of orders 2 to 4 the row-per-lane
+    Thomas kernel).  The four columns of the smallest box against the oracle like every other route, then against the fused route"""
+    case = _with_engine(oracle, ("B4", 1, 4))
+    fused = _schur_eta_against_the_oracle(case)
+    monkeypatch.setenv("MIMSEM_SCHUR_FUSED", "0")
+    chain = _schur_eta_against_the_oracle(case, keeps_status=False)
+    for name, a, b in zip(("d_u", "d_rho", "d_eta", "d_pi"), chain, fused):
+        assert_columns("chain against fused " + name, a, b)
 
 
 @pytest.mark.parametrize("flags", [0, 3], ids=["eul", "box"])
