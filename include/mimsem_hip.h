@@ -361,6 +361,25 @@ int mimsem_horiz_bernoulli(mimsem_ctx* ctx, int nk, const double* velx1, const d
 int mimsem_horiz_flux_rhs(mimsem_ctx* ctx, int nk, const double* u1, const double* u2, long long ldu,
                           const double* h1, const double* h2, long long ldh, double scale, double* out, long long ldo);
 
+/* The element-local forcing of HorizSolve::momentum_rhs (eul/HorizSolve.cpp:496-635, box/HorizSolve.cpp:412-526) for levels 0 .. nk-1 in
+ * TWO launches (k_horiz_momentum_forcing, csrc/momentum_forcing.inc, and the 1-form gather) instead of a RotMat, a Uhmat and a UtQWmat
+ * apply with the combines between them:
+ *   out_k (+)= R(q_k; level k, scale) a_k                                  RotMat::assemble  (eul/Assembly.cpp:1051-1065, box/Assembly.cpp:826-882)
+ *            + F(th_k; level k, const_vert per flag) g_k                   Uhmat::assemble   (eul/Assembly.cpp:432-448, box/Assembly.cpp:273-326)
+ *            + 1/2 sum over i in {k-1, k}, 0 <= i <= nk-2, of Rh(dz_i; scale) v_i   UtQWmat::assemble (eul/Assembly.cpp:1504-1517, box/Assembly.cpp:1359-1410; no thickness)
+ * q [nk][n0], a [nk][n1], th [nk][n2], g [nk][n1], dz [nk-1][n1], v [nk-1][n2], out [nk][n1]: PACKED row-major arrays of the context's
+ * local vectors (rows follow each other at the vector's own length; the entry takes no row distance).  Each of the pairs (q, a), (th, g),
+ * (dz, v) may be NULL together: that term is absent (all three absent: out = 0, or untouched with MIMSEM_FLAG_ACCUM).  flags:
+ * MIMSEM_FLAG_ACCUM adds onto out, as mimsem_op_apply has it; MIMSEM_FLAG_VERT is Uhmat's const_vert (the other two terms have no such
+ * switch).  Element orders 1..7.  The three integrands are summed at the quadrature point before one projection; the element pass leaves
+ * element-local results in the context's element workspace, the gather sums every edge slot's contributions in the plan's order: no
+ * atomics, a fixed summation order -- two calls on the same input give the same bits; no host synchronisation; capturable once a call
+ * outside the capture has sized the workspace (MIMSEM_ERR_STATE if it had to grow inside one).  A null context or out, one NULL of a pair,
+ * (dz, v) given with nk == 1, an unknown flag, out equal to an input or nk outside 1..ctx nk: MIMSEM_ERR_ARG; an order outside 1..7:
+ * MIMSEM_ERR_UNSUPPORTED; nothing launched, out untouched.                                                                            */
+int mimsem_horiz_momentum_forcing(mimsem_ctx* ctx, int nk, unsigned flags, double scale, const double* q, const double* a,
+                                  const double* th, const double* g, const double* dz, const double* v, double* out);
+
 /* Row N3: the packed [u,h] operator of the shallow-water Picard step, SWEqn::assemble_operator (src/SWEqn_Picard.cpp:622-725),
  * which the reference forms with MatMatMult / MatGetRow / MatSetValues and hands to KSPSolve(kspA):
  *     y_u = (M1 + a R(f)) u + a g E12 M2 h        y_h = M2 (a H E21 u + h)        a = ROS_ALPHA dt, g = grav, H = H_MEAN

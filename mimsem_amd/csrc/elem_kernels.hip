@@ -2179,3 +2179,4 @@ int launch_halo_unpack(mimsem_ctx* c, const int* idx, int count, int nlev, int m
 #include "energetics.inc"
 #include "bernoulli.inc"
 #include "flux_rhs.inc"
+#include "momentum_forcing.inc"

@@ -674,6 +674,40 @@ class Engine:
         check(self.L.mimsem_horiz_flux_rhs(self.ctx, nk, ins[0], ins[1], ld(x2), ins[2], ins[3], ld(r2), scale, _ps(o2)[0], ld(o2)), "horiz_flux_rhs")
         return out
 
+    def momentum_forcing(self, rot=None, pgf=None, vor=None, scale=1.0, flags=0, out=None):
+        """mimsem_horiz_momentum_forcing: the element-local forcing of HorizSolve::momentum_rhs (eul/HorizSolve.cpp:496-635,
+        box/HorizSolve.cpp:412-526) of every level in two launches:
+            out_k (+)= R(q_k) a_k + F(th_k; const_vert per FLAG_VERT) g_k + 1/2 sum_{i in {k-1, k}, 0 <= i <= nk-2} Rh(dz_i) v_i
+        rot = (q [nk, n0], a [nk, n1]), pgf = (th [nk, n2], g [nk, n1]), vor = (dz [nk-1, n1], v [nk-1, n2]); a pair left None is an absent
+        term (vor must be None with one level).  flags: FLAG_ACCUM adds onto `out` (then required), FLAG_VERT.  The library takes packed
+        rows only: a strided view is made contiguous here.  out [nk, n1] is one contiguous block and must not be an input"""
+        s = self.sizes
+        _need(not (flags & ~(FLAG_VERT | FLAG_ACCUM)), "flags: FLAG_VERT and FLAG_ACCUM only")
+        pairs = []
+        for name, pair in (("rot", rot), ("pgf", pgf), ("vor", vor)):
+            _need(pair is None or (len(pair) == 2 and pair[0] is not None and pair[1] is not None), name + ": a pair of two tensors or None")
+            pairs.append((None, None) if pair is None else tuple(t if t.is_contiguous() else t.contiguous() for t in pair))
+        (q, a), (th, g), (dz, v) = pairs
+        nrows = lambda t: t.shape[0] if t.dim() == 2 else 1
+        if a is not None or g is not None:                                       # the level count: from the first term given, else from out
+            nk = nrows(a if a is not None else g)
+        elif dz is not None:
+            nk = nrows(dz) + 1
+        else:
+            _need(out is not None, "all three terms absent and no out")
+            nk = nrows(out)
+        _need(1 <= nk <= self.nk, "at most the context's %d levels" % self.nk)
+        _need(dz is None or nk >= 2, "vor: one level has no interface")
+        q2, a2 = self._rows(q, s[0], "rot[0]", rows=nk, optional=True), self._rows(a, s[1], "rot[1]", rows=nk, optional=True)
+        t2, g2 = self._rows(th, s[2], "pgf[0]", rows=nk, optional=True), self._rows(g, s[1], "pgf[1]", rows=nk, optional=True)
+        d2, v2 = self._rows(dz, s[1], "vor[0]", rows=nk - 1, optional=True), self._rows(v, s[2], "vor[1]", rows=nk - 1, optional=True)
+        _need(out is not None or not (flags & FLAG_ACCUM), "FLAG_ACCUM needs out")
+        out, o2 = self._out(out, nk, s[1], exact=True)
+        ins = [_ps(t)[0] for t in (q2, a2, t2, g2, d2, v2)]
+        _need(_ps(o2)[0] not in ins, "out: must not be an input")
+        check(self.L.mimsem_horiz_momentum_forcing(self.ctx, nk, flags, scale, *ins, _ps(o2)[0]), "horiz_momentum_forcing")
+        return out
+
     def _sw_rows(self, x, out):
         """packed rows [u | h] of the sw_operator family (contiguous rows, any row stride): the view of x, the result and its view"""
         x2 = self._rows(x, self.sizes[1] + self.sizes[2], "x", strided="r")

@@ -32,10 +32,11 @@ import os
 import numpy as np
 import torch
 
-from . import io, umjs14
+from . import bubble, io, umjs14
 from .energetics import Energetics
+from .geom import gll_weights
 from .hmomentum import HorizMomentum
-from .horizsolve import SCALE, VERT, HorizSolve
+from .horizsolve import LX, SCALE, VERT, BoxHorizSolve, HorizSolve
 from .vertsolve import VertSolve
 from .vortdiag import VortDiag
 
@@ -72,9 +73,9 @@ class Euler:
         self.eng, self.dt, self.nk = eng, dt, eng.nk
         self.hs_forcing, self.hs_lat = hs_forcing, hs_lat
         self.newton_maxit, self.newton_tol = newton_maxit, newton_tol
-        self.horiz = HorizSolve(eng, quad_coords=quad_coords, do_visc=do_visc)
+        self.horiz = self._make_horiz(quad_coords, do_visc)
         self.horiz.fused_phi = self.FUSED_PHI
-        self.vert = VertSolve(eng, dt)
+        self.vert = self._make_vert()
         self.vort = VortDiag(eng, self.horiz, self.vert)
         self.hmom = HorizMomentum(eng, self.horiz, dt, hs_forcing)
         self.energetics = Energetics(eng, self.vert, self.horiz)
@@ -88,6 +89,12 @@ class Euler:
         self.step = 0                    # the dump counter (Euler::step, set to startStep by the driver: eul/UMJS14.cpp:297)
         self.init1_redone = 0            # init1 solves run again after a missed check
         self._m2inv = self._last = self._thick = None
+
+    def _make_horiz(self, quad_coords, do_visc):
+        return HorizSolve(self.eng, quad_coords=quad_coords, do_visc=do_visc)
+
+    def _make_vert(self):
+        return VertSolve(self.eng, self.dt)
 
     def _step(self, velx, velz, rho, rt, exner, carried, ec=True):
         """one evaluation of the step from `carried` = (first_step, u_curr, uz); changes nothing of self.first_step / u_* / uz*.
@@ -107,7 +114,8 @@ class Euler:
         uz_prev = None if first else uz_last
         u_prev, u_curr = u_curr, velx.clone()
         # 1. explicit horizontal momentum solve, the predictor (:1421-1457)
-        theta_0 = to_h(eng.diag_theta(0 if ec else 1, rho_v, rt_v), rows_th)
+        theta_0 = to_h(self._stage1_theta(ec, rho_v, rt_v, velz), rows_th)
+        self._theta_0 = theta_0                                                         # (what the box twin's diagnostics take the entropy of)
         uz = vort.horiz_pot_vort(velx, rho)
         dwdx1 = vort.vert_vort(velz_h0, rho)
         if first:
@@ -123,9 +131,10 @@ class Euler:
             ok.append(horiz.verify())                                                   # (the solves of the iteration before)
             dF, dG, _, _ = adv_rhs(velx, velx_p, rho, to_h(rho_j), to_h(theta_l2_h, rows_th))
             return to_v(dF), to_v(dG)
-        velz_n, rho_nv, rt_nv, exner_nv = solve(velz, rho_v, rt_v, exner_v, self.zv, horiz_forcing=forcing, udwdx=None,
+        velz_n, rho_nv, rt_nv, exner_nv = solve(velz, rho_v, rt_v, exner_v, self.zv, horiz_forcing=forcing,
                                                 hs_lat=self.hs_lat if self.hs_forcing else None,
-                                                maxit=self.newton_maxit, tol=self.newton_tol)
+                                                maxit=self.newton_maxit, tol=self.newton_tol,
+                                                **self._vertical_solve_options(first, velx, velx_p, velz_h0))
         rho_n, rt_n, exner_n = to_h(rho_nv), to_h(rt_nv), to_h(exner_nv)
         velz_hn = to_h(velz_n, nk - 1)
         # 3. explicit horizontal solve, the corrector (:1470-1493): the time-centred theta_l2_h, exner_h the vertical solve left; the friction
@@ -139,6 +148,19 @@ class Euler:
         velx_n = self.hmom.corrector(velx, Fu, exner_n)
         ok.append(horiz.verify())
         return (velx_n, velz_n, rho_n, rt_n, exner_n), (u_prev, u_curr, uz, uz_prev), all(ok)
+
+    # ---- what the box twin's step does differently (BoxEuler) ------------------------------------------------------------------------------
+    def _stage1_theta(self, ec, rho_v, rt_v, velz):
+        """theta_0 of stage 1 in the vertical layout: diagTheta_L2 (:1421) / diagTheta2 (:1201)"""
+        return self.eng.diag_theta(0 if ec else 1, rho_v, rt_v)
+
+    def _vertical_solve_options(self, first, velx, velx_p, velz_h0):
+        """further keyword arguments of the vertical solve of stage 2"""
+        return dict(udwdx=None)
+
+    def _diagnostics(self, new):
+        """the energetics line of the new state (:1501)"""
+        return self.energetics.diagnostics(*new)
 
     def strang_ec(self, velx, velz, rho, rt, exner, diagnostics=True):
         """one step; the inputs are not changed.  Returns (velx, velz, rho, rt, exner, values): the new fields and the twelve numbers of
@@ -171,7 +193,7 @@ class Euler:
         self.u_prev, self.u_curr, self.uz, self.uz_prev = kept
         self.first_step = False
         self.steps += 1
-        values = self.energetics.diagnostics(*new) if diagnostics else None            # :1501
+        values = self._diagnostics(new) if diagnostics else None                       # :1501
         return (*new, values)
 
     # ---- the initial state (eul/Euler_2.cpp:429-529, eul/UMJS14.cpp:318-322) -----------------------------------------------------------
@@ -297,3 +319,95 @@ class Euler:
         self.first_step = True
         self.u_prev = self.u_curr = self.uz = self.uz_prev = None
         return velx, velz, rho, rt, exner
+
+
+class BoxEuler(Euler):
+    """Euler::Strang of the doubly periodic box (box/Euler_2.cpp:1306-1477): Euler.strang's skeleton -- the carried state, the check points,
+    the redo on a miss, the commit after the checks -- on BoxHorizSolve, with what the box twin does differently:
+
+      stage 1 (:1359-1383)  theta_0 = Euler::diagTheta (:543-565) = diag_theta_wup(0.25 dt, rho, rt, velz): the test functions upwinded by the
+                            vertical velocity; plain M1 predictor and corrector solves, no friction
+      uuz (:1337)           AssembleVertMomVort(velz_0) runs before ul is filled on the first step and PETSc vectors start zeroed: uuz = 0 on
+                            the first step, vert_mom_vort(velx, velz_0) on later ones (ul then holds the velocity the last step left)
+      stage 2 (:1392)       solve_schur_2(schur3_flags = 3, theta_up, udwdx = uuz, vert_mom_vort bound to the predictor velocity (u2l = ul,
+                            box/VertSolve.cpp:1403), horiz_forcing = advection_rhs(velx_0, velx_p, ...))
+      stage 3 (:1399-1413)  on vert.theta_h / vert.exner_h with Fk of the last advection_rhs; uz / uz_prev and u_prev / u_curr as on the sphere.
+                            The order of the local copies at :1403 (ul, ul_prev against velx_0, velx) has no effect here: the box Phi and wxu
+                            are symmetric in the pair
+      diagnostics (:887-1026)  eleven numbers are Energetics' own; the entropy is the box's: CP sum_columns sum_{k=0..nk} lz_k sum_q Q_q
+                            log((W theta_k)_q), lz half a layer at both ends, of STAGE 1's theta_0 -- the field the reference passes (:1421)
+
+    Orders 1..4 (Engine.diag_theta_wup).  Uniform layers only (BoxHorizSolve).  Not built: Trapazoidal (:1065), the quadrature-grid dumps"""
+    # the element-local sum of momentum_rhs: mimsem_horiz_momentum_forcing (two launches) or the composed applies -- decided by the
+    # measurement of scripts/prof_box_strang.py (profiles/box_strang.txt: p = 4, 32 x 32 x 64; one evaluation 585 us against 609 us, the
+    # forcing alone 63 us against 115 us)
+    FUSED_FORCING = True
+
+    def __init__(self, eng, dt, levs, quad_coords, lx=LX, newton_maxit=20, newton_tol=1e-12, do_visc=True):
+        """eng: Engine of a one-patch PeriodicBox (global numbering, nk >= 4, order <= 4); levs [nk+1, nq]; quad_coords [nq, 3]"""
+        if eng.mesh.n > 4:
+            raise NotImplementedError("BoxEuler: orders 1..4 (the upwinded theta diagnosis), got %d" % eng.mesh.n)
+        self.lx = lx
+        super().__init__(eng, dt, levs, quad_coords, newton_maxit=newton_maxit, newton_tol=newton_tol, do_visc=do_visc)
+        self.horiz.fused_forcing = self.FUSED_FORCING
+        self._theta_0 = None
+        w = torch.as_tensor(gll_weights(eng.mesh.m), dtype=torch.float64, device=eng.device)
+        self._Q = (w[:, None] * w[None, :]).reshape(-1)                                 # Q_q = w_qx w_qy, q = qy mp1 + qx
+        lz = torch.full((self.nk + 1,), self.horiz.thickness, dtype=torch.float64, device=eng.device)
+        lz[0] *= 0.5; lz[-1] *= 0.5                                                     # :988
+        self._lz = lz
+
+    def _make_horiz(self, quad_coords, do_visc):
+        return BoxHorizSolve(self.eng, lx=self.lx, do_visc=do_visc)
+
+    def _make_vert(self):
+        return VertSolve(self.eng, self.dt, rayleigh=0.0)                               # box/VertSolve.cpp:30: no Rayleigh layer
+
+    def _stage1_theta(self, ec, rho_v, rt_v, velz):
+        return self.eng.diag_theta_wup(0.25 * self.dt, rho_v, rt_v, velz)              # Euler::diagTheta :543-565
+
+    def _vertical_solve_options(self, first, velx, velx_p, velz_h0):
+        eng, nk = self.eng, self.nk
+        uuz = eng.zeros(eng.nEl, (nk - 1) * eng.n2e) if first else self.vort.vert_mom_vort(velx, velz_h0)             # :1337
+        mom_vort = lambda velz_j: self.vort.vert_mom_vort(velx_p, eng.l2_vert_to_horiz(velz_j.contiguous(), nk - 1))   # box/VertSolve.cpp:1403
+        return dict(udwdx=uuz, schur3_flags=3, theta_up=True, vert_mom_vort=mom_vort)
+
+    def entropy(self, theta):
+        """:979-997 of theta [nk+1, n2] (horizontal layout), a device scalar"""
+        tq = self.eng.interp_quad(2, theta, push_forward=False)                         # W theta_k at the points: [nk+1, nEl, mp12]
+        return bubble.CP * (self._lz[:, None, None] * self._Q[None, None, :] * torch.log(tq)).sum()
+
+    def _diagnostics(self, new):
+        out = self.energetics.diagnostics(*new, read=False).clone()
+        out[11] = self.entropy(self._theta_0)
+        return out.tolist()
+
+    def strang(self, velx, velz, rho, rt, exner, diagnostics=True):
+        """one step; the inputs are not changed.  Returns (velx, velz, rho, rt, exner, values) as Euler.strang"""
+        return self._checked_step("strang", False, velx, velz, rho, rt, exner, diagnostics)
+
+    def strang_ec(self, *a, **kw):
+        raise NotImplementedError("BoxEuler: the box twin has no Strang_ec")
+
+    def initial_state(self, theta_0=bubble.THETA_0, ztop=bubble.ZTOP):
+        """(velx, velz, rho, rt, exner) of the rising bubble (box/Bubble.cpp:179-183): the analytic fields of mimsem_amd/bubble.py at this
+        object's quadrature points and level count, projected by init1 / init2 -- which are box/Euler_2.cpp:719-817 line for line: the same
+        UtQ / WtQ operators, SCALE, and M1->M / M2->M, on uniform layers the level-k matrices; velz = 0"""
+        uq, rho, rt, exner = bubble.layer_fields(self.nk, self.xq, ztop=ztop, lx=self.lx, theta_0=theta_0)
+        velz = self.eng.zeros(self.eng.nEl, (self.nk - 1) * self.eng.n2e)
+        return self.init1(uq), velz, self.init2(rho), self.init2(rt), self.init2(exner)
+
+    def run(self, state, nsteps, dump_every=0, outdir="output", start_step=0, on_step=None):
+        """the driver's loop (box/Bubble.cpp:208-215), as Euler.run with Strang"""
+        return super().run(state, nsteps, dump_every, outdir, start_step, on_step, integrator="strang")
+
+    def dump(self, state, step, outdir="output"):
+        """the .vec files of the `save` branch (:1424-1454): velocity_h, density, rhoTheta, exner (nk levels), velocity_z (nk-1 levels in the
+        horizontal layout) and theta (nk+1 levels, Euler::diagTheta of the state: the upwinded diagnosis).  The quadrature-grid fields are not
+        written"""
+        eng, nk = self.eng, self.nk
+        velx, velz, rho, rt, exner = state
+        theta = eng.l2_vert_to_horiz(eng.diag_theta_wup(0.25 * self.dt, eng.l2_horiz_to_vert(rho), eng.l2_horiz_to_vert(rt), velz), nk + 1)
+        velz_h = eng.l2_vert_to_horiz(velz.contiguous(), nk - 1)
+        for name, a in (("velocity_h", velx), ("density", rho), ("rhoTheta", rt), ("exner", exner), ("velocity_z", velz_h), ("theta", theta)):
+            io.save_levels(name, step, a.detach().cpu().numpy(), outdir)

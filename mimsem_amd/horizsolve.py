@@ -33,6 +33,8 @@ class HorizSolve:
         self.fused_phi = False                                  # diagnose_Phi: True = the one-launch kernel (Engine.bernoulli), False = the eight composed launches
         self.fused_hu = False                                   # the mass-flux right-hand side of advection_rhs / momentum_rhs: True = Engine.flux_rhs
                                                                 # (two launches), False = _uvec_hu4 (four accumulated applies); the _ec methods keep _uvec_hu4
+        self.fused_forcing = False                              # the element-local sum of momentum_rhs (rotational term, pressure gradient force, second
+                                                                # vorticity term): True = Engine.momentum_forcing (two launches), False = the composed applies
         if quad_coords is not None:
             self.coriolis(quad_coords)
 
@@ -177,38 +179,121 @@ class HorizSolve:
             self.k2i_dev = self.eng.wsum(1, eng.combine(Fk, 1.0, "mul", dp)) / SCALE   # stays on the device (no host sync: hipGraph-capturable)
         return self._vorticity_and_viscosity(fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2)
 
-    def _vorticity_and_viscosity(self, fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2):
-        """the end both momentum right-hand sides share (:565-623, :710-768): the second vorticity term and the biharmonic viscosity, added to fu"""
+    def _vorticity_operands(self, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2):
+        """coefficient and input of the second vorticity term (:565-607): Rh is linear in its coefficient, so dudz_h - dwdx_h is one field"""
         eng = self.eng
-        # second vorticity term: interface i feeds levels i and i+1
         dz = eng.combine(dudz1, 0.5, beta=0.5, c=dudz2)
         if dwdx1 is not None:
             eng.combine(dwdx1, -0.5, beta=1.0, c=dz, out=dz)
             eng.combine(dwdx2, -0.5, beta=1.0, c=dz, out=dz)
         v = Fz if Fz is not None else eng.combine(velz1, 0.5, beta=0.5, c=velz2)
-        t = eng.apply("UTQWMAT", v, f=dz, lev0=0, scale=SCALE)                  # UtQWmat::assemble(u1, scale): no thickness
-        eng.combine(t, 0.5, beta=1.0, c=fu[1:], out=fu[1:])
-        eng.combine(t, 0.5, beta=1.0, c=fu[:-1], out=fu[:-1])
+        return dz, v
+
+    def _viscosity(self, fu, uh):
+        """the biharmonic viscosity (:609-623, :754-768), added to fu"""
         if self.do_visc:
             self._ap("UMAT", self.laplacian(self.laplacian(uh)), flags=VERT | ACCUM, out=fu)
         return fu
+
+    def _vorticity_and_viscosity(self, fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2):
+        """the end both momentum right-hand sides share (:565-623, :710-768): the second vorticity term and the biharmonic viscosity, added to fu"""
+        eng = self.eng
+        # second vorticity term: interface i feeds levels i and i+1
+        dz, v = self._vorticity_operands(dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2)
+        t = eng.apply("UTQWMAT", v, f=dz, lev0=0, scale=SCALE)                  # UtQWmat::assemble(u1, scale): no thickness
+        eng.combine(t, 0.5, beta=1.0, c=fu[1:], out=fu[1:])
+        eng.combine(t, 0.5, beta=1.0, c=fu[:-1], out=fu[:-1])
+        return self._viscosity(fu, uh)
+
+    def _rotational_operands(self, velx1, velx2, uh, rho1, rho2, Fx):
+        """(q, a) of the rotational term R(q) a (:519-554): the potential vorticity of the mean state and the mass flux, solved for when
+        the caller has none"""
+        q = self.diagnose_q(self.eng.combine(rho1, 0.5, beta=0.5, c=rho2), uh)
+        if Fx is None:
+            Fx, _ = self.m1.solve(self._hu(velx1, velx2, rho1, rho2))
+        return q, Fx
 
     def momentum_rhs(self, theta, dudz1, dudz2, velz1, velz2, Pi, velx1, velx2, rho1, rho2, Fx=None, Fz=None, dwdx1=None, dwdx2=None, Fk=None):
         """:496-635 for every level at once: momentum_rhs_ec with theta [nk+1, n2] on the interfaces.  There is no grad(theta); the pressure
         gradient force is the single term fu += F(theta_h; no vert_scale) dPi, theta_h = 1/2 theta_k + 1/2 theta_{k+1} (:514-517, :556-558),
         and self.k2i = sum_k Fk_k . (F(theta_h) dPi)_k / SCALE (:560-563, needs Fk).  The mass flux of the rotational term (Fx None) is
-        formed by fused_hu.  Returns fu [nk, n1]"""
+        formed by fused_hu.  With fused_forcing the rotational term, the pressure gradient force and the second vorticity term are one
+        Engine.momentum_forcing call; dp for k2i then keeps its own Uhmat apply.  Returns fu [nk, n1]"""
         eng = self.eng
         Phi = self.diagnose_Phi(velx1, velx2, velz1, velz2)
         dPi = self.grad(Pi)
         fu = eng.incidence("E12", Phi)
         uh = eng.combine(velx1, 0.5, beta=0.5, c=velx2)
-        q = self.diagnose_q(eng.combine(rho1, 0.5, beta=0.5, c=rho2), uh)
-        if Fx is None:
-            Fx, _ = self.m1.solve(self._hu(velx1, velx2, rho1, rho2))
-        self._ap("ROTMAT", Fx, f=q, flags=ACCUM, out=fu)
-        dp = self._ap("UHMAT", dPi, f=self._theta_levels(theta), flags=0)        # pressure gradient force
+        q, a = self._rotational_operands(velx1, velx2, uh, rho1, rho2, Fx)
+        theta_h = self._theta_levels(theta)
+        if self.fused_forcing:
+            eng.momentum_forcing(rot=(q, a), pgf=(theta_h, dPi), vor=self._vorticity_operands(dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2),
+                                 scale=SCALE, flags=ACCUM, out=fu)
+            if Fk is not None:
+                dp = self._ap("UHMAT", dPi, f=theta_h, flags=0)
+                self.k2i_dev = self.eng.wsum(1, eng.combine(Fk, 1.0, "mul", dp)) / SCALE
+            return self._viscosity(fu, uh)
+        self._ap("ROTMAT", a, f=q, flags=ACCUM, out=fu)
+        dp = self._ap("UHMAT", dPi, f=theta_h, flags=0)                          # pressure gradient force
         eng.combine(dp, 1.0, beta=1.0, c=fu, out=fu)
         if Fk is not None:
             self.k2i_dev = self.eng.wsum(1, eng.combine(Fk, 1.0, "mul", dp)) / SCALE   # stays on the device (no host sync)
         return self._vorticity_and_viscosity(fu, uh, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2)
+
+
+LX = 1000.0                    # box/HorizSolve.cpp:22
+
+
+def uniform_thickness(thick, rtol=1e-14):
+    """the one layer thickness of a mesh whose layers all have it (thick: any array of thicknesses, e.g. DeviceMesh.thick), to rtol
+    relative; ValueError otherwise"""
+    import numpy as np
+    thick = np.asarray(thick, dtype=np.float64)
+    lo, hi = float(thick.min()), float(thick.max())
+    if not (lo > 0.0 and hi - lo <= rtol * hi):
+        raise ValueError("BoxHorizSolve: uniform layers only -- the thickness ranges from %.17g to %.17g" % (lo, hi))
+    return hi
+
+
+class BoxHorizSolve(HorizSolve):
+    """HorizSolve of the doubly periodic box (box/HorizSolve.cpp).  What differs from the sphere's class:
+
+      viscosity()      :106-114: del2 = -sqrt(2 * 0.072 dx^3.2), dx = sqrt(LX^2 / nDofs0G)
+      rotational term  diagnose_wxu :382-410: R(1/2 curl u1 + 1/2 curl u2; level) (1/2 u1 + 1/2 u2), curl = M0^-1 E01 M1 u without a Coriolis
+                       term -- no diagnose_q, no mass-flux solve.  curl is linear: one curl of the mean velocity
+      momentum_rhs     :412-526: E12 Phi + wxu + F(theta_h; no const_vert) dPi + the Rh terms + M1 del^4, through HorizSolve.momentum_rhs with
+                       the rotational operands above; the Rh coefficient is dudz_h - dwdx_h by linearity (_vorticity_operands); k2i as there
+      advection_rhs    :214-324: the sphere's theta_in_Wt branch, inherited; do_temp_visc (:285-310) is not built, its only caller
+                       (box/VertSolve.cpp:1333) passes false
+
+    UNIFORM LAYERS ONLY.  The reference assembles M1->M, M2->M and m0 once, at level 0 (box/Assembly.cpp:44), and applies them at every
+    level; on layers of one thickness they are the level-k operators the solvers of the base class apply.  Every box/ driver has such layers
+    (z_at_level = ki ZTOP / NK); the constructor raises on any other mesh.
+
+    A defect of the reference that is NOT mirrored: the box diagnose_Phi (:326-380) takes its kinetic-energy part from Wvec::assemble_K, whose
+    Wt table is allocated zeroed and never filled (box/Assembly.cpp:2994-3005), so that part is zero in the reference as written.  Built is
+    the evident intent, the commented-out K->assemble form at :336-349 -- the sphere's diagnose_Phi, inherited.  The _ec routines have no
+    box twin"""
+
+    def __init__(self, eng, lx=LX, del2=None, do_visc=True):
+        self.thickness = uniform_thickness(eng.mesh.thick)
+        self.lx = lx
+        if del2 is None:
+            n0g = float(eng.wsum(0, torch.ones(eng.sizes[0], dtype=torch.float64, device=eng.device)))
+            del2 = self.viscosity(lx, n0g)
+        super().__init__(eng, del2=del2, quad_coords=None, do_visc=do_visc)
+
+    @staticmethod
+    def viscosity(lx, n0g):
+        """:106-114 with the GLOBAL node count nDofs0G"""
+        dx = math.sqrt(lx * lx / n0g)
+        return -math.sqrt(2.0 * 0.072 * dx ** 3.2)
+
+    def _rotational_operands(self, velx1, velx2, uh, rho1, rho2, Fx):
+        """diagnose_wxu :382-410: the relative vorticity of the mean velocity and the mean velocity itself"""
+        return self.curl(uh), uh
+
+    def _no_box_twin(self, *a, **kw):
+        raise NotImplementedError("BoxHorizSolve: box/HorizSolve.cpp has no such routine")
+
+    coriolis = diagnose_q = momentum_rhs_ec = advection_rhs_ec = _no_box_twin

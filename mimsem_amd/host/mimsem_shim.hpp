@@ -708,6 +708,13 @@ struct Euler {
                       double scale, double* Phi, long long ldp) const {
         check(mimsem_horiz_bernoulli(mesh->ctx, nk, velx1, velx2, ldu, velz1, velz2, ldz, scale, Phi, ldp), "HorizSolve::diagnose_Phi");
     }
+    // the element-local forcing of HorizSolve::momentum_rhs (eul/HorizSolve.cpp:496-635, box/HorizSolve.cpp:412-526) of levels 0 .. nk-1 in two
+    // launches: fu (+)= R(q) a + F(th; const_vert per MIMSEM_FLAG_VERT) g + 1/2 sum over a level's interfaces of Rh(dz) v.  Packed rows: q [nk][n0],
+    // a, g, fu [nk][n1], th [nk][n2], dz [nk-1][n1], v [nk-1][n2]; a pair left null is an absent term.  flags: MIMSEM_FLAG_ACCUM, MIMSEM_FLAG_VERT
+    void momentum_forcing(int nk, unsigned flags, double scale, const double* q, const double* a, const double* th, const double* g,
+                          const double* dz, const double* v, double* fu) const {
+        check(mimsem_horiz_momentum_forcing(mesh->ctx, nk, flags, scale, q, a, th, g, dz, v, fu), "HorizSolve::momentum_forcing");
+    }
     Mesh* mesh;
 };
 
