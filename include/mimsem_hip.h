@@ -380,6 +380,29 @@ int mimsem_horiz_flux_rhs(mimsem_ctx* ctx, int nk, const double* u1, const doubl
 int mimsem_horiz_momentum_forcing(mimsem_ctx* ctx, int nk, unsigned flags, double scale, const double* q, const double* a,
                                   const double* th, const double* g, const double* dz, const double* v, double* out);
 
+/* Zonal-mean statistics of a 3-D state on the device (csrc/zonal_stats.inc): what a Held-Suarez run (eul/HeldSuarez.cpp) is averaged into.
+ *
+ * mimsem_zonal_plan_build: band_host is a HOST array [nEl][mp12] that names the band in [0, nb) of every quadrature point of every
+ * element, or -1 for a point that is left out.  The library checks every value, sorts the kept points by (band, element, point) and keeps
+ * the list on the device: the context owns it (released with the context), a second call replaces it.  A value outside [-1, nb), nb <= 0
+ * or a null pointer: MIMSEM_ERR_ARG, an earlier plan stays in place.  Synchronous copies: not inside a stream capture (MIMSEM_ERR_STATE).
+ *
+ * mimsem_euler_zonal_moments: with the fields of Geom::write1 / write2(vert_scale = true) (eul/Geom.cpp:474-631) at the quadrature point q
+ * of element e on level k -- (u, v) = interp1_g(velx_k) / thick_k, r, H, P = interp2_g(rho_k, rt_k, exner_k) / thick_k, T = H P / (CP r)
+ * (CP = 1004.5: the Exner function carries it, eul/VertOps.cpp:1564) -- and the weight a = Q_q det[e][q] (every element adds its own
+ * share of a shared point)
+ *   acc[m][k][b] += sum over the points of band b of a {1, u, v, T, uu, vv, uv, vT, TT}[m]          m = 0 .. 8, k = 0 .. nlev-1
+ * velx [nlev][n1], rho, rt, exner [nlev][n2]: PACKED row-major arrays of the context's local vectors (the entry takes no row distance);
+ * acc [9][nlev][nb], DEVICE.  The sample is formed completely, then added once: a running time sum needs no read-back, and base + sample
+ * is the same bits on every call.  ONE launch, a block per (non-empty band, level); no floating-point atomics, no workspace; the grid and
+ * the order of every sum depend on (plan, nlev, order) only; capturable.  An empty band adds exactly nothing and nothing is loaded for it.
+ * A point with r <= 0 or a NaN input makes the moments that hold its field NaN in that (level, band) entry and nowhere else (r: T, vT,
+ * TT).  Element orders 1..7.  No plan, nlev outside 1..ctx nk, a null pointer or acc overlapping an input: MIMSEM_ERR_ARG, nothing
+ * launched, acc untouched.                                                                                                          */
+int mimsem_zonal_plan_build(mimsem_ctx* ctx, const int* band_host, int nb);
+int mimsem_euler_zonal_moments(mimsem_ctx* ctx, int nlev, const double* velx, const double* rho, const double* rt, const double* exner,
+                               double* acc);
+
 /* Row N3: the packed [u,h] operator of the shallow-water Picard step, SWEqn::assemble_operator (src/SWEqn_Picard.cpp:622-725),
  * which the reference forms with MatMatMult / MatGetRow / MatSetValues and hands to KSPSolve(kspA):
  *     y_u = (M1 + a R(f)) u + a g E12 M2 h        y_h = M2 (a H E21 u + h)        a = ROS_ALPHA dt, g = grav, H = H_MEAN

@@ -181,6 +181,8 @@ _SIGS = {
     "mimsem_horiz_bernoulli": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_ll, c_dp, c_dp, c_ll, C.c_double, c_dp, c_ll]),
     "mimsem_horiz_flux_rhs": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_ll, c_dp, c_dp, c_ll, C.c_double, c_dp, c_ll]),
     "mimsem_horiz_momentum_forcing": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "mimsem_zonal_plan_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "mimsem_euler_zonal_moments": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp, c_dp]),
     "mimsem_ksp_get_pc_blocks": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
     "mimsem_ksp_ritz": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "mimsem_graph_begin": (C.c_int, [C.c_void_p]),

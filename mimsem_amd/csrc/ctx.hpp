@@ -83,6 +83,15 @@ struct WaveTables {
 
 enum class Mem { Plain, Uncached, FineGrained };      // kinds of device memory mimsem_ctx::alloc hands out
 
+// The band plan of mimsem_zonal_plan_build (zonal_stats.inc): the kept quadrature points sorted by (band, element, point).  A whole new
+// value is assigned once its three tables are on the device; the tables it replaces stay allocated until the context goes.
+struct ZonalPlan {
+    int nb = 0, nne = 0, npts = 0;      // bands of the caller's table (0: no plan), non-empty bands, kept points
+    int* band = nullptr;                // [nne]     band of work item i
+    int* off = nullptr;                 // [nne + 1] its points are pt[off[i]] .. pt[off[i+1] - 1]
+    int* pt = nullptr;                  // [npts]    e mp12 + q, every entry checked against nEl mp12 by the builder
+};
+
 struct mimsem_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -133,6 +142,7 @@ struct mimsem_ctx {
     int* d_ppart = nullptr;             // [nps][2] their partial-sum indices (-1 = none)
     // wave-level fused scatter-add (k_apply_wave, elem_wave.inc): the plan is `wv` (WaveTables above); what follows are the tuning knobs
     WaveTables wv;
+    ZonalPlan zon;                      // mimsem_zonal_plan_build
     int wave_order = 3;                 // bit 0: XCD-contiguous block order, bit 1: group-major items (MIMSEM_WAVE_ORDER)
     int wave_lch = 0;                   // MIMSEM_WAVE_LCH override of the levels per chunk
     int wave2_mode = 1;                 // MIMSEM_WAVE2: 2-form-valued operators on k_apply_wave2 (p = 3): 0 none, 1 Whmat / WtQUmat / WtQdUdz, 2 also Wmat

@@ -136,6 +136,7 @@ class Engine:
         self.nEl, self.nk = dmesh.nEl, dmesh.nk
         self.sizes = {0: dmesh.n0, 1: dmesh.n1, 2: dmesh.n2, "q": dmesh.nq, "q2": 2 * dmesh.nq}
         self._linear_inv = None              # the LINEAR_INV column blocks energetics_column reads (made on its first call)
+        self._zonal_nb = 0                   # bands of the context's zonal plan (zonal_plan; 0: none)
 
     def __del__(self):
         try:
@@ -707,6 +708,37 @@ class Engine:
         _need(_ps(o2)[0] not in ins, "out: must not be an input")
         check(self.L.mimsem_horiz_momentum_forcing(self.ctx, nk, flags, scale, *ins, _ps(o2)[0]), "horiz_momentum_forcing")
         return out
+
+    def zonal_plan(self, band, nb=None):
+        """mimsem_zonal_plan_build: band [nEl, mp12] (host integers) names the band in [0, nb) of every quadrature point of every element,
+        -1 leaves a point out; nb: the number of bands (default: the largest value + 1).  The library validates the table and keeps the
+        sorted point list on the device; a second call replaces it.  Returns nb"""
+        b, addr = _host(np.asarray(band), np.int32)
+        _need(b.shape == (self.nEl, self.mp12), "band: [nEl=%d, mp12=%d] integers, got %s" % (self.nEl, self.mp12, b.shape))
+        nb = int(b.max()) + 1 if nb is None else int(nb)
+        _need(nb >= 1 and int(b.min()) >= -1 and int(b.max()) < nb, "band: values in [-1, nb), nb >= 1")
+        check(self.L.mimsem_zonal_plan_build(self.ctx, addr, nb), "zonal_plan_build")
+        self._zonal_nb = nb
+        return nb
+
+    def zonal_moments(self, velx, rho, rt, exner, acc):
+        """mimsem_euler_zonal_moments: acc [9, nlev, nb] += the band sums of a {1, u, v, T, uu, vv, uv, vT, TT} of the physical fields of
+        velx [nlev, n1], rho, rt, exner [nlev, n2] over the bands of zonal_plan, in one launch.  The library takes packed rows only: a
+        strided view is made contiguous here.  acc is one contiguous block and must not be an input"""
+        nb = self._zonal_nb
+        _need(nb > 0, "zonal_moments: no plan (Engine.zonal_plan)")
+        ins = [t if t is None or t.is_contiguous() else t.contiguous() for t in (velx, rho, rt, exner)]
+        vx = self._rows(ins[0], self.sizes[1], "velx", min_rows=1)
+        nlev = vx.shape[0]
+        _need(nlev <= self.nk, "velx: at most the context's %d levels" % self.nk)
+        r2, t2, e2 = self._like(self.sizes[2], nlev, rho=ins[1], rt=ins[2], exner=ins[3])
+        _need(r2 is not None and t2 is not None and e2 is not None, "rho, rt, exner: [nlev, n2] required")
+        _need(acc is not None and tuple(acc.shape) == (9, nlev, nb), "acc: [9, nlev=%d, nb=%d] required" % (nlev, nb))
+        pa = self._vec(acc, 9 * nlev * nb, "acc")
+        ptrs = [_ps(t)[0] for t in (vx, r2, t2, e2)]
+        _need(pa not in ptrs, "acc: must not be an input")
+        check(self.L.mimsem_euler_zonal_moments(self.ctx, nlev, *ptrs, pa), "euler_zonal_moments")
+        return acc
 
     def _sw_rows(self, x, out):
         """packed rows [u | h] of the sw_operator family (contiguous rows, any row stride): the view of x, the result and its view"""

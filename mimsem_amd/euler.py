@@ -231,21 +231,22 @@ class Euler:
             self.init1_redone += 1
         raise RuntimeError("Euler.init1: the solve missed its check again after the switch to the adaptive solver")
 
-    def initial_state(self, vp=umjs14.VP):
+    def initial_state(self, vp=umjs14.VP, cut=True):
         """(velx, velz, rho, rt, exner) of the baroclinic-wave case in strang_ec's layouts (eul/UMJS14.cpp:313-322): the analytic fields of
         mimsem_amd/umjs14.py at this object's quadrature points and level count, projected by init1 / init2; velz = 0.  The levels this
-        object was built with are expected to be umjs14.levels(nk, quad_coords); vp = 0 gives the steady state"""
-        uq, rho, rt, exner = umjs14.layer_fields(self.nk, self.xq, vp)
+        object was built with are expected to be umjs14.levels(nk, quad_coords); vp = 0 gives the steady state; cut=False is the wind
+        perturbation of eul/HeldSuarez.cpp, not cut beyond D0 (mimsem_amd/heldsuarez.py)"""
+        uq, rho, rt, exner = umjs14.layer_fields(self.nk, self.xq, vp, cut)
         velz = self.eng.zeros(self.eng.nEl, (self.nk - 1) * self.eng.n2e)
         return self.init1(uq), velz, self.init2(rho), self.init2(rt), self.init2(exner)
 
     # ---- the loop, the `save` branch and the restart (eul/UMJS14.cpp:334-353, eul/Euler_2.cpp:1503-1534) -------------------------------------
-    def run(self, state, nsteps, dump_every=0, outdir="output", start_step=0, on_step=None, integrator="strang_ec"):
+    def run(self, state, nsteps, dump_every=0, outdir="output", start_step=0, on_step=None, integrator="strang_ec", on_state=None):
         """the driver's loop (eul/UMJS14.cpp:347-353): step = start_step dump_every + 1 .. nsteps, each one strang_ec (or, with
         integrator="strang", strang: eul/HeldSuarez.cpp:352) whose twelve numbers go to
         outdir/energetics.dat (Energetics.write_line); on a step with step % dump_every == 0 the dump counter self.step (which starts at
-        start_step) goes up by one and dump() writes under it.  on_step(step, values), when given, is called after every step.  Returns the
-        final state"""
+        start_step) goes up by one and dump() writes under it.  on_step(step, values), when given, is called after every step;
+        on_state(step, state), when given, before it with the step's new fields (ZonalStats.sample fits as it is).  Returns the final state"""
         if integrator not in ("strang_ec", "strang"):
             raise ValueError("Euler.run: integrator is 'strang_ec' or 'strang', got %r" % (integrator,))
         one_step = getattr(self, integrator)
@@ -260,6 +261,8 @@ class Euler:
             if dump_every and step % dump_every == 0:
                 self.step += 1                                                          # :1505
                 self.dump(state, self.step, outdir)
+            if on_state is not None:
+                on_state(step, state)
             if on_step is not None:
                 on_step(step, out[5])
         return state

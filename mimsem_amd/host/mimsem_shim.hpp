@@ -703,6 +703,13 @@ struct Euler {
     void energetics_column(const double* velz, const double* rho, const double* zv, const double* linear_inv, double* out) const {
         check(mimsem_euler_energetics_column(mesh->ctx, velz, rho, zv, linear_inv, out), "Euler::energetics_column");
     }
+    // the band plan of the zonal-mean statistics: band (HOST, [nEl][mp12]) names the band in [0, nb) of every quadrature point, -1 leaves it out
+    void zonal_plan(const int* band, int nb) const { check(mimsem_zonal_plan_build(mesh->ctx, band, nb), "Euler::zonal_plan"); }
+    // acc (device, [9][nk][nb]) += the band sums of a {1, u, v, T, uu, vv, uv, vT, TT} of levels 0 .. nk-1 in one launch; packed rows velx [nk][n1],
+    // rho, rt, exner [nk][n2].  No host synchronisation.
+    void zonal_moments(int nk, const double* velx, const double* rho, const double* rt, const double* exner, double* acc) const {
+        check(mimsem_euler_zonal_moments(mesh->ctx, nk, velx, rho, rt, exner, acc), "Euler::zonal_moments");
+    }
     // HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470) of levels 0 .. nk-1 in one launch: Phi [nk][n2] from velx1, velx2 [nk][n1] and velz1, velz2 [nk-1][n2]
     void diagnose_Phi(int nk, const double* velx1, const double* velx2, long long ldu, const double* velz1, const double* velz2, long long ldz,
                       double scale, double* Phi, long long ldp) const {

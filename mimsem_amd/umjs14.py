@@ -125,42 +125,45 @@ def gc_dist(x):
     return RAD_EARTH * np.arccos(np.clip(c, -1.0, 1.0))
 
 
-def _pert(x, ki, nk, vp, fac, sign):
+def _pert(x, ki, nk, vp, fac, sign, cut=True):
+    """cut: the guard `if(gc > D0) return 0.0` (:160, :177), which eul/HeldSuarez.cpp has commented out (mimsem_amd/heldsuarez.py: cut=False)"""
     gc = gc_dist(x)
     theta = 0.5 * np.pi * gc / D0
     ct, st = np.cos(theta), np.sin(theta)
-    zero = (np.abs(gc - 0.0) < GUARD) | (np.abs(gc - RAD_EARTH * np.pi) < GUARD) | (gc > D0)
+    zero = (np.abs(gc - 0.0) < GUARD) | (np.abs(gc - RAD_EARTH * np.pi) < GUARD)
+    if cut:
+        zero = zero | (gc > D0)
     s = np.where(zero, 1.0, np.sin(gc / RAD_EARTH))
     val = sign * 16.0 * vp * z_taper(x, ki, nk) / (3.0 * np.sqrt(3.0)) * ct * ct * ct * st * fac / s
     return np.where(zero, 0.0, val)
 
 
-def u_pert(x, ki, nk=NK, vp=VP):
+def u_pert(x, ki, nk=NK, vp=VP, cut=True):
     """:147-163"""
     phi, lam = _lat(x), _lon(x)
     fac = -np.sin(PHI_C) * np.cos(phi) + np.cos(PHI_C) * np.sin(phi) * np.cos(lam - LAMBDA_C)
-    return _pert(x, ki, nk, vp, fac, -1.0)
+    return _pert(x, ki, nk, vp, fac, -1.0, cut)
 
 
-def v_pert(x, ki, nk=NK, vp=VP):
+def v_pert(x, ki, nk=NK, vp=VP, cut=True):
     """:165-180"""
     fac = np.cos(PHI_C) * np.sin(_lon(x) - LAMBDA_C)
-    return _pert(x, ki, nk, vp, fac, +1.0)
+    return _pert(x, ki, nk, vp, fac, +1.0, cut)
 
 
 def _z_mid(x, ki, nk):
     return 0.5 * (z_at_level(x, ki, nk) + z_at_level(x, ki + 1, nk))
 
 
-def u_init(x, ki, nk=NK, vp=VP):
+def u_init(x, ki, nk=NK, vp=VP, cut=True):
     """:182-188: the jet at the mean height of layer ki plus the mean of the two interface perturbations"""
     um = u_mean(x, _z_mid(x, ki, nk) + RAD_EARTH)
-    return um + 0.5 * (u_pert(x, ki, nk, vp) + u_pert(x, ki + 1, nk, vp))
+    return um + 0.5 * (u_pert(x, ki, nk, vp, cut) + u_pert(x, ki + 1, nk, vp, cut))
 
 
-def v_init(x, ki, nk=NK, vp=VP):
+def v_init(x, ki, nk=NK, vp=VP, cut=True):
     """:190-194"""
-    return 0.5 * (v_pert(x, ki, nk, vp) + v_pert(x, ki + 1, nk, vp))
+    return 0.5 * (v_pert(x, ki, nk, vp, cut) + v_pert(x, ki + 1, nk, vp, cut))
 
 
 def theta_init(x, ki, nk=NK):
@@ -199,10 +202,10 @@ def levels(nk, xq):
     return np.stack([(top - topog) * z_at_level(xq, ki, nk) / top + topog for ki in range(nk + 1)])
 
 
-def layer_fields(nk, xq, vp=VP):
+def layer_fields(nk, xq, vp=VP, cut=True):
     """what the driver hands Euler::init1 / init2 (:319-322): uq [nk, nq, 2] (u_init, v_init interleaved per point, eul/Euler_2.cpp:454-455)
     and rho, rt, exner [nk, nq] on the points xq"""
     lay = range(nk)
-    uq = np.stack([np.stack([u_init(xq, k, nk, vp), v_init(xq, k, nk, vp)], axis=-1) for k in lay])
+    uq = np.stack([np.stack([u_init(xq, k, nk, vp, cut), v_init(xq, k, nk, vp, cut)], axis=-1) for k in lay])
     return (uq, np.stack([rho_init(xq, k, nk) for k in lay]), np.stack([rt_init(xq, k, nk) for k in lay]),
             np.stack([exner_init(xq, k, nk) for k in lay]))
