@@ -1,6 +1,6 @@
 // bernoulli.inc -- mimsem_horiz_bernoulli (include/mimsem_hip.h): HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470), the horizontal
-// Bernoulli function of momentum_rhs_ec, for EVERY level in ONE launch.  Included at the end of elem_kernels.hip after energetics.inc,
-// whose lane-per-quadrature-point layout (Dims), LDS-staged edge table and interp_point it shares.
+// Bernoulli function of momentum_rhs_ec, for EVERY level in ONE launch.  Dims, interp_point and wave_lds_sync come from elem_unit.hpp; the
+// rest of the frame is spelled out here: on that header's unit layer the call measured 0.5 % slower (profiles/elem_unit_layer.txt 4).
 //
 // The reference forms Phi_k from three K (WtQUmat) and three M2h (Whmat, no vertical scaling) products:
 //   Phi_k = 1/3 (K(u1) u1 + K(u1) u2 + K(u2) u2) + 1/6 (M2h(z1) z1 + M2h(z1) z2 + M2h(z2) z2)

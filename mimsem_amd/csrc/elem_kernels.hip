@@ -19,17 +19,9 @@
 #include <hip/hip_ext.h>
 #include "ctx.hpp"
 #include "small_block_inverse.hpp"
+#include "elem_unit.hpp"      // Dims, Space, wave_lds_sync, interp_point and the unit layer of the fused passes
 
 namespace {
-
-template <int N> struct Dims {
-    static constexpr int n = N, np1 = N + 1, mp1 = N + 1, mp12 = mp1*mp1;
-    static constexpr int n0e = np1*np1, n1e = np1*N, n2e = N*N;
-    static constexpr int LPE = (mp12 <= 4) ? 4 : (mp12 <= 16 ? 16 : (mp12 <= 32 ? 32 : 64));
-    static constexpr int BLOCK = 256, EPB = BLOCK/LPE;
-};
-
-enum Space { S0 = 0, S1 = 1, S2 = 2, SN = 3, SQ = 4, SQ2 = 5 };   // SQ/SQ2: scalar / interleaved vector on the quad-point grid
 
 template <int OP> struct OpTraits;
 #define MIMSEM_TRAIT(op, in_, cf_, out_) \
@@ -228,14 +220,6 @@ __device__ __forceinline__ unsigned xcd_swizzle(unsigned bid, unsigned nb, int o
     return (bid%NX)*per + bid/NX;
 }
 
-// Lanes of one element never span wavefronts (LPE divides 64), so the LDS hand-offs between the lanes of
-// an element need only wave-level ordering, not s_barrier: LDS operations of one wave execute in order.
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // per-lane gather addresses of one space: lane q fetches DoF q (and n1e+q for 1-forms); -1 = lane idle
 template <int N, Space SP>
 __device__ __forceinline__ void dof_slots(const ElemArgs& a, int e, int q, bool act, int& s0, int& s1) {
@@ -268,31 +252,6 @@ __device__ __forceinline__ void stage_dofs(const ElemArgs& a, const double* vec,
     int s0, s1;
     dof_slots<N, SP>(a, e, q, true, s0, s1);
     dof_store<N, SP>(s0 >= 0 ? vec[s0] : 0.0, s1 >= 0 ? vec[s1] : 0.0, s0, s1, q, dst);
-}
-
-// value(s) of a staged field at quad point (qx,qy): collocated tables => short 1-D sums
-template <int N, Space SP>
-__device__ __forceinline__ void interp_point(const double* dofs, const double* sE, int q, int qx, int qy,
-                                             double& u, double& v) {
-    using D = Dims<N>;
-    u = 0.0; v = 0.0;
-    if constexpr (SP == S1) {           // Geom::interp1_l eul/Geom.cpp:342-361 with l_j(x_q) = delta_jq
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            u += dofs[j*D::np1 + qx]*sE[qy*N + j];
-            v += dofs[D::n1e + qy*N + j]*sE[qx*N + j];
-        }
-    } else if constexpr (SP == S2) {    // Geom::interp2_l :363-376
-#pragma unroll
-        for (int jy = 0; jy < N; jy++)
-#pragma unroll
-            for (int jx = 0; jx < N; jx++)
-                u += dofs[jy*N + jx]*(sE[qx*N + jx]*sE[qy*N + jy]);
-    } else if constexpr (SP == S0 || SP == SQ) {    // Geom::interp0 :328-340 (collocated) / a quad-grid value
-        u = dofs[q];
-    } else if constexpr (SP == SQ2) {
-        u = dofs[q]; v = dofs[D::mp12 + q];
-    }
 }
 
 // Work item = (element, chunk of `lch` consecutive levels).  Level-invariant data (metric, quadrature weight,
@@ -1067,52 +1026,55 @@ __global__ __launch_bounds__(256) void k_incidence(int which, int nEl, int nlev,
 // ---- field values at the quadrature points (row A7: Geom::interp0 / interp1_l / interp2_l / interp1_g / interp2_g,
 // eul/Geom.cpp:328-417).  Work item = (level, element); lane q owns quadrature point q.  Result layout per level:
 // form 0 / 2: [nEl][mp12]; form 1: [nEl][mp12][2].  `global` applies the Piola push-forward (J/det, 1/det).
+struct InterpQuadArgs {
+    ElemTables t;
+    int form, global, nlev;
+    const double* x; long long xs;
+    double* out; long long os;
+};
+
 template <int N>
-__global__ __launch_bounds__(256) void k_interp_quad(int form, int global, int nEl, int nlev,
-        const int* i0, const int* i1x, const int* i1y, const int* i2,
-        const double* __restrict__ J, const double* __restrict__ det, const double* __restrict__ E,
-        const double* __restrict__ x, long long xs, double* __restrict__ out, long long os) {
+__global__ __launch_bounds__(256) void k_interp_quad(InterpQuadArgs a) {
     using D = Dims<N>;
     constexpr int LPE = D::LPE, EPB = D::EPB;
     __shared__ double sE[D::mp1*N];
     __shared__ double s_x[EPB][2*LPE];
-    const int tid = threadIdx.x, el = tid/LPE, q = tid%LPE;
-    if (tid < D::mp1*N) sE[tid] = E[tid];
-    const long long eg = (long long)blockIdx.x*EPB + el;
-    const bool act = eg < (long long)nEl*nlev;
-    const int lev = act ? (int)(eg/nEl) : 0, e = act ? (int)(eg%nEl) : 0;
-    const double* xv = x + (size_t)lev*xs;
+    const Lane ln = lane_of_thread<N>();
+    const int el = ln.el, q = ln.q;
+    stage_edge_table<N>(sE, a.t.E);
+    const Unit un = unit_of((long long)blockIdx.x*EPB + el, a.t.nEl, a.nlev);
+    const bool act = un.act;
+    const int lev = un.lev, e = un.e;
+    const double* xv = a.x + (size_t)lev*a.xs;
     if (act) {
-        if (form == 1) {
-            if (q < D::n1e) { s_x[el][q] = xv[i1x[e*D::n1e + q]]; s_x[el][D::n1e + q] = xv[i1y[e*D::n1e + q]]; }
-        } else if (form == 2) {
-            if (q < D::n2e) s_x[el][q] = xv[i2 ? i2[e*D::n2e + q] : e*D::n2e + q];
+        if (a.form == 1) {
+            if (q < D::n1e) stage_form1<N>(form1_slots<N>(a.t, e, q), q, xv, s_x[el]);
+        } else if (a.form == 2) {
+            if (q < D::n2e) s_x[el][q] = xv[form2_slot<N>(a.t.i2, e, q)];
         } else {
-            if (q < D::n0e) s_x[el][q] = xv[i0[e*D::n0e + q]];
+            if (q < D::n0e) s_x[el][q] = xv[a.t.i0[e*D::n0e + q]];
         }
     }
     __syncthreads();
     if (!act || q >= D::mp12) return;
-    const int qx = q%D::mp1, qy = q/D::mp1;
     const size_t gq = (size_t)e*D::mp12 + q;
     double u, v;
-    if (form == 1) {
-        interp_point<N, S1>(s_x[el], sE, q, qx, qy, u, v);
-        if (global) {
-            const double* Je = J + (size_t)e*4*D::mp12;
-            const double dj = det[gq];
-            const double gu = (Je[0*D::mp12 + q]*u + Je[1*D::mp12 + q]*v)/dj;
-            const double gv = (Je[2*D::mp12 + q]*u + Je[3*D::mp12 + q]*v)/dj;
+    if (a.form == 1) {
+        interp_point<N, S1>(s_x[el], sE, q, ln.qx, ln.qy, u, v);
+        if (a.global) {
+            const PointMetric g = point_metric<N>(a.t, 0, e, q);        // (lev = 0: J and det only; nlev is not bound by the context's nk here)
+            const double gu = (g.J00*u + g.J01*v)/g.det;
+            const double gv = (g.J10*u + g.J11*v)/g.det;
             u = gu; v = gv;
         }
-        double* o = out + (size_t)lev*os + 2*gq;
+        double* o = a.out + (size_t)lev*a.os + 2*gq;
         o[0] = u; o[1] = v;
-    } else if (form == 2) {
-        interp_point<N, S2>(s_x[el], sE, q, qx, qy, u, v);
-        if (global) u /= det[gq];
-        out[(size_t)lev*os + gq] = u;
+    } else if (a.form == 2) {
+        interp_point<N, S2>(s_x[el], sE, q, ln.qx, ln.qy, u, v);
+        if (a.global) u /= point_metric<N>(a.t, 0, e, q).det;
+        a.out[(size_t)lev*a.os + gq] = u;
     } else {
-        out[(size_t)lev*os + gq] = s_x[el][q];
+        a.out[(size_t)lev*a.os + gq] = s_x[el][q];
     }
 }
 
@@ -1908,45 +1870,20 @@ int launch_incidence(mimsem_ctx* c, int which, int nlev, const double* x, long l
         if (rc) return rc;
         out = c->d_ye; os = per;
     }
-    int rc;
-    switch (es.n) {
-    case 1: rc = incidence_n<1>(c, which, nlev, x, xs, out, os); break;
-    case 2: rc = incidence_n<2>(c, which, nlev, x, xs, out, os); break;
-    case 3: rc = incidence_n<3>(c, which, nlev, x, xs, out, os); break;
-    case 4: rc = incidence_n<4>(c, which, nlev, x, xs, out, os); break;
-    case 5: rc = incidence_n<5>(c, which, nlev, x, xs, out, os); break;
-    case 6: rc = incidence_n<6>(c, which, nlev, x, xs, out, os); break;
-    case 7: rc = incidence_n<7>(c, which, nlev, x, xs, out, os); break;
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    const int rc = for_order<1, 7>(es.n, [&](auto n) { return incidence_n<decltype(n)::value>(c, which, nlev, x, xs, out, os); });
     if (rc) return rc;
     if (form != 2) return launch_gather_sum(c, form, nlev, out, os, 0, y, ys);
     return MIMSEM_OK;
 }
 
-template <int N>
-static int interp_quad_n(mimsem_ctx* c, int form, int global, int nlev, const double* x, long long xs, double* out, long long os) {
-    using D = Dims<N>;
-    const long long total = (long long)c->nEl*nlev;
-    if (total == 0) return MIMSEM_OK;
-    const unsigned grid = (unsigned)((total + D::EPB - 1)/D::EPB);
-    hipLaunchKernelGGL((k_interp_quad<N>), dim3(grid), dim3(256), 0, c->stream, form, global, c->nEl, nlev,
-                       c->d_i0, c->d_i1x, c->d_i1y, c->d_i2, c->d_J, c->d_det, c->d_E, x, xs, out, os);
-    MIMSEM_HIP_TRY(hipGetLastError());
-    return MIMSEM_OK;
-}
-
 int launch_interp_quad(mimsem_ctx* c, int form, int global, int nlev, const double* x, long long xs, double* out, long long os) {
-    switch (c->es.n) {
-    case 1: return interp_quad_n<1>(c, form, global, nlev, x, xs, out, os);
-    case 2: return interp_quad_n<2>(c, form, global, nlev, x, xs, out, os);
-    case 3: return interp_quad_n<3>(c, form, global, nlev, x, xs, out, os);
-    case 4: return interp_quad_n<4>(c, form, global, nlev, x, xs, out, os);
-    case 5: return interp_quad_n<5>(c, form, global, nlev, x, xs, out, os);
-    case 6: return interp_quad_n<6>(c, form, global, nlev, x, xs, out, os);
-    case 7: return interp_quad_n<7>(c, form, global, nlev, x, xs, out, os);
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    const long long total = (long long)c->nEl*nlev;
+    if (c->es.n < 1 || c->es.n > 7) return MIMSEM_ERR_UNSUPPORTED;
+    if (total == 0) return MIMSEM_OK;
+    InterpQuadArgs a{};
+    if (int rc = elem_tables(c, form == 0 ? NEED_I0 : 0, a.t)) return rc;       // (nEl > 0 here: a context with elements has every table)
+    a.form = form; a.global = global; a.nlev = nlev; a.x = x; a.xs = xs; a.out = out; a.os = os;
+    return for_order<1, 7>(c->es.n, [&](auto n) { return launch_units<decltype(n)::value>(c, k_interp_quad<decltype(n)::value>, total, a); });
 }
 
 template <int N>
@@ -1985,16 +1922,7 @@ int launch_sw_operator(mimsem_ctx* c, int nlev, double a, double grav, double H,
     const double* u = x; const double* h = x + c->n1;
     double* yh = y + c->n1;
     const double ag = a*grav, aH = a*H;
-    switch (es.n) {
-    case 1: rc = sw_operator_n<1>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    case 2: rc = sw_operator_n<2>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    case 3: rc = sw_operator_n<3>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    case 4: rc = sw_operator_n<4>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    case 5: rc = sw_operator_n<5>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    case 6: rc = sw_operator_n<6>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    case 7: rc = sw_operator_n<7>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); break;
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    rc = for_order<1, 7>(es.n, [&](auto n) { return sw_operator_n<decltype(n)::value>(c, nlev, a, ag, aH, f0, f0s, u, xs, h, xs, c->d_ye, per, yh, ys); });
     if (rc) return rc;
     return launch_gather_sum(c, 1, nlev, c->d_ye, per, 0, y, ys);
 }

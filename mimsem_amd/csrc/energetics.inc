@@ -1,6 +1,6 @@
 // energetics.inc -- mimsem_euler_energetics_horiz (include/mimsem_hip.h): the four horizontal integrals of Euler::diagnostics
-// (eul/Euler_2.cpp:600-744) over all levels in ONE element pass plus a small fixed-order final pass.  Included at the end of
-// elem_kernels.hip, whose lane-per-quadrature-point layout (Dims), LDS-staged edge table and interp_point it shares.
+// (eul/Euler_2.cpp:600-744) over all levels in ONE element pass plus a small fixed-order final pass.  A fused element pass on the
+// unit layer of elem_unit.hpp, as a fixed-stride walk.
 //
 //   keh  = 1/2 sum_k velx_k . F(rho_k, k, vert) velx_k / SCALE      (:630-636; coefficients Uhmat::assemble eul/Assembly.cpp:432-448)
 //   ie   = CV/CP sum_k rt_k . M2(k, vert) exner_k / SCALE           (:667-673; Wmat::assemble eul/Assembly.cpp:347-353)
@@ -28,9 +28,8 @@ namespace {
 constexpr int EN_MAX_BLOCKS = 2048;      // 8 workgroups of 256 on each of the 256 CUs; more units than that: blocks take several
 
 struct EnergeticsArgs {
-    int nEl, nlev;
-    const int *i1x, *i1y, *i2;
-    const double *J, *det, *tI, *E, *w;
+    ElemTables t;
+    int nlev;
     const double* u; long long us;
     const double* rho; long long rs;
     const double* rt; long long ts;
@@ -53,47 +52,40 @@ __global__ __launch_bounds__(256) void k_energetics_horiz(EnergeticsArgs a) {
     __shared__ double s_u[EPB][2*LPE];
     __shared__ double s_r[EPB][LPE], s_t[EPB][LPE], s_p[EPB][LPE], s_h[EPB][LPE];
     __shared__ double red[4][4];
-    const int tid = threadIdx.x, el = tid/LPE, q = tid%LPE;
-    const int qx = q%D::mp1, qy = q/D::mp1;
-    if (tid < D::mp1*N) sE[tid] = a.E[tid];
-    const double Q = q < D::mp12 ? a.w[qx]*a.w[qy] : 0.0;
-    const long long total = (long long)a.nEl*a.nlev;
-    const size_t lstride = (size_t)a.nEl*D::mp12;
+    const Lane ln = lane_of_thread<N>();
+    const int tid = threadIdx.x, el = ln.el, q = ln.q, qx = ln.qx, qy = ln.qy;
+    stage_edge_table<N>(sE, a.t.E);
+    const double Q = q < D::mp12 ? a.t.w[qx]*a.t.w[qy] : 0.0;        // once per lane, not per unit of the walk (PointMetric::Q is not used)
+    const long long total = (long long)a.t.nEl*a.nlev;
     double keh = 0.0, ie = 0.0, en = 0.0, ms = 0.0;
     __syncthreads();                     // sE (the only block-level barrier of the loop: an element's lanes share a wave)
     for (long long base = (long long)blockIdx.x*EPB; base < total; base += (long long)gridDim.x*EPB) {      // (block-uniform trip count)
-        const long long eg = base + el;
-        const bool act = eg < total;
-        const int lev = act ? (int)(eg/a.nEl) : 0, e = act ? (int)(eg%a.nEl) : 0;
+        const Unit un = unit_of(base + el, a.t.nEl, a.nlev);
+        const bool act = un.act;
+        const int lev = un.lev, e = un.e;
         if (act) {
-            if (q < D::n1e) {
-                const double* uv = a.u + (size_t)lev*a.us;
-                s_u[el][q] = uv[a.i1x[e*D::n1e + q]]; s_u[el][D::n1e + q] = uv[a.i1y[e*D::n1e + q]];
-            }
+            if (q < D::n1e) stage_form1<N>(form1_slots<N>(a.t, e, q), q, a.u + (size_t)lev*a.us, s_u[el]);
             if (q < D::n2e) {
-                const size_t s = a.i2 ? (size_t)a.i2[e*D::n2e + q] : (size_t)e*D::n2e + q;
+                const size_t s = form2_slot<N>(a.t.i2, e, q);
                 s_r[el][q] = a.rho[(size_t)lev*a.rs + s]; s_t[el][q] = a.rt[(size_t)lev*a.ts + s];
                 s_p[el][q] = a.ex[(size_t)lev*a.es + s]; s_h[el][q] = a.th[(size_t)lev*a.hs + s];
             }
         }
         wave_lds_sync();
         if (act && q < D::mp12) {
-            const size_t gq = (size_t)e*D::mp12 + q;
-            const double* Je = a.J + (size_t)e*4*D::mp12;
-            const double J00 = Je[0*D::mp12 + q], J01 = Je[1*D::mp12 + q], J10 = Je[2*D::mp12 + q], J11 = Je[3*D::mp12 + q];
-            const double det = a.det[gq], tI = a.tI[(size_t)lev*lstride + gq];
+            const PointMetric g = point_metric<N>(a.t, lev, e, q);
             double u, v, r, T, P, h, dmy;
             interp_point<N, S1>(s_u[el], sE, q, qx, qy, u, v);
             interp_point<N, S2>(s_r[el], sE, q, qx, qy, r, dmy);
             interp_point<N, S2>(s_t[el], sE, q, qx, qy, T, dmy);
             interp_point<N, S2>(s_p[el], sE, q, qx, qy, P, dmy);
             interp_point<N, S2>(s_h[el], sE, q, qx, qy, h, dmy);
-            const double sd = 1.0/det;
+            const double det = g.det, tI = g.tI, sd = 1.0/det;
             const double rq = r/det;                                  // interp2_g
             const double hi = rq*tI;
-            const double caa = hi*(J00*J00 + J10*J10)*Q*sd*tI;        // Uhmat::assemble, vert_scale
-            const double cab = hi*(J00*J01 + J10*J11)*Q*sd*tI;
-            const double cbb = hi*(J01*J01 + J11*J11)*Q*sd*tI;
+            const double caa = hi*(g.J00*g.J00 + g.J10*g.J10)*Q*sd*tI;        // Uhmat::assemble, vert_scale
+            const double cab = hi*(g.J00*g.J01 + g.J10*g.J11)*Q*sd*tI;
+            const double cbb = hi*(g.J01*g.J01 + g.J11*g.J11)*Q*sd*tI;
             const double c2 = Q*sd*tI;                                // Wmat::assemble, vert_scale
             keh += u*(caa*u + cab*v) + v*(cab*u + cbb*v);
             ie += T*(c2*P);
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(256) void k_energetics_final(int nb, const double* 
 template <int N>
 int energetics_horiz_n(mimsem_ctx* c, EnergeticsArgs& a, double* out) {
     using D = Dims<N>;
-    const long long total = (long long)a.nEl*a.nlev;
+    const long long total = (long long)a.t.nEl*a.nlev;
     const int nb = (int)std::max<long long>(1, std::min<long long>(EN_MAX_BLOCKS, (total + D::EPB - 1)/D::EPB));
     const int rc = c->ensure_kry((long long)nb*4);                    // (grows outside a capture only: MIMSEM_ERR_STATE inside one)
     if (rc) return rc;
@@ -170,10 +162,9 @@ __global__ __launch_bounds__(64) void k_energetics_column(EnColumnArgs a) {
     constexpr int LPE = D::LPE, EPB = 64/LPE, n2 = D::n2e, nn = n2*n2;
     __shared__ double sE[D::mp1*N];
     __shared__ double s_r[EPB][LPE], s_v[EPB][LPE], s_t[EPB][LPE], s_b[EPB][LPE];
-    const int tid = threadIdx.x, el = tid/LPE, q = tid%LPE;
-    const int qx = q%D::mp1, qy = q/D::mp1;
-    const int jx = q%N, jy = q/N;                                     // (as a DoF lane, q < n2e)
-    if (tid < D::mp1*N) sE[tid] = a.E[tid];
+    const Lane ln = lane_of_thread<N>();
+    const int tid = threadIdx.x, el = ln.el, q = ln.q, qx = ln.qx, qy = ln.qy;
+    stage_edge_table<N>(sE, a.E);
     const double Q = q < D::mp12 ? a.w[qx]*a.w[qy] : 0.0;
     const int nk = a.nk, ni = a.nk - 1;
     double kev = 0.0, k2p = 0.0, p2k = 0.0, pe = 0.0;
@@ -206,14 +197,7 @@ __global__ __launch_bounds__(64) void k_energetics_column(EnColumnArgs a) {
             }
             wave_lds_sync();             // s_r, s_v read; s_t stored
             if (k > 0) {
-                if (dof) {
-                    double b = 0.0;
-#pragma unroll
-                    for (int py = 0; py < D::mp1; py++)
-#pragma unroll
-                        for (int px = 0; px < D::mp1; px++) b += (sE[px*N + jx]*sE[py*N + jy])*s_t[el][py*D::mp1 + px];
-                    s_b[el][q] = b;
-                }
+                if (dof) s_b[el][q] = project2<N>(sE, s_t[el], q);
                 wave_lds_sync();
                 if (dof) {
                     const double* Ar = Ae + (size_t)(k - 1)*nn;
@@ -266,13 +250,7 @@ extern "C" int mimsem_euler_energetics_column(mimsem_ctx* c, const double* velz,
     a.nEl = c->nEl; a.nk = c->nk;
     a.det = c->d_det; a.E = c->d_E; a.w = c->d_w;
     a.velz = velz; a.rho = rho; a.zv = zv; a.Ainv = linear_inv;
-    switch (c->es.n) {
-    case 1: return energetics_column_n<1>(c, a, out);
-    case 2: return energetics_column_n<2>(c, a, out);
-    case 3: return energetics_column_n<3>(c, a, out);
-    case 4: return energetics_column_n<4>(c, a, out);
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    return for_order<1, 4>(c->es.n, [&](auto n) { return energetics_column_n<decltype(n)::value>(c, a, out); });
 }
 
 extern "C" int mimsem_euler_energetics_horiz(mimsem_ctx* c, int nlev, const double* velx, long long ldu, const double* rho, long long ldr,
@@ -280,20 +258,9 @@ extern "C" int mimsem_euler_energetics_horiz(mimsem_ctx* c, int nlev, const doub
                                              const double* theta, long long ldth, double* out) {
     if (!c || !velx || !rho || !rt || !exner || !theta || !out) return MIMSEM_ERR_ARG;
     if (nlev < 1 || nlev > c->nk || ldu < 0 || ldr < 0 || ldt < 0 || lde < 0 || ldth < 0) return MIMSEM_ERR_ARG;
-    if (!c->d_J || !c->d_det || !c->d_tI || !c->d_E || !c->d_w || !c->d_i1x || !c->d_i1y) return MIMSEM_ERR_STATE;
     EnergeticsArgs a{};
-    a.nEl = c->nEl; a.nlev = nlev;
-    a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2;
-    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.E = c->d_E; a.w = c->d_w;
+    if (int rc = elem_tables(c, 0, a.t)) return rc;
+    a.nlev = nlev;
     a.u = velx; a.us = ldu; a.rho = rho; a.rs = ldr; a.rt = rt; a.ts = ldt; a.ex = exner; a.es = lde; a.th = theta; a.hs = ldth;
-    switch (c->es.n) {
-    case 1: return energetics_horiz_n<1>(c, a, out);
-    case 2: return energetics_horiz_n<2>(c, a, out);
-    case 3: return energetics_horiz_n<3>(c, a, out);
-    case 4: return energetics_horiz_n<4>(c, a, out);
-    case 5: return energetics_horiz_n<5>(c, a, out);
-    case 6: return energetics_horiz_n<6>(c, a, out);
-    case 7: return energetics_horiz_n<7>(c, a, out);
-    default: return MIMSEM_ERR_UNSUPPORTED;
-    }
+    return for_order<1, 7>(c->es.n, [&](auto n) { return energetics_horiz_n<decltype(n)::value>(c, a, out); });
 }

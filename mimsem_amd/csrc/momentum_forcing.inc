@@ -1,7 +1,6 @@
 // momentum_forcing.inc -- mimsem_horiz_momentum_forcing (include/mimsem_hip.h): the element-local forcing of HorizSolve::momentum_rhs
-// (eul/HorizSolve.cpp:496-635, box/HorizSolve.cpp:412-526) for EVERY level in one element pass plus the 1-form gather.  Included at the end
-// of elem_kernels.hip after flux_rhs.inc, whose lane-per-quadrature-point layout (Dims), LDS-staged edge table, interp_point and
-// launch_gather_sum it shares.
+// (eul/HorizSolve.cpp:496-635, box/HorizSolve.cpp:412-526) for EVERY level in one element pass plus the 1-form gather.  A fused
+// element pass on the unit layer of elem_unit.hpp.
 //
 // The reference adds three assembled operators into the level's right-hand side:
 //   out_k (+)= R(q_k; level k, scale) a_k                              RotMat::assemble  (eul/Assembly.cpp:1051-1065, box/Assembly.cpp:826-882)
@@ -21,8 +20,7 @@
 // out with MIMSEM_FLAG_ACCUM.  Two launches, no atomics, a fixed summation order: two calls give the same bits.
 //
 // Each of the pairs (q, a), (th, g), (dz, v) may be absent (both NULL): a kernel-argument branch, uniform over the grid, skips its loads
-// and its integrand.  The loads of an inactive lane (a unit past the end, a lane past the element's DoFs or points) and of the interfaces
-// -1 and nk-1 sit inside their branch: nothing is loaded from a clamped address and thrown away.
+// and its integrand; the loads of the interfaces -1 and nk-1 sit inside their branch as well.
 //
 // Work item = (level, element) as k_horiz_flux_rhs numbers them; lane q owns quadrature point q and, for q < n1e, the x edge q and the
 // y edge q of the element.  Byte model of the element pass with all three terms: a unit reads a, g and the dz of its (at most) two
@@ -33,9 +31,8 @@
 namespace {
 
 struct MomForcingArgs {
-    int nEl, nk, vert;
-    const int *i0, *i1x, *i1y, *i2;
-    const double *J, *det, *tI, *E, *w;
+    ElemTables t;
+    int nk, vert;
     const double *q, *a, *th, *g, *dz, *v;
     long long n0, n1, n2;                                   // packed rows: the row strides are the context's vector lengths
     double scale;
@@ -49,38 +46,34 @@ __global__ __launch_bounds__(256) void k_horiz_momentum_forcing(MomForcingArgs a
     __shared__ double sE[D::mp1*N];
     __shared__ double s_a[EPB][2*LPE], s_g[EPB][2*LPE], s_z[2][EPB][2*LPE];
     __shared__ double s_h[EPB][LPE], s_w[2][EPB][LPE], s_x[EPB][LPE], s_y[EPB][LPE];
-    const int tid = threadIdx.x, el = tid/LPE, q = tid%LPE;
-    const int qx = q%D::mp1, qy = q/D::mp1;
-    if (tid < D::mp1*N) sE[tid] = a.E[tid];
-    const long long total = (long long)a.nEl*a.nk;
-    const long long eg = (long long)blockIdx.x*EPB + el;
-    const bool act = eg < total;
-    const int lev = act ? (int)(eg/a.nEl) : 0, e = act ? (int)(eg%a.nEl) : 0;
+    const Lane ln = lane_of_thread<N>();
+    const int el = ln.el, q = ln.q, qx = ln.qx, qy = ln.qy;
+    stage_edge_table<N>(sE, a.t.E);
+    const Unit un = unit_of((long long)blockIdx.x*EPB + el, a.t.nEl, a.nk);
+    const bool act = un.act;
+    const int lev = un.lev, e = un.e;
     const bool rot = a.q != nullptr, pgf = a.th != nullptr, vor = a.dz != nullptr;          // (uniform: kernel arguments)
     const bool lo = vor && lev > 0, hi = vor && lev < a.nk - 1;                             // the interfaces lev-1 and lev of this level
     if (act) {
         if (q < D::n1e) {
-            const int ix = a.i1x[e*D::n1e + q], iy = a.i1y[e*D::n1e + q];
-            if (rot) { const double* r = a.a + (size_t)lev*a.n1; s_a[el][q] = r[ix]; s_a[el][D::n1e + q] = r[iy]; }
-            if (pgf) { const double* r = a.g + (size_t)lev*a.n1; s_g[el][q] = r[ix]; s_g[el][D::n1e + q] = r[iy]; }
-            if (lo) { const double* r = a.dz + (size_t)(lev - 1)*a.n1; s_z[0][el][q] = r[ix]; s_z[0][el][D::n1e + q] = r[iy]; }
-            if (hi) { const double* r = a.dz + (size_t)lev*a.n1; s_z[1][el][q] = r[ix]; s_z[1][el][D::n1e + q] = r[iy]; }
+            const int2 s1 = form1_slots<N>(a.t, e, q);
+            if (rot) stage_form1<N>(s1, q, a.a + (size_t)lev*a.n1, s_a[el]);
+            if (pgf) stage_form1<N>(s1, q, a.g + (size_t)lev*a.n1, s_g[el]);
+            if (lo) stage_form1<N>(s1, q, a.dz + (size_t)(lev - 1)*a.n1, s_z[0][el]);
+            if (hi) stage_form1<N>(s1, q, a.dz + (size_t)lev*a.n1, s_z[1][el]);
         }
         if (q < D::n2e && (pgf || vor)) {
-            const size_t slot = a.i2 ? (size_t)a.i2[e*D::n2e + q] : (size_t)e*D::n2e + q;
+            const size_t slot = form2_slot<N>(a.t.i2, e, q);
             if (pgf) s_h[el][q] = a.th[(size_t)lev*a.n2 + slot];
             if (lo) s_w[0][el][q] = a.v[(size_t)(lev - 1)*a.n2 + slot];
             if (hi) s_w[1][el][q] = a.v[(size_t)lev*a.n2 + slot];
         }
     }
-    __syncthreads();                     // sE; the unit's rows (an element's lanes share a wave, but sE is the block's)
+    __syncthreads();                     // sE; the unit's rows
     if (act && q < D::mp12) {
-        const size_t gq = (size_t)e*D::mp12 + q;
-        const double* Je = a.J + (size_t)e*4*D::mp12;
-        const double J00 = Je[0*D::mp12 + q], J01 = Je[1*D::mp12 + q], J10 = Je[2*D::mp12 + q], J11 = Je[3*D::mp12 + q];
-        const double det = a.det[gq], tI = a.tI[(size_t)lev*((size_t)a.nEl*D::mp12) + gq];
-        const double Q = a.w[qx]*a.w[qy];
-        const double sd = 1.0/det, m = (a.scale*Q)*sd;
+        const PointMetric p = point_metric<N>(a.t, lev, e, q);
+        const double tI = p.tI;
+        const double sd = 1.0/p.det, m = (a.scale*p.Q)*sd;
         double U = 0.0, V = 0.0;                                                   // the part that goes through G = J^T J
         double cx = 0.0, cy = 0.0;
         double u, v, h, dmy;
@@ -104,14 +97,14 @@ __global__ __launch_bounds__(256) void k_horiz_momentum_forcing(MomForcingArgs a
             U += s*u; V += s*v;
         }
         if (pgf || vor) {
-            const double Gaa = J00*J00 + J10*J10, Gab = J00*J01 + J10*J11, Gbb = J01*J01 + J11*J11;
+            const double Gaa = p.J00*p.J00 + p.J10*p.J10, Gab = p.J00*p.J01 + p.J10*p.J11, Gbb = p.J01*p.J01 + p.J11*p.J11;
             cx = Gaa*U + Gab*V;
             cy = Gab*U + Gbb*V;
         }
         if (rot) {
             interp_point<N, S1>(s_a[el], sE, q, qx, qy, u, v);
-            const double vort = a.q[(size_t)lev*a.n0 + a.i0[e*D::n0e + q]];       // interp0 at a collocated node (n0e == mp12)
-            const double r = (vort*(J00*J11 - J01*J10))*(m*tI*tI);
+            const double vort = a.q[(size_t)lev*a.n0 + a.t.i0[e*D::n0e + q]];     // interp0 at a collocated node (n0e == mp12)
+            const double r = (vort*(p.J00*p.J11 - p.J01*p.J10))*(m*tI*tI);
             cx -= r*v;
             cy += r*u;
         }
@@ -120,26 +113,11 @@ __global__ __launch_bounds__(256) void k_horiz_momentum_forcing(MomForcingArgs a
     }
     wave_lds_sync();
     if (act && q < D::n1e) {
-        const int ixx = q%D::np1, iyx = q/D::np1;     // x-normal edge: node in x, edge fn in y
-        const int ixy = q%N,      iyy = q/N;          // y-normal edge: edge fn in x, node in y
-        double yx = 0.0, yy = 0.0;
-#pragma unroll
-        for (int k = 0; k < D::mp1; k++) {
-            yx += sE[k*N + iyx]*s_x[el][k*D::mp1 + ixx];
-            yy += sE[k*N + ixy]*s_y[el][iyy*D::mp1 + k];
-        }
-        double* o = a.ye + (size_t)lev*a.yes + (size_t)e*2*D::n1e;                // (lev, e) < (nk, nEl): inside the nk * yes doubles ensured
+        double yx, yy;
+        project1<N>(sE, s_x[el], s_y[el], q, yx, yy);
+        double* o = a.ye + (size_t)lev*a.yes + (size_t)e*2*D::n1e;                // inside the nk * yes doubles ensured
         o[q] = yx; o[D::n1e + q] = yy;
     }
-}
-
-template <int N>
-int horiz_momentum_forcing_n(mimsem_ctx* c, const MomForcingArgs& a) {
-    constexpr int EPB = Dims<N>::EPB;
-    const long long total = (long long)a.nEl*a.nk;
-    hipLaunchKernelGGL((k_horiz_momentum_forcing<N>), dim3((unsigned)((total + EPB - 1)/EPB)), dim3(256), 0, c->stream, a);
-    MIMSEM_HIP_TRY(hipGetLastError());
-    return MIMSEM_OK;
 }
 
 }  // namespace
@@ -152,7 +130,8 @@ extern "C" int mimsem_horiz_momentum_forcing(mimsem_ctx* c, int nk, unsigned fla
     if (nk == 1 && dz) return MIMSEM_ERR_ARG;                                      // one level has no interface
     if (out == q || out == a || out == th || out == g || out == dz || out == v) return MIMSEM_ERR_ARG;
     if (c->es.n < 1 || c->es.n > 7) return MIMSEM_ERR_UNSUPPORTED;
-    if (!c->d_J || !c->d_det || !c->d_tI || !c->d_E || !c->d_w || !c->d_i0 || !c->d_i1x || !c->d_i1y || !c->d_g1) return MIMSEM_ERR_STATE;
+    MomForcingArgs p{};
+    if (int rc = elem_tables(c, NEED_I0 | NEED_G1, p.t)) return rc;
     if (c->nEl == 0) return MIMSEM_OK;
     const int accum = (flags & MIMSEM_FLAG_ACCUM) ? 1 : 0;
     if (!q && !th && !dz) {                                                        // nothing to add: out = 0 unless it accumulates
@@ -162,22 +141,11 @@ extern "C" int mimsem_horiz_momentum_forcing(mimsem_ctx* c, int nk, unsigned fla
     const long long per = (long long)c->nEl*2*c->es.n1e;
     int rc = c->ensure_ye(per*nk);                                       // (grows outside a capture only: MIMSEM_ERR_STATE inside one)
     if (rc) return rc;
-    MomForcingArgs p{};
-    p.nEl = c->nEl; p.nk = nk; p.vert = (flags & MIMSEM_FLAG_VERT) ? 1 : 0;
-    p.i0 = c->d_i0; p.i1x = c->d_i1x; p.i1y = c->d_i1y; p.i2 = c->d_i2;
-    p.J = c->d_J; p.det = c->d_det; p.tI = c->d_tI; p.E = c->d_E; p.w = c->d_w;
+    p.nk = nk; p.vert = (flags & MIMSEM_FLAG_VERT) ? 1 : 0;
     p.q = q; p.a = a; p.th = th; p.g = g; p.dz = dz; p.v = v;
     p.n0 = c->n0; p.n1 = c->n1; p.n2 = c->n2;
     p.scale = scale; p.ye = c->d_ye; p.yes = per;
-    switch (c->es.n) {
-    case 1: rc = horiz_momentum_forcing_n<1>(c, p); break;
-    case 2: rc = horiz_momentum_forcing_n<2>(c, p); break;
-    case 3: rc = horiz_momentum_forcing_n<3>(c, p); break;
-    case 4: rc = horiz_momentum_forcing_n<4>(c, p); break;
-    case 5: rc = horiz_momentum_forcing_n<5>(c, p); break;
-    case 6: rc = horiz_momentum_forcing_n<6>(c, p); break;
-    default: rc = horiz_momentum_forcing_n<7>(c, p); break;
-    }
+    rc = for_order<1, 7>(c->es.n, [&](auto n) { return launch_units<decltype(n)::value>(c, k_horiz_momentum_forcing<decltype(n)::value>, (long long)p.t.nEl*p.nk, p); });
     if (rc) return rc;
     return launch_gather_sum(c, 1, nk, c->d_ye, per, accum, out, c->n1);
 }

@@ -1,6 +1,6 @@
 // zonal_stats.inc -- mimsem_zonal_plan_build / mimsem_euler_zonal_moments (include/mimsem_hip.h): the binned first and second moments of
 // the physical fields of a 3-D state, level by level, in ONE launch that stays on the device -- what a Held-Suarez run (eul/HeldSuarez.cpp)
-// is averaged into.  Included at the end of elem_kernels.hip, whose Dims, edge table and en_wave_sum (energetics.inc) it shares.
+// is averaged into.  Of the unit layer of elem_unit.hpp it takes the tables, the metric and the dispatch: its work mapping is its own.
 //
 // Fields at the quadrature point q of element e on level k, those of Geom::write1 / write2(vert_scale = true) (eul/Geom.cpp:474-631) as
 // Euler.quad_fields states them: with (ul, vl), rl, hl, pl the LOCAL interpolants of velx_k, rho_k, rt_k, exner_k (interp_point),
@@ -31,9 +31,8 @@ constexpr int ZN_MOM = 9;
 constexpr double ZN_CP = 1004.5;         // eul/Euler_2.cpp:29
 
 struct ZonalArgs {
-    int nEl, nlev, nb;
-    const int *i1x, *i1y, *i2;
-    const double *J, *det, *tI, *E, *w;
+    ElemTables t;
+    int nlev, nb;
     const double *u, *rho, *rt, *ex;
     long long n1, n2;                    // packed rows: the row strides are the context's vector lengths
     const int *band, *off, *pt;          // plan: [nne] band of the work item, [nne + 1] offsets, [npts] e mp12 + q
@@ -46,14 +45,13 @@ __global__ __launch_bounds__(256) void k_zonal_moments(ZonalArgs a) {
     __shared__ double sE[D::mp1*N], sW[D::mp1];
     __shared__ double red[4][ZN_MOM];
     const int tid = threadIdx.x, lev = blockIdx.y;
-    if (tid < D::mp1*N) sE[tid] = a.E[tid];
-    if (tid < D::mp1) sW[tid] = a.w[tid];
+    stage_edge_table<N>(sE, a.t.E);
+    if (tid < D::mp1) sW[tid] = a.t.w[tid];
     const int beg = a.off[blockIdx.x], end = a.off[blockIdx.x + 1];              // (blockIdx.x < nne: inside the nne + 1 offsets)
     const double* uv = a.u + (size_t)lev*a.n1;
     const double* rho = a.rho + (size_t)lev*a.n2;
     const double* rt = a.rt + (size_t)lev*a.n2;
     const double* ex = a.ex + (size_t)lev*a.n2;
-    const double* tIl = a.tI + (size_t)lev*((size_t)a.nEl*D::mp12);
     double s[ZN_MOM];
 #pragma unroll
     for (int m = 0; m < ZN_MOM; m++) s[m] = 0.0;
@@ -61,9 +59,9 @@ __global__ __launch_bounds__(256) void k_zonal_moments(ZonalArgs a) {
     for (int i = beg + tid; i < end; i += 256) {                                 // the lane's points, in list order
         const int p = a.pt[i], e = p/D::mp12, q = p - e*D::mp12;                 // (validated by the plan: e < nEl)
         const int qx = q%D::mp1, qy = q/D::mp1;
-        const int* ix = a.i1x + (size_t)e*D::n1e;
-        const int* iy = a.i1y + (size_t)e*D::n1e;
-        double ul = 0.0, vl = 0.0;       // interp_point<N, S1>
+        const int* ix = a.t.i1x + (size_t)e*D::n1e;
+        const int* iy = a.t.i1y + (size_t)e*D::n1e;
+        double ul = 0.0, vl = 0.0;       // interp_point<N, S1>, the DoFs straight from global memory
 #pragma unroll
         for (int j = 0; j < N; j++) {
             ul += uv[ix[j*D::np1 + qx]]*sE[qy*N + j];
@@ -74,14 +72,13 @@ __global__ __launch_bounds__(256) void k_zonal_moments(ZonalArgs a) {
         for (int jy = 0; jy < N; jy++)
 #pragma unroll
             for (int jx = 0; jx < N; jx++) {
-                const size_t slot = a.i2 ? (size_t)a.i2[(size_t)e*D::n2e + jy*N + jx] : (size_t)e*D::n2e + jy*N + jx;
+                const size_t slot = form2_slot<N>(a.t.i2, e, jy*N + jx);
                 const double w = sE[qx*N + jx]*sE[qy*N + jy];
                 rl += rho[slot]*w; hl += rt[slot]*w; pl += ex[slot]*w;
             }
-        const double* Je = a.J + (size_t)e*4*D::mp12;
-        const double J00 = Je[0*D::mp12 + q], J01 = Je[1*D::mp12 + q], J10 = Je[2*D::mp12 + q], J11 = Je[3*D::mp12 + q];
-        const double det = a.det[p], t = tIl[p];
-        const double u = ((J00*ul + J01*vl)/det)*t, v = ((J10*ul + J11*vl)/det)*t;
+        const PointMetric g = point_metric<N>(a.t, lev, e, q);
+        const double det = g.det, t = g.tI;                                       // (the weight comes from sW: g.Q is not used)
+        const double u = ((g.J00*ul + g.J01*vl)/det)*t, v = ((g.J10*ul + g.J11*vl)/det)*t;
         const double r = (rl/det)*t, H = (hl/det)*t, P = (pl/det)*t;
         const double T = r > 0.0 ? (H*P)/(ZN_CP*r) : __builtin_nan("");           // r <= 0 or NaN: the entry says so
         const double wa = (sW[qx]*sW[qy])*det;
@@ -99,13 +96,6 @@ __global__ __launch_bounds__(256) void k_zonal_moments(ZonalArgs a) {
         double* o = a.acc + ((size_t)tid*a.nlev + lev)*a.nb + a.band[blockIdx.x];
         *o = *o + ((red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]));
     }
-}
-
-template <int N>
-int zonal_moments_n(mimsem_ctx* c, const ZonalArgs& a) {
-    hipLaunchKernelGGL((k_zonal_moments<N>), dim3((unsigned)c->zon.nne, (unsigned)a.nlev), dim3(256), 0, c->stream, a);
-    MIMSEM_HIP_TRY(hipGetLastError());
-    return MIMSEM_OK;
 }
 
 bool zonal_overlap(const double* a, size_t na, const double* b, size_t nb) {
@@ -158,22 +148,16 @@ extern "C" int mimsem_euler_zonal_moments(mimsem_ctx* c, int nlev, const double*
     if (zonal_overlap(acc, na, velx, n1) || zonal_overlap(acc, na, rho, n2) || zonal_overlap(acc, na, rt, n2) || zonal_overlap(acc, na, exner, n2))
         return MIMSEM_ERR_ARG;
     if (c->es.n < 1 || c->es.n > 7) return MIMSEM_ERR_UNSUPPORTED;
-    if (!c->d_J || !c->d_det || !c->d_tI || !c->d_E || !c->d_w || !c->d_i1x || !c->d_i1y) return MIMSEM_ERR_STATE;
-    if (c->zon.nne == 0) return MIMSEM_OK;                                        // every point left out: acc + 0.0
     ZonalArgs a{};
-    a.nEl = c->nEl; a.nlev = nlev; a.nb = c->zon.nb;
-    a.i1x = c->d_i1x; a.i1y = c->d_i1y; a.i2 = c->d_i2;
-    a.J = c->d_J; a.det = c->d_det; a.tI = c->d_tI; a.E = c->d_E; a.w = c->d_w;
+    if (int rc = elem_tables(c, 0, a.t)) return rc;
+    if (c->zon.nne == 0) return MIMSEM_OK;                                        // every point left out: acc + 0.0
+    a.nlev = nlev; a.nb = c->zon.nb;
     a.u = velx; a.rho = rho; a.rt = rt; a.ex = exner; a.n1 = c->n1; a.n2 = c->n2;
     a.band = c->zon.band; a.off = c->zon.off; a.pt = c->zon.pt;
     a.acc = acc;
-    switch (c->es.n) {
-    case 1: return zonal_moments_n<1>(c, a);
-    case 2: return zonal_moments_n<2>(c, a);
-    case 3: return zonal_moments_n<3>(c, a);
-    case 4: return zonal_moments_n<4>(c, a);
-    case 5: return zonal_moments_n<5>(c, a);
-    case 6: return zonal_moments_n<6>(c, a);
-    default: return zonal_moments_n<7>(c, a);
-    }
+    return for_order<1, 7>(c->es.n, [&](auto n) {             // work item = (non-empty band, level)
+        hipLaunchKernelGGL((k_zonal_moments<decltype(n)::value>), dim3((unsigned)c->zon.nne, (unsigned)nlev), dim3(256), 0, c->stream, a);
+        MIMSEM_HIP_TRY(hipGetLastError());
+        return (int)MIMSEM_OK;
+    });
 }

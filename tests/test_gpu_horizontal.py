@@ -3,7 +3,7 @@ Bar (BASELINE.json north_star): fields within 1e-10 relative L2; integer topolog
 import numpy as np
 import pytest
 
-from tests.helpers import SCALE, make_patch, rel_l2
+from tests.helpers import SCALE, make_patch, rel_l2, z_levels
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
@@ -18,6 +18,29 @@ def setup(request, oracle):
     cs, topo, geom, P, rng = make_patch(oracle, pn, ne, nprocs, pi, nk=3, seed=pn * 100 + pi)
     eng = Engine(DeviceMesh([topo], [geom], nk=3, numbering="local"))
     return eng, P, rng
+
+
+@pytest.fixture(scope="module")
+def order_one_box(oracle):
+    """order 1 (the sphere has no coordinates below order 2, so `setup` cannot reach it) on a 6 x 6 periodic box whose metric is replaced by
+    a sheared one that varies from point to point, J = [[2.5, 0.7], [-0.4, 2.0]] (1 + 0.1 noise), det = J00 J11 - J01 J10: every entry of
+    the push-forward counts.  The engine and the oracle get the same arrays"""
+    from mimsem_amd.device import DeviceMesh, Engine
+    from mimsem_amd.geom import BoxGeom
+    from mimsem_amd.mesh import PeriodicBox, box_coords
+    from mimsem_amd.topo import Topo
+    pn, ne, nk, lx = 1, 6, 2, 30.0
+    bx = PeriodicBox(pn, ne, 1)
+    topo = Topo(bx, 0, nk)
+    geom = BoxGeom(topo, bx, box_coords(pn, ne, lx), nk, lx)
+    r = np.random.default_rng(36)
+    geom.set_levels(z_levels(nk, geom.n0, r))
+    geom.J[...] = np.array([2.5, 0.7, -0.4, 2.0]) * (1.0 + 0.1 * r.uniform(-1.0, 1.0, geom.J.shape))
+    geom.det[...] = geom.J[..., 0] * geom.J[..., 3] - geom.J[..., 1] * geom.J[..., 2]
+    P = oracle.Patch(pn, pn, bx.nel, nk)
+    P.set_metric(geom.det, geom.J)
+    P.set_levels(geom.levs)
+    return Engine(DeviceMesh([topo], [geom], nk=nk, numbering="local")), P
 
 
 def _fields(P, rng):
@@ -332,6 +355,26 @@ def test_interp_quad_matches_oracle_points(setup, kind, form, push):
     mp1 = P.mp1 if hasattr(P, "mp1") else eng.mesh.m + 1
     nex = P.nElsX
     nc = 2 if form == 1 else 1
+    want = np.zeros((2, nex * nex, mp1 * mp1, nc))
+    for lev in range(2):
+        for ey in range(nex):
+            for ex in range(nex):
+                for q in range(mp1 * mp1):
+                    want[lev, ey * nex + ex, q] = P.interp(kind, ex, ey, q % mp1, q // mp1, x[lev])[:nc]
+    got = got.reshape(want.shape)
+    assert rel_l2(got, want) < 1e-13, kind
+    one = eng.interp_quad(form, eng.tensor(x[1]), push_forward=push).cpu().numpy().reshape(want.shape[1:])
+    assert np.array_equal(one, got[1])
+
+
+@pytest.mark.parametrize("kind,form,push", [("0", 0, True), ("1l", 1, False), ("1g", 1, True), ("2l", 2, False), ("2g", 2, True)])
+def test_interp_quad_order_one_matches_oracle_points(order_one_box, kind, form, push):
+    """the same at order 1, the 4-lane layout, which `setup` cannot reach: a 6 x 6 periodic box with a full Jacobian, two levels: 72 units,
+    64 to a block"""
+    eng, P = order_one_box
+    x = np.random.default_rng(37).standard_normal((2, (P.n0, P.n1, P.n2)[form]))
+    got = eng.interp_quad(form, eng.tensor(x), push_forward=push).cpu().numpy()
+    mp1, nex, nc = 2, P.nElsX, 2 if form == 1 else 1
     want = np.zeros((2, nex * nex, mp1 * mp1, nc))
     for lev in range(2):
         for ey in range(nex):

@@ -142,10 +142,11 @@ def _random_tensors(eng, nk, seed):
     return dict(rot=(draw(nk, n0), draw(nk, n1)), pgf=(draw(nk, n2), draw(nk, n1)), vor=(draw(nk - 1, n1), draw(nk - 1, n2)))
 
 
-@pytest.mark.parametrize("pn", [1, 6, 7])
+@pytest.mark.parametrize("pn", [1, 2, 5, 6, 7])
 def test_other_orders_against_the_composed_route(pn):
-    """the 4-lane layout (order 1, a 5 x 5 box: 75 units, 64 + 11) and the 64-lane one (orders 6 and 7, a one-element-per-face sphere: 49 and 64
-    live lanes); no dense restatement at these orders: the composed device route is the reference"""
+    """the 4-lane layout (order 1, a 5 x 5 box: 75 units, 64 + 11) and, on a one-element-per-face sphere (18 units), orders 2 and 5 (9 and 36
+    live lanes of 16 and 64) and the 64-lane orders 6 and 7 (49 and 64 live lanes): with the fixtures' orders 3 and 4 every built order runs;
+    no dense restatement at these orders: the composed device route is the reference"""
     from mimsem_amd.geom import BoxGeom, Geom
     from mimsem_amd.mesh import CubedSphere, PeriodicBox, box_coords, sphere_coords
     from mimsem_amd.topo import Topo
