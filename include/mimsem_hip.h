@@ -332,6 +332,21 @@ int mimsem_euler_energetics_horiz(mimsem_ctx* ctx, int nlev, const double* velx,
 int mimsem_euler_energetics_column(mimsem_ctx* ctx, const double* velz, const double* rho, const double* zv, const double* linear_inv,
                                    double* out);
 
+/* The entropy of the box twin's energetics line (box/Euler_2.cpp:979-997, slot 11 of output/energetics.dat) in one element pass
+ * (csrc/log_entropy.inc) and a fixed-order final pass; out: DEVICE pointer to 1 double
+ *   out[0] = factor sum_rows lz[row] sum_e sum_q Q_q log((W theta_row)_q)             (:986-991; factor: the CP of :997)
+ * (W theta)_q: the LOCAL 2-form interpolant at quadrature point q (Ax_b with vert->vo->W, :987) -- no 1/det and no thickness, what
+ * mimsem_interp_quad gives without MIMSEM_INTERP_GLOBAL; Q_q = w_qx w_qy (vert->vo->Q).  theta: 2-form rows in the horizontal layout,
+ * row r at theta + r theta_pitch (doubles; 0, the same row for every r, or at least n2); lz: DEVICE array [nrows], the layer weights of :988.  nrows is
+ * not bound by the context's nk (the box passes its nk + 1 interfaces), as mimsem_interp_quad's nlev is not.  theta must be positive at
+ * every point: the logarithm of anything else is NaN or -inf and the sum says so.  Element orders 1..7.  Deterministic: no floating-point
+ * atomics, the grid depends on (nEl, nrows, order) only, two calls on the same input give the same bits.  No host synchronisation,
+ * nothing is read back; the partial sums live in the context's reduction workspace, which grows on the first call only (capturable once
+ * warmed up: MIMSEM_ERR_STATE if it had to grow inside a capture).  A null pointer, a pitch below 0 or in 1 .. n2-1, or nrows < 1: MIMSEM_ERR_ARG,
+ * nothing launched, out untouched.                                                                                                  */
+int mimsem_euler_log_entropy(mimsem_ctx* ctx, int nrows, const double* theta, long long theta_pitch, const double* lz, double factor,
+                             double* out);
+
 /* HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470), the horizontal Bernoulli function of momentum_rhs_ec, for levels 0 .. nk-1 in ONE
  * launch (k_horiz_bernoulli, csrc/bernoulli.inc) instead of three accumulating WtQUmat applies, two interface averages and three
  * accumulating Whmat applies:

@@ -178,6 +178,7 @@ _SIGS = {
     "mimsem_elem_block_pc_build_levels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint, c_dp, c_ll, c_dp]),
     "mimsem_euler_energetics_horiz": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp, c_ll, c_dp]),
     "mimsem_euler_energetics_column": (C.c_int, [C.c_void_p, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "mimsem_euler_log_entropy": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_ll, c_dp, C.c_double, c_dp]),
     "mimsem_horiz_bernoulli": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_ll, c_dp, c_dp, c_ll, C.c_double, c_dp, c_ll]),
     "mimsem_horiz_flux_rhs": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_ll, c_dp, c_dp, c_ll, C.c_double, c_dp, c_ll]),
     "mimsem_horiz_momentum_forcing": (C.c_int, [C.c_void_p, C.c_int, C.c_uint, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),

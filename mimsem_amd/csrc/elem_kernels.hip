@@ -2109,3 +2109,4 @@ int launch_halo_unpack(mimsem_ctx* c, const int* idx, int count, int nlev, int m
 #include "flux_rhs.inc"
 #include "momentum_forcing.inc"
 #include "zonal_stats.inc"
+#include "log_entropy.inc"

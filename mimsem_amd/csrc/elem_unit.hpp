@@ -1,5 +1,5 @@
 // elem_unit.hpp -- the frame of a point-per-lane element kernel: what the fused element passes of elem_kernels.hip (energetics.inc,
-// flux_rhs.inc, momentum_forcing.inc, zonal_stats.inc, k_interp_quad) have around their arithmetic; a new pass starts from here (DESIGN.md
+// flux_rhs.inc, momentum_forcing.inc, zonal_stats.inc, log_entropy.inc, k_interp_quad) have around their arithmetic; a new pass starts from here (DESIGN.md
 // 4.3).  bernoulli.inc and tsw_kernels.hip spell the same frame out themselves (profiles/elem_unit_layer.txt section 4 says why).
 // Layout: a unit is one (level, element); LPE lanes carry it, lane q owns quadrature point q and, where q is small enough, DoF q / the
 // edge pair q.  LPE divides 64, so an element's lanes share a wave: hand-offs through LDS rows need wave_lds_sync() only; the edge table

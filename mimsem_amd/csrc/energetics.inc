@@ -101,12 +101,13 @@ __global__ __launch_bounds__(256) void k_energetics_horiz(EnergeticsArgs a) {
     if (tid < 4) a.part[(size_t)blockIdx.x*4 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
 }
 
-// wave t sums term t of the nb partial 4-vectors in a fixed order and applies its constant factor
-__global__ __launch_bounds__(256) void k_energetics_final(int nb, const double* __restrict__ part, double f0, double f1, double f2, double f3,
-                                                          double* __restrict__ out) {
+// wave t sums term t of the nb partial NT-vectors in a fixed order and applies its constant factor (NT waves; log_entropy.inc has NT = 1)
+template <int NT>
+__global__ __launch_bounds__(64*NT) void k_energetics_final(int nb, const double* __restrict__ part, double f0, double f1, double f2, double f3,
+                                                            double* __restrict__ out) {
     const int lane = threadIdx.x & 63, t = threadIdx.x >> 6;
     double s = 0.0;
-    for (int i = lane; i < nb; i += 64) s += part[(size_t)i*4 + t];
+    for (int i = lane; i < nb; i += 64) s += part[(size_t)i*NT + t];
     s = en_wave_sum(s);
     if (lane == 0) out[t] = s*(t == 0 ? f0 : (t == 1 ? f1 : (t == 2 ? f2 : f3)));
 }
@@ -121,7 +122,7 @@ int energetics_horiz_n(mimsem_ctx* c, EnergeticsArgs& a, double* out) {
     a.part = c->d_kry;
     hipLaunchKernelGGL((k_energetics_horiz<N>), dim3(nb), dim3(256), 0, c->stream, a);
     MIMSEM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_energetics_final, dim3(1), dim3(256), 0, c->stream, nb, (const double*)c->d_kry, 0.5, 717.5/1004.5, 0.5, 1.0, out);      // CV/CP eul/Euler_2.cpp:29-30
+    hipLaunchKernelGGL(k_energetics_final<4>, dim3(1), dim3(256), 0, c->stream, nb, (const double*)c->d_kry, 0.5, 717.5/1004.5, 0.5, 1.0, out);      // CV/CP eul/Euler_2.cpp:29-30
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;
 }
@@ -230,7 +231,7 @@ int energetics_column_n(mimsem_ctx* c, EnColumnArgs& a, double* out) {
     a.part = c->d_kry;
     hipLaunchKernelGGL((k_energetics_column<N>), dim3(nb), dim3(64), 0, c->stream, a);
     MIMSEM_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_energetics_final, dim3(1), dim3(256), 0, c->stream, nb, (const double*)c->d_kry, 0.5/EN_SCALE, 1.0/EN_SCALE, 1.0/EN_SCALE,
+    hipLaunchKernelGGL(k_energetics_final<4>, dim3(1), dim3(256), 0, c->stream, nb, (const double*)c->d_kry, 0.5/EN_SCALE, 1.0/EN_SCALE, 1.0/EN_SCALE,
                        1.0/EN_SCALE, out);
     MIMSEM_HIP_TRY(hipGetLastError());
     return MIMSEM_OK;

@@ -642,6 +642,18 @@ class Engine:
               "euler_energetics_column")
         return out
 
+    def log_entropy(self, theta, lz, factor=1.0, out=None):
+        """mimsem_euler_log_entropy: factor sum_r lz[r] sum_e sum_q Q_q log((W theta_r)_q), the entropy of the box's energetics line
+        (box/Euler_2.cpp:979-997), as a device tensor of 1; theta [nrows, n2] (rows contiguous, any row stride; nrows is not bound by the
+        context's nk), lz [nrows]"""
+        th = self._rows(theta, self.sizes[2], "theta", min_rows=1, strided="r")
+        nrows = th.shape[0]
+        out = self._new(1) if out is None else out
+        ps = _ps if nrows > 1 else (lambda v2: (_ps(v2)[0], 0))                      # (one row: row stride 0)
+        check(self.L.mimsem_euler_log_entropy(self.ctx, nrows, *ps(th), self._vec(lz, nrows, "lz"), float(factor), self._vec(out, 1, "out")),
+              "euler_log_entropy")
+        return out
+
     def bernoulli(self, velx1, velx2, velz1, velz2, scale=1.0, out=None):
         """mimsem_horiz_bernoulli: HorizSolve::diagnose_Phi (eul/HorizSolve.cpp:419-470) of every level in one launch; velx1, velx2 [nk, n1],
         velz1, velz2 [nk-1, n2] (horizontal layout) -> Phi [nk, n2].  Rows contiguous, any row stride (the two of a pair share it); velx1 is

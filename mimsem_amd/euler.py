@@ -345,6 +345,10 @@ class BoxEuler(Euler):
     # measurement of scripts/prof_box_strang.py (profiles/box_strang.txt: p = 4, 32 x 32 x 64; one evaluation 585 us against 609 us, the
     # forcing alone 63 us against 115 us)
     FUSED_FORCING = True
+    # the entropy of the energetics line: mimsem_euler_log_entropy (two launches, nothing but theta read) or interp_quad, torch.log and a
+    # weighted sum -- decided by the measurement of scripts/prof_box_entropy.py (profiles/box_entropy.txt: p = 4, 32 x 32 x 64; 24.9 us
+    # against 43.7 us)
+    FUSED_ENTROPY = True
 
     def __init__(self, eng, dt, levs, quad_coords, lx=LX, newton_maxit=20, newton_tol=1e-12, do_visc=True):
         """eng: Engine of a one-patch PeriodicBox (global numbering, nk >= 4, order <= 4); levs [nk+1, nq]; quad_coords [nq, 3]"""
@@ -377,7 +381,9 @@ class BoxEuler(Euler):
 
     def entropy(self, theta):
         """:979-997 of theta [nk+1, n2] (horizontal layout), a device scalar"""
-        tq = self.eng.interp_quad(2, theta, push_forward=False)                         # W theta_k at the points: [nk+1, nEl, mp12]
+        if self.FUSED_ENTROPY:
+            return self.eng.log_entropy(theta, self._lz, bubble.CP)[0]
+        tq = self.eng.interp_quad(2, theta, push_forward=False)                        # W theta_k at the points: [nk+1, nEl, mp12]
         return bubble.CP * (self._lz[:, None, None] * self._Q[None, None, :] * torch.log(tq)).sum()
 
     def _diagnostics(self, new):

@@ -20,7 +20,7 @@ namespace mimsem_host {
 
 class HorizSolve {
     Mesh* mesh; const double* fg; Shard* sh;
-    int nk, n0, n1, n2; bool have_k2i = false, wanted_fixed = true;
+    int nk, n0, n1, n2; bool have_k2i = false, wanted_fixed = true, box = false;
     DeviceArrays mem;
     double* own1n;                                           // (sharded) ownership weights of all levels side by side (the rows of a batched inner product)
     KspHandle ksp1;
@@ -64,6 +64,22 @@ public:
         check(mimsem_ksp_set_tolerances(ksp1, rtol, 1.0e-50, 1000, 0, 2), "mimsem_ksp_set_tolerances");
         use_fixed_length(true);
     }
+    // Box mode (box/HorizSolve.cpp), selected by this tag: lx the side of the doubly periodic box; thick the HOST layer thicknesses the mesh was made
+    // with (mimsem_mesh_desc::thick, `count` doubles).  What differs from the sphere: del2 = -sqrt(2 * 0.072 dx^3.2), dx = sqrt(lx^2 / nDofs0G)
+    // (:106-114); the rotational operands of momentum_rhs are curl(u_h) WITHOUT Coriolis and u_h itself (diagnose_wxu :382-410) -- no diagnose_q, no
+    // mass-flux solve, rho1 / rho2 may be null; the _ec routines and diagnose_q have no box twin and throw.  UNIFORM LAYERS ONLY: the reference assembles
+    // its matrices once, at level 0 (box/Assembly.cpp:44); the constructor throws on any other mesh.  One context (the box is one patch).
+    struct Box { double lx; const double* thick; size_t count; };
+    HorizSolve(Mesh* m, const Box& bx, bool visc = true) : HorizSolve(m, nullptr, 0, visc, nullptr) {
+        box = true;
+        if (!bx.thick || bx.count == 0) throw std::runtime_error("HorizSolve (box): the layer thicknesses are needed for the uniform-layer check");
+        double lo = bx.thick[0], hi = bx.thick[0];
+        for (size_t i = 1; i < bx.count; i++) { lo = std::min(lo, bx.thick[i]); hi = std::max(hi, bx.thick[i]); }
+        if (!(lo > 0.0 && hi - lo <= 1.0e-14*hi)) throw std::runtime_error("HorizSolve (box): uniform layers only");
+        const double dx = std::sqrt(bx.lx*bx.lx/(double)n0);
+        del2 = -std::sqrt(2.0*0.072*std::pow(dx, 3.2));
+    }
+    bool box_mode() const { return box; }
     HorizSolve(const HorizSolve&) = delete; HorizSolve& operator=(const HorizSolve&) = delete;
     void use_fixed_length(bool on) {
         fixed_length = false; wanted_fixed = on;
@@ -148,6 +164,7 @@ public:
     // :380-417: dF, dG [nk][n2] (horizontal layout; the caller's HorizToVert is mimsem_l2_transpose), Fk, Gk [nk][n1]
     void advection_rhs_ec(const double* u1, const double* u2, const double* h1, const double* h2, const double* theta, double* dF, double* dG,
                           double* Fk, double* Gk) {
+        no_box_twin("advection_rhs_ec");
         diagnose_fluxes(u1, u2, h1, h2, theta, Fk, Gk);
         inc(1, Fk, n1, b2, n2);
         ap(MIMSEM_OP_WMAT, MIMSEM_FLAG_VERT, nullptr, 0, b2, n2, dF, n2, 1.0);
@@ -160,8 +177,34 @@ public:
     // grad(theta) of the last advection_rhs_ec [nk][n1]: momentum_rhs_ec of the same stage solves the same system for the same theta
     // (:403 and :659 in the reference, two KSPSolves with one answer) -- passed as its dTheta it saves one of the seven mass solves
     const double* last_grad_theta() const { return gt1; }
+    // The switches of the non-_ec right-hand sides, as HorizSolve.fused_hu / fused_forcing / fused_phi in Python: the mass-flux right-hand side by
+    // mimsem_horiz_flux_rhs, the element-local forcing of momentum_rhs by mimsem_horiz_momentum_forcing, diagnose_Phi by mimsem_horiz_bernoulli.
+    // All off by default: the _ec routines keep their bits.  One context only (not on a shard).
+    // In box mode fused_hu acts in advection_rhs only: the box's rotational term takes u_h itself, momentum_rhs forms no mass flux there.
+    bool fused_hu = false, fused_forcing = false, fused_phi = false;
+    // F = M1^-1 (hu),  G = M1^-1 F(1/2 theta_k + 1/2 theta_{k+1}; no vert_scale) F  (:285-327, theta_in_Wt = true: theta [nk+1][n2] on the interfaces)
+    void diagnose_fluxes_Wt(const double* u1, const double* u2, const double* h1, const double* h2, const double* theta, double* F, double* G) {
+        hu(u1, u2, h1, h2, d1);
+        solve_M1(d1, F);
+        theta_levels(theta, b2);                                                                            // :313-317
+        ap(MIMSEM_OP_UHMAT, 0, b2, n2, F, n1, d1, n1, 1.0);
+        solve_M1(d1, G);
+    }
+    // :330-375: dF = E21 Fk, dG = E21 Gk [nk][n2] (no M2 factor: VertSolve::solve_schur_2 applies VB after adding them), Fk, Gk [nk][n1];
+    // theta [nk+1][n2] on the interfaces.  The do_temp_visc branch (:341-364) is not built, as in Python
+    void advection_rhs(const double* u1, const double* u2, const double* h1, const double* h2, const double* theta, double* dF, double* dG,
+                       double* Fk, double* Gk) {
+        diagnose_fluxes_Wt(u1, u2, h1, h2, theta, Fk, Gk);
+        inc(1, Fk, n1, dF, n2);
+        inc(1, Gk, n1, dG, n2);
+    }
     // :419-470
     void diagnose_Phi(const double* u1, const double* u2, const double* velz1, const double* velz2, double* Phi) {
+        if (fused_phi) {
+            one_context("fused_phi");
+            check(mimsem_horiz_bernoulli(mesh->ctx, nk, u1, u2, n1, velz1, velz2, n2, SCALE, Phi, n2), "mimsem_horiz_bernoulli");
+            return;
+        }
         ap(MIMSEM_OP_WTQUMAT, 0, u1, n1, u1, n1, Phi, n2, 1.0/3.0);
         ap(MIMSEM_OP_WTQUMAT, MIMSEM_FLAG_ACCUM, u1, n1, u2, n1, Phi, n2, 1.0/3.0);
         ap(MIMSEM_OP_WTQUMAT, MIMSEM_FLAG_ACCUM, u2, n1, u2, n1, Phi, n2, 1.0/3.0);
@@ -174,6 +217,7 @@ public:
     }
     // (M0h(rho)) q = E01 M1 u + M0 f; M0h is diagonal  (:472-493)
     void diagnose_q(const double* rho, const double* u, double* q) {
+        no_box_twin("diagnose_q");
         ap(MIMSEM_OP_UMAT, MIMSEM_FLAG_VERT, nullptr, 0, u, n1, g1, n1, 1.0);
         inc(3, g1, n1, q, n0);
         mesh->combine(n0, 1.0, m0, 1, fg, 1.0, q, q, nk);
@@ -187,7 +231,7 @@ public:
                          const double* velx1, const double* velx2, const double* rho1, const double* rho2, double* fu,
                          const double* Fx = nullptr, const double* Fz = nullptr, const double* dwdx1 = nullptr, const double* dwdx2 = nullptr,
                          const double* Fk = nullptr, const double* dTheta = nullptr) {
-        mimsem_ctx* c = mesh->ctx;
+        no_box_twin("momentum_rhs_ec");
         diagnose_Phi(velx1, velx2, velz1, velz2, a2);
         inc(2, a2, n2, fu, n1);
         grad(Pi, a1);                                                                                         // dPi
@@ -202,26 +246,46 @@ public:
         ap(MIMSEM_OP_WHMAT, MIMSEM_FLAG_VERT, Pi, n2, theta, n2, a2, n2, 1.0);
         inc(2, a2, n2, d1, n1);                                                                               // dp
         mesh->combine(n1, 0.5, d1, 0, nullptr, 1.0, fu, fu, nk);
-        have_k2i = Fk != nullptr;
-        if (Fk && sh) { mesh->combine(n1, 1.0, Fk, 1, own1n, 0.0, nullptr, w1, nk); check(mimsem_krylov_rowdot(c, 1, (long long)nk*n1, w1, (long long)nk*n1, d1, (long long)nk*n1, scal), "mimsem_krylov_rowdot"); }
-        else if (Fk) check(mimsem_krylov_rowdot(c, 1, (long long)nk*n1, Fk, (long long)nk*n1, d1, (long long)nk*n1, scal), "mimsem_krylov_rowdot");
-        // second vorticity term: interface i feeds levels i and i+1 (:704-746)
-        if (nk > 1) {
-            mesh->combine(n1, 0.5, dudz1, 0, nullptr, 0.5, dudz2, a1, nk - 1);                                        // dz
-            if (dwdx1) { mesh->combine(n1, -0.5, dwdx1, 0, nullptr, 1.0, a1, a1, nk - 1); mesh->combine(n1, -0.5, dwdx2, 0, nullptr, 1.0, a1, a1, nk - 1); }
-            const double* v = Fz;
-            if (!v) { mesh->combine(n2, 0.5, velz1, 0, nullptr, 0.5, velz2, a2, nk - 1); v = a2; }
-            apn(nk - 1, MIMSEM_OP_UTQWMAT, 0, a1, n1, v, n2, b1, n1, 1.0);                                      // UtQWmat::assemble(u1, scale): no thickness
-            mesh->combine(n1, 0.5, b1, 0, nullptr, 1.0, fu + n1, fu + n1, nk - 1);
-            mesh->combine(n1, 0.5, b1, 0, nullptr, 1.0, fu, fu, nk - 1);
-        }
-        if (do_visc) {
-            laplacian(c1, a1);
-            laplacian(a1, b1);
-            ap(MIMSEM_OP_UMAT, MIMSEM_FLAG_VERT | MIMSEM_FLAG_ACCUM, nullptr, 0, b1, n1, fu, n1, 1.0);
-        }
+        k2i_dot(Fk, d1);
+        vorticity_and_viscosity(fu, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2);
     }
-    // horizontal kinetic-to-internal energy exchange of the last momentum_rhs_ec that was given Fk (synchronises)
+    // :496-635 for every level at once: momentum_rhs_ec with theta [nk+1][n2] on the interfaces.  There is no grad(theta); the pressure gradient
+    // force is the single term fu += F(theta_h; no vert_scale) dPi, theta_h = 1/2 theta_k + 1/2 theta_{k+1} (:514-517, :556-558), and k2i() =
+    // sum_k Fk_k . (F(theta_h) dPi)_k / SCALE (:560-563, needs Fk).  The mass flux of the rotational term (Fx null) is formed by fused_hu; with
+    // fused_forcing the rotational term, the pressure gradient force and the second vorticity term are one mimsem_horiz_momentum_forcing call
+    // (dp for k2i then keeps its own Uhmat apply).  The second vorticity term and the viscosity are momentum_rhs_ec's
+    void momentum_rhs(const double* theta, const double* dudz1, const double* dudz2, const double* velz1, const double* velz2, const double* Pi,
+                      const double* velx1, const double* velx2, const double* rho1, const double* rho2, double* fu,
+                      const double* Fx = nullptr, const double* Fz = nullptr, const double* dwdx1 = nullptr, const double* dwdx2 = nullptr,
+                      const double* Fk = nullptr) {
+        diagnose_Phi(velx1, velx2, velz1, velz2, a2);
+        inc(2, a2, n2, fu, n1);
+        grad(Pi, a1);                                                                                         // dPi
+        mesh->combine(n1, 0.5, velx1, 0, nullptr, 0.5, velx2, c1, nk);                                        // uh
+        if (box) { curl(c1, a0); Fx = c1; }                                                                   // diagnose_wxu box :382-410
+        else {
+            mesh->combine(n2, 0.5, rho1, 0, nullptr, 0.5, rho2, b2, nk);
+            diagnose_q(b2, c1, a0);
+            if (!Fx) { hu(velx1, velx2, rho1, rho2, d1); solve_M1(d1, e1); Fx = e1; }
+        }
+        theta_levels(theta, b2);                                                                              // theta_h (:514-517)
+        if (fused_forcing) {
+            one_context("fused_forcing");
+            const double* v = nk > 1 ? vorticity_operands(dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2, b1) : nullptr;
+            check(mimsem_horiz_momentum_forcing(mesh->ctx, nk, MIMSEM_FLAG_ACCUM, SCALE, a0, Fx, b2, a1, nk > 1 ? b1 : nullptr, v, fu),
+                  "mimsem_horiz_momentum_forcing");
+            if (Fk) ap(MIMSEM_OP_UHMAT, 0, b2, n2, a1, n1, d1, n1, 1.0);
+            k2i_dot(Fk, d1);
+            viscosity(fu);
+            return;
+        }
+        ap(MIMSEM_OP_ROTMAT, MIMSEM_FLAG_ACCUM, a0, n0, Fx, n1, fu, n1, 1.0);
+        ap(MIMSEM_OP_UHMAT, 0, b2, n2, a1, n1, d1, n1, 1.0);                                                   // dp: the pressure gradient force
+        mesh->combine(n1, 1.0, d1, 0, nullptr, 1.0, fu, fu, nk);
+        k2i_dot(Fk, d1);
+        vorticity_and_viscosity(fu, dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2);
+    }
+    // horizontal kinetic-to-internal energy exchange of the last momentum_rhs_ec / momentum_rhs that was given Fk (synchronises)
     double k2i() {
         if (!have_k2i) return 0.0;
         double v = 0.0;
@@ -243,6 +307,52 @@ public:
     }
 
 private:
+    void no_box_twin(const char* what) const { if (box) throw std::runtime_error(std::string("HorizSolve (box): box/HorizSolve.cpp has no ") + what); }
+    void one_context(const char* what) const { if (sh) throw std::runtime_error(std::string("HorizSolve (sharded): ") + what + " is for one context"); }
+    // 1/2 theta_k + 1/2 theta_{k+1} of theta on the nk+1 interfaces (:314-316, :515-517)
+    void theta_levels(const double* theta, double* th) { mesh->combine(n2, 0.5, theta, 0, nullptr, 0.5, theta + n2, th, nk); }
+    // the mass-flux right-hand side of the two non-_ec routines: the fused kernel when fused_hu is set
+    void hu(const double* ua, const double* ub, const double* ha, const double* hb, double* out) {
+        if (!fused_hu) { uvec_hu4(ua, ub, ha, hb, out); return; }
+        one_context("fused_hu");
+        check(mimsem_horiz_flux_rhs(mesh->ctx, nk, ua, ub, n1, ha, hb, n2, SCALE, out, n1), "mimsem_horiz_flux_rhs");
+    }
+    // the sum Fk . dp over every level, left on the device for k2i() (:560-563, :697-701)
+    void k2i_dot(const double* Fk, const double* dp) {
+        mimsem_ctx* c = mesh->ctx;
+        have_k2i = Fk != nullptr;
+        if (Fk && sh) { mesh->combine(n1, 1.0, Fk, 1, own1n, 0.0, nullptr, w1, nk); check(mimsem_krylov_rowdot(c, 1, (long long)nk*n1, w1, (long long)nk*n1, dp, (long long)nk*n1, scal), "mimsem_krylov_rowdot"); }
+        else if (Fk) check(mimsem_krylov_rowdot(c, 1, (long long)nk*n1, Fk, (long long)nk*n1, dp, (long long)nk*n1, scal), "mimsem_krylov_rowdot");
+    }
+    // coefficient and input of the second vorticity term (:565-607, :704-746): dz = 1/2 dudz1 + 1/2 dudz2 - 1/2 dwdx1 - 1/2 dwdx2 into `dz` (Rh is linear
+    // in its coefficient); returns v: Fz, or the mean vertical velocity in a2
+    const double* vorticity_operands(const double* dudz1, const double* dudz2, const double* velz1, const double* velz2, const double* Fz,
+                                     const double* dwdx1, const double* dwdx2, double* dz) {
+        mesh->combine(n1, 0.5, dudz1, 0, nullptr, 0.5, dudz2, dz, nk - 1);
+        if (dwdx1) { mesh->combine(n1, -0.5, dwdx1, 0, nullptr, 1.0, dz, dz, nk - 1); mesh->combine(n1, -0.5, dwdx2, 0, nullptr, 1.0, dz, dz, nk - 1); }
+        if (Fz) return Fz;
+        mesh->combine(n2, 0.5, velz1, 0, nullptr, 0.5, velz2, a2, nk - 1);
+        return a2;
+    }
+    // the end both momentum right-hand sides share (:565-623, :704-768): the second vorticity term -- interface i feeds levels i and i+1 -- and the
+    // biharmonic viscosity, added to fu
+    void vorticity_and_viscosity(double* fu, const double* dudz1, const double* dudz2, const double* velz1, const double* velz2, const double* Fz,
+                                 const double* dwdx1, const double* dwdx2) {
+        if (nk > 1) {
+            const double* v = vorticity_operands(dudz1, dudz2, velz1, velz2, Fz, dwdx1, dwdx2, a1);
+            apn(nk - 1, MIMSEM_OP_UTQWMAT, 0, a1, n1, v, n2, b1, n1, 1.0);                                      // UtQWmat::assemble(u1, scale): no thickness
+            mesh->combine(n1, 0.5, b1, 0, nullptr, 1.0, fu + n1, fu + n1, nk - 1);
+            mesh->combine(n1, 0.5, b1, 0, nullptr, 1.0, fu, fu, nk - 1);
+        }
+        viscosity(fu);
+    }
+    // the biharmonic viscosity of the mean velocity c1 (:609-623, :754-768), added to fu
+    void viscosity(double* fu) {
+        if (!do_visc) return;
+        laplacian(c1, a1);
+        laplacian(a1, b1);
+        ap(MIMSEM_OP_UMAT, MIMSEM_FLAG_VERT | MIMSEM_FLAG_ACCUM, nullptr, 0, b1, n1, fu, n1, 1.0);
+    }
     double* level_rows(const double* own1) {
         std::vector<double> o1(n1), on((size_t)nk*n1);
         mesh->to_host(o1.data(), own1, n1);

@@ -703,6 +703,11 @@ struct Euler {
     void energetics_column(const double* velz, const double* rho, const double* zv, const double* linear_inv, double* out) const {
         check(mimsem_euler_energetics_column(mesh->ctx, velz, rho, zv, linear_inv, out), "Euler::energetics_column");
     }
+    // out (device, 1 double): factor sum_r lz[r] sum_e sum_q Q_q log((W theta_r)_q), the entropy of the box's energetics line (box/Euler_2.cpp:979-997);
+    // theta [nrows][n2] (rows `pitch` doubles apart; nrows is not bound by nk: the box has nk + 1 interfaces), lz (device) [nrows].  No host synchronisation.
+    void log_entropy(int nrows, const double* theta, long long pitch, const double* lz, double factor, double* out) const {
+        check(mimsem_euler_log_entropy(mesh->ctx, nrows, theta, pitch, lz, factor, out), "Euler::log_entropy");
+    }
     // the band plan of the zonal-mean statistics: band (HOST, [nEl][mp12]) names the band in [0, nb) of every quadrature point, -1 leaves it out
     void zonal_plan(const int* band, int nb) const { check(mimsem_zonal_plan_build(mesh->ctx, band, nb), "Euler::zonal_plan"); }
     // acc (device, [9][nk][nb]) += the band sums of a {1, u, v, T, uu, vv, uv, vT, TT} of levels 0 .. nk-1 in one launch; packed rows velx [nk][n1],

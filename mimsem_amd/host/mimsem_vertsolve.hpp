@@ -5,7 +5,9 @@
 //                 (:677-823: the linear solve) and mimsem_column_newton_update (:1858-1912); stops on the exner and rho norms
 //   VertSolve2    VertSolve::solve_schur_2 (:1059-1246), the loop around solve_schur_column_3 and the vertical half of Euler::Strang: per iteration
 //                 mimsem_column_newton2_residual (assemble_residual :386-430 and the right-hand sides of :1134-1154), mimsem_column_solve_schur_3
-//                 (:504-675) and mimsem_column_newton2_update (:1159-1183); theta lives on the nk+1 interfaces only; stops on THREE norms (:1202)
+//                 (:504-675) and mimsem_column_newton2_update (:1159-1183); theta lives on the nk+1 interfaces only; stops on THREE norms (:1202).
+//                 With theta_up / vert_mom_vort the loop of the box twin (box/VertSolve.cpp:1264-1458): theta from mimsem_column_diag_theta_wup,
+//                 the u dw/dx term time-centred between udwdx and AssembleVertMomVort of the iterate
 // Both then take the max-norms of VertSolve::MaxNorm (:228: mimsem_column_max_norms) and mimsem_column_diag_theta_blend (diagTheta2 / diagTheta_L2
 // :289-352 with the half-time blend): VertNewton below is that shared loop.  All state in the "vertical" layout of L2Vecs::vz: [nEl][slots*n2e], velz
 // on the nk-1 interfaces, theta on nk+1, the rest on the nk levels.  Orders 1..4 (the fused entries' range).  Header-only, C++17, no HIP toolchain.
@@ -52,12 +54,19 @@ protected:
 
     // The loop: velz / rho / rt / exner at the old time level in, at the new one out (in place).  step() is one iteration up to and including the
     // update, which leaves the squares in nrm; record(mx) keeps the four norms and says whether to stop.  Returns the number of iterations run.
+    // theta_up: theta_i / theta_h from diagTheta2 with the test functions upwinded by velz / velz_j over 0.25 dt (box/VertSolve.cpp:1312, :1394-1399;
+    // that loop has no level arrays); after(): what follows the theta diagnosis of an iteration (box :1403).
     template <class Step, class Record>
     int newton(double* velz, double* rho, double* rt, double* exner, int maxit, Step step, Record record) {
+        return newton(velz, rho, rt, exner, maxit, step, record, false, [] {});
+    }
+    template <class Step, class Record, class After>
+    int newton(double* velz, double* rho, double* rt, double* exner, int maxit, Step step, Record record, bool theta_up, After after) {
         mimsem_ctx* c = mesh->ctx;
         mesh->copy(ni, velz, velz_j); mesh->copy(nl, rho, rho_j); mesh->copy(nl, rt, rt_j); mesh->copy(nl, exner, exner_j);      // :1099-1102
         // diagTheta2 (:1766, :1105) and, for the loop that has the level arrays, diagTheta_L2 (:1773)
-        check(mimsem_column_diag_theta_blend(c, rho, rt, theta_i, nullptr, theta_l2_i, nullptr, 1.0, 0.0), "diag_theta_blend");
+        if (theta_up) check(mimsem_column_diag_theta_wup(c, 0.25*dt, rho, rt, velz, theta_i, nullptr, 1.0, 0.0), "diag_theta_wup");
+        else check(mimsem_column_diag_theta_blend(c, rho, rt, theta_i, nullptr, theta_l2_i, nullptr, 1.0, 0.0), "diag_theta_blend");
         mesh->copy(nt, theta_i, theta_h);
         if (theta_l2_i) mesh->copy(nl, theta_l2_i, theta_l2_h);
         mesh->copy(nl, exner, exner_h); mesh->copy(ni, velz, velz_h); mesh->copy(nl, rho, rho_h); mesh->copy(nl, rt, rt_h);       // :1112-1117
@@ -67,7 +76,9 @@ protected:
             // MaxNorm (:228): per column sqrt(sum d^2 / sum x^2), the maximum over the columns (the rank-local part of the MPI_Allreduce(MAX))
             check(mimsem_column_max_norms(c, nrm, sums, sums + 4*(size_t)nEl), "column_max_norms");
             // (the theta diagnosis does not depend on the norms: launched before the host waits for them)                   :1896-1912, :1186-1191
-            check(mimsem_column_diag_theta_blend(c, rho_j, rt_j, theta_h, theta_i, theta_l2_h, theta_l2_i, 0.5, 0.5), "diag_theta_blend");
+            if (theta_up) check(mimsem_column_diag_theta_wup(c, 0.25*dt, rho_j, rt_j, velz_j, theta_h, theta_i, 0.5, 0.5), "diag_theta_wup");
+            else check(mimsem_column_diag_theta_blend(c, rho_j, rt_j, theta_h, theta_i, theta_l2_h, theta_l2_i, 0.5, 0.5), "diag_theta_blend");
+            after();                     // (before the norms are read: on the LAST iteration too, as box :1403 and the Python loop have it)
             double mx[4];
             mesh->to_host(mx, sums + 4*(size_t)nEl, 4);
             if (allreduce_max) allreduce_max(mx, 4);                                                                        // :1915-1918, :1195-1198
@@ -133,9 +144,17 @@ public:
     struct Norms { double exner, w, rho, rt; };
     std::vector<Norms> history;                       // |d x| / |x| (max over the columns) of the iterations of the last solve
     unsigned schur3_flags = 0;                        // passed to mimsem_column_solve_schur_3 (MIMSEM_SCHUR3_BOX: box/VertSolve.cpp, with rayleigh = 0)
+    // The loop of the box twin (box/VertSolve.cpp:1264-1458; with schur3_flags = 3 and rayleigh = 0).  theta_up: theta_i / theta_j from
+    // mimsem_column_diag_theta_wup(0.25 dt, ..) at the start and after every iteration (:1312, :1394; orders 1..4, needs |0.25 dt w| < 1).
+    // vert_mom_vort(velz_j, uuz_j): AssembleVertMomVort (:1460-1499) of the iterate into uuz_j [nEl][(nk-1)*n2e]; with udwdx it makes the term
+    // time-centred, F_w += 1/2 dt udwdx + 1/2 dt uuz_j (:1343-1346), uuz_j = udwdx in the first iteration (:1326) and recomputed at the end of
+    // each (:1403); without udwdx it is not called (the reference's `if(udwdx)`).  Both off: the eul loop, bit for bit.
+    bool theta_up = false;
+    std::function<void(const double*, double*)> vert_mom_vort;
 
     VertSolve2(Mesh* m, double dt_) : VertNewton(m, dt_) {
         for (double** p : {&F_rt, &d_rt, &hs}) *p = mem.get(nl);
+        for (double** p : {&uuz_j, &add_w}) *p = mem.get(ni);
     }
 
     // VertSolve::solve_schur_2: zv from VertSolve::initGZ.  udwdx (nullable, [nEl][(nk-1)*n2e]): :1134; hs_lat (nullable, [nEl][mp12]): the Held-Suarez
@@ -144,21 +163,28 @@ public:
                       const double* udwdx = nullptr, const double* hs_lat = nullptr) {
         mimsem_ctx* c = mesh->ctx;
         history.clear();
+        const bool centred = udwdx && vert_mom_vort;
+        if (centred) mesh->copy(ni, udwdx, uuz_j);                                                                              // box :1326
         return newton(velz, rho, rt, exner, maxit, [&] {
-            const double *a_rho = nullptr, *a_rt = nullptr, *a_hs = nullptr;
+            const double *a_rho = nullptr, *a_rt = nullptr, *a_hs = nullptr, *a_w = udwdx;
+            if (centred) {                                                                                                      // box :1343-1346
+                check(mimsem_vec_combine(c, 1, (long long)ni, 0.5, udwdx, 0, 0, nullptr, 0, 0.5, uuz_j, 0, add_w, 0), "vec_combine");
+                a_w = add_w;
+            }
             if (horiz_forcing) { horiz_forcing(rho, rho_j, theta_h, add_rho, add_rt); a_rho = add_rho; a_rt = add_rt; }            // :1124
             if (hs_lat) { check(mimsem_column_temp_forcing_hs(c, hs_lat, exner_h, theta_h, rho_h, hs), "temp_forcing_hs"); a_hs = hs; }
             check(mimsem_column_newton2_residual(c, dt, rayleigh, theta_h, exner_h, velz, velz_j, rho, rho_j, zv, rt, rt_j, exner_j,
-                                                 udwdx, a_rho, a_rt, a_hs, F_w, F_rho, F_rt, F_exner, k2i), "newton2_residual");
+                                                 a_w, a_rho, a_rt, a_hs, F_w, F_rho, F_rt, F_exner, k2i), "newton2_residual");
             check(mimsem_column_solve_schur_3(c, dt, schur3_flags, theta_h, velz_h, rho_h, rt_h, exner_h, F_w, F_rho, F_rt, F_exner,
                                               d_w, d_rho, d_rt, d_exner, nullptr), "solve_schur_3");                              // :1156
             check(mimsem_column_newton2_update(c, d_w, d_rho, d_rt, d_exner, velz, rho, rt, exner, velz_j, rho_j, rt_j, exner_j,
                                                velz_h, rho_h, rt_h, exner_h, nrm), "newton2_update");                             // :1159-1183
-        }, [&](const double* mx) { history.push_back({mx[0], mx[1], mx[2], mx[3]}); return mx[0] < tol && mx[2] < tol && mx[3] < tol; });   // :1202
+        }, [&](const double* mx) { history.push_back({mx[0], mx[1], mx[2], mx[3]}); return mx[0] < tol && mx[2] < tol && mx[3] < tol; },    // :1202
+        theta_up, [&] { if (centred) vert_mom_vort(velz_j, uuz_j); });                                                            // box :1403
     }
 
 private:
-    double *F_rt, *d_rt, *hs;
+    double *F_rt, *d_rt, *hs, *uuz_j, *add_w;
 };
 
 }  // namespace mimsem_host

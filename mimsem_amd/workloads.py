@@ -81,14 +81,15 @@ def write_tsw_case(path, dm, fg, dt, nsteps, use_graph=True, m1h_its=16, quad=No
 
 
 def write_euler_case(path, mesh, levs, quad_coords, state, dt, nsteps, hs_lat=None, newton_maxit=20, newton_tol=1.0e-12, vort_its=0,
-                     do_visc=True, m1_steps=0, eng=None):
+                     do_visc=True, m1_steps=0, eng=None, box_lx=None):
     """A 3-D Euler case for the C++ host (tests/cpp/test_euler.cpp, mimsem_amd/host/euler_call.cpp over mimsem_euler.hpp): the tables of a
     DeviceMesh (global numbering, nk >= 2), what the host does not diagnose itself -- the Coriolis 0-form fg [nk, n0] of HorizSolve.coriolis
     from quad_coords [nq, 3] and the geopotential zv [nEl, nk n2e] of VertSolve.init_gz from levs [nk+1, nq], both made here on the device
     (eng: an Engine of the mesh, made when None) --, the start state (velx, velz, rho, rt, exner) in Euler.strang_ec's layouts (host arrays or
     tensors) and the step parameters.  hs_lat [nEl, mp12]: Held-Suarez forcing with that latitude field; vort_its > 0: the count VortDiag's
     fixed-length solves start with (tests: 1 must miss its check), 0: found adaptively; m1_steps > 0: the Chebyshev solves of M1 cut to that
-    many steps (tests: 4 must miss)"""
+    many steps (tests: 4 must miss).  box_lx: the case is the doubly periodic box of that side (tests/cpp/test_box_euler.cpp, euler_call's box
+    case over box::Euler): no Coriolis form is written, `lx` [1] is; the mesh is one patch with uniform layers, quad_coords is not read"""
     import numpy as np
     from .device import Engine
     from .horizsolve import HorizSolve
@@ -96,8 +97,11 @@ def write_euler_case(path, mesh, levs, quad_coords, state, dt, nsteps, hs_lat=No
     eng = Engine(mesh) if eng is None else eng
     host = lambda t: np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float64)
     a = mesh_arrays(mesh)
-    h = HorizSolve(eng, del2=0.0, quad_coords=quad_coords)
-    a.update(fg=host(h.fg.expand(eng.nk, -1)).ravel(), zv=host(VertSolve(eng, dt).init_gz(levs)).ravel(),
+    if box_lx is None:
+        a["fg"] = host(HorizSolve(eng, del2=0.0, quad_coords=quad_coords).fg.expand(eng.nk, -1)).ravel()
+    else:
+        a["lx"] = np.array([box_lx], dtype=np.float64)
+    a.update(zv=host(VertSolve(eng, dt).init_gz(levs)).ravel(),
              dt=np.array([dt], dtype=np.float64), newton_tol=np.array([newton_tol], dtype=np.float64),
              opts=np.array([nsteps, 0 if hs_lat is None else 1, newton_maxit, vort_its, int(do_visc), m1_steps], dtype=np.int32))
     for k, v in zip(("velx", "velz", "rho", "rt", "exner"), state):

@@ -37,6 +37,8 @@ def parse(argv):
     ap.add_argument("--newton-maxit", type=int, default=20)
     ap.add_argument("--fused-forcing", action="store_true", help="momentum_rhs through mimsem_horiz_momentum_forcing")
     ap.add_argument("--profile", default=None, help="write the summary to this file as well")
+    ap.add_argument("--write-case", default=None, metavar="PATH",
+                    help="write the initial state as a case for the C++ host (mimsem_amd/host/euler_call.cpp, workloads.write_euler_case) and stop")
     ap.add_argument("--time-limit", type=float, default=1200.0)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     return ap.parse_args(argv)
@@ -81,6 +83,13 @@ def work(a):
     torch.cuda.synchronize()
     print("mesh, engine and %s: %.1f s (init1 solves redone: %d)" % ("restart" if a.start_step else "initial state", time.perf_counter() - t0, eu.init1_redone),
           flush=True)
+    if a.write_case:
+        from mimsem_amd import bubble as bb
+        from mimsem_amd.workloads import write_euler_case
+        write_euler_case(a.write_case, eng.mesh, bb.levels(a.nk, eu.xq, a.ztop), None, state, a.dt, a.nsteps, newton_maxit=a.newton_maxit,
+                         do_visc=False, eng=eng, box_lx=a.lx)
+        print("case for the C++ host written to %s" % a.write_case, flush=True)
+        return 0
     ms, newton, lines = [], [], []
     inner = eu.strang
 
